@@ -39,19 +39,23 @@ roofline (dominant kernel = the timed launch; duration from HIP events on the la
 cpu_baseline: the C oracle (oracle/, a port of the reference's NumPy step) timed on host cores over a bounded
 sample of the same workload.
 
-Output: the LAST stdout line is ONE compact JSON object (< 4 KB: the contract keys, ``roofline``, ``cpu_baseline``, and
-``legs`` = one short row per secondary measurement).  Everything longer - workload descriptions, byte definitions, every
-secondary leg in full, device state, the CPU thread scan, calibration - goes to ``--detail`` (default
-``gpurun_out/bench_detail.json``), named by the line's ``detail`` key; nothing else is printed to stdout, and stderr
-stays quiet unless something fails.  (Round 4's single 22 KB line could not be recovered from the driver's 8 KB tail.)
+Output: the LAST stdout line is ONE compact JSON object (< 4 KB: the contract keys, ``roofline``, and with ``--full`` also
+``cpu_baseline`` and ``legs`` = one short row per secondary measurement).  A plain run measures the headline only; ``--full``
+adds, after it, the CPU baselines, the secondary legs, the device sampler, the multi-rank C3 leg and exchange check, and the
+full record - workload descriptions, byte definitions, every secondary leg in full, device state, the CPU thread scan,
+calibration - in ``--detail`` (default ``bench_out/bench_detail.json``), named by the line's ``detail`` key; nothing else is
+printed to stdout, and stderr stays quiet unless something fails.  (Round 4's single 22 KB line could not be recovered from the driver's 8 KB tail.)
 Default ``--secondary`` = the per-step kernel at three batch sizes, BASELINE configs[2]'s per-GPU shard (plain and chunk-major
 trajectories), configs[3] and configs[4]'s per-GPU shard with the policy in-kernel (~1 s each), and the sustained stretch (11 s of the headline launches, so that an outside GPU-busy
-sampler cannot miss it); with the 10 s + 3 s CPU baselines the default run takes ~30 s.  ``--secondary all`` adds the
+sampler cannot miss it); with the 10 s + 3 s CPU baselines a ``--full`` run takes ~30 s.  ``--secondary all`` adds the
 policy-in-kernel rollouts, ReinmavEnv, the gym-shaped env and the VecEnv (~25 s more).
+``--dump-outputs DIR`` writes the last timed launch's outputs as float32 ``DIR/<name>.npy`` with the env axis last (rollout:
+actions, obs, rew, done; step: obs = state, rew, done; a fixed seeded sample of the envs past 32 MiB; rank 0's shard).
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -355,6 +359,42 @@ def step_leg(g, torch, dev, kind: str, n: int, K: int, W: int, tune=None):
                                                            "(tools/micro/launch_floor.hip): a bound on any one-launch-per-step kernel at small batches"})}
 
 
+DUMP_BYTES = 32 << 20   # --dump-outputs: at most this many bytes of arrays (a seeded sample of the envs beyond it)
+
+
+def sample_envs(t, layout: str, idx, ce: int = 0):
+    """The envs ``idx`` (a long tensor) of one output array as float32 numpy with the env axis last: [T][dim][k] / [T][k] for
+    trajectories in any rollout layout (soa [T](dim)[N], aos [T][N](dim), chunked [C][T](dim)[ce]), [dim][k] / [k] for
+    per-env arrays (layout 'soa')."""
+    import torch
+
+    t = torch.as_tensor(t)
+    idx = idx.to(t.device)
+    if layout == "chunked":
+        x = t[idx // ce, ..., idx % ce].movedim(0, -1)
+    elif layout == "aos":
+        x = t[:, idx].transpose(1, 2) if t.dim() == 3 else t[:, idx]
+    else:
+        x = t[..., idx]
+    return x.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(path: str, arrays: dict, layout: str, n: int, ce: int = 0):
+    """--dump-outputs: ``arrays`` (name -> device tensor or host array, env axis as in ``layout``) as ``path/<name>.npy``,
+    restricted to a fixed seeded sample of the n envs when all of them would exceed DUMP_BYTES."""
+    import numpy as np
+    import torch
+
+    one = torch.zeros(1, dtype=torch.int64)
+    per_env = sum(sample_envs(a, layout, one, ce).nbytes for a in arrays.values())
+    k = min(n, max(1, DUMP_BYTES // per_env))
+    idx = np.arange(n) if k == n else np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+    idx = torch.from_numpy(idx.astype(np.int64))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), sample_envs(a, layout, idx, ce))
+
+
 def leg_rows(other: dict) -> dict:
     """One short row per secondary leg for the compact line (the full objects go to the detail file)."""
     legs = {}
@@ -429,21 +469,31 @@ def main():
     ap.add_argument("--exchange-every", type=int, default=1,
                     help="multi-rank runs: post the episode-stats all-gather after every k-th rollout launch (default 1 = every launch)")
     ap.add_argument("--action-ring", type=int, default=64, help="step mode: number of pre-generated action buffers")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the other modes' short measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: CPU baselines, the secondary legs, device state, "
+                         "the detail file (a plain run does only the headline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computed in its last launch to DIR/<name>.npy (float32, <= 32 MiB: a fixed "
+                         "seeded sample of the envs)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the other modes' short measurements")
     ap.add_argument("--tune", default="", help="comma list of key=value overrides of the launch heuristics (rmav_set_tuning), "
                                                "e.g. split=0,store_policy=2")
     ap.add_argument("--sustained-seconds", type=float, default=11.0,
                     help="length of the `sustained` leg: the headline launches back to back, long enough for an outside GPU-busy sampler "
                          "with a 5 s period to see at least two busy samples")
-    ap.add_argument("--secondary", default="step,sustained,cpu_mt,c3_shard,c4,c5",
-                    help="comma list of the other measurements (single process only): step (k_step at 65 536 / 262 144 / 1 048 576 envs), "
-                         "sustained, in_place, c3_shard, c4, c4_pe, reinmav, gym1, vecenv, policy, cpu_mt (OpenMP CPU baseline), cpu_py; "
-                         "'all' = every one of them (~25 s more)")
+    ap.add_argument("--secondary", default=None,
+                    help="--full: comma list of the other measurements (single process only): step (k_step at 65 536 / 262 144 / 1 048 576 "
+                         "envs), sustained, in_place, c3_shard, c4, c4_pe, reinmav, gym1, vecenv, policy, cpu_mt (OpenMP CPU baseline), cpu_py; "
+                         "'all' = every one of them (~25 s more); default step,sustained,cpu_mt,c3_shard,c4,c5")
     ap.add_argument("--detail", default=None,
-                    help="file that receives the full record (every leg, descriptions, device state); default gpurun_out/bench_detail.json "
-                         "(bench_detail_n<N>.json for N > 1); '-' = none")
+                    help="--full: file that receives the full record (every leg, descriptions, device state); default "
+                         "bench_out/bench_detail.json (bench_detail_n<N>.json for N > 1); '-' = none")
     args = ap.parse_args()
+    if args.secondary is not None and not args.full:
+        ap.error("--secondary selects legs of a --full run")
+    if args.secondary is None:
+        args.secondary = "step,sustained,cpu_mt,c3_shard,c4,c5"
 
     import torch
     import torch.distributed as dist
@@ -589,7 +639,12 @@ def main():
                                 exchange.post(torch.from_numpy(eb["last_return"]), torch.from_numpy(eb["last_length"]))
                             else:
                                 exchange.post(env=env)
-                return run, chunk, R
+
+                def last():   # the buffer set of the latest launch: what the caller receives, in args.layout
+                    b = ring[(it[0] - 1) % R]
+                    names = ("obs", "rew", "done") if args.actions == "buffer" else ("actions", "obs", "rew", "done")
+                    return {k: b[k] for k in names}, args.layout, ce
+                return run, chunk, R, last
             # step mode: one launch per env-step; the launch loop runs inside librmav (rmav_rollout with
             # fused=0), so Python/ctypes overhead is paid once per RING launches.  State is updated in
             # place (obs == state, as SURVEY.md 8d defines the 101 algorithmic bytes); reward and done
@@ -598,18 +653,25 @@ def main():
             bufs = {"rew": torch.empty((RING, n), dtype=torch.float32, device=dev),
                     "done": torch.empty((RING, n), dtype=torch.uint8, device=dev)}
 
+            latest = [0]
+
             def run(k):
                 while k > 0:
                     m = min(k, RING)
                     env.rollout(m, mode="buffer", actions=ring[:m], layout="soa", fused=False, want=("rew", "done"),
                                 out={"rew": bufs["rew"][:m], "done": bufs["done"][:m]})
+                    latest[0] = m - 1
                     k -= m
-            return run, 1, 1
+
+            def last():   # the state after the latest launch (obs == state) and that launch's reward / done
+                return ({"obs": env.get_state(layout="soa"), "rew": bufs["rew"][latest[0]], "done": bufs["done"][latest[0]]},
+                        "soa", 0)
+            return run, 1, 1, last
 
         prewarm_launches = [0]
 
         def measure(mode, chunk, K, W, in_place=False, prewarm_ms=0.0):
-            run, per_launch, R = make_runner(mode, chunk, in_place)
+            run, per_launch, R, last = make_runner(mode, chunk, in_place)
             if prewarm_ms > 0:
                 # The first ~5 ms of GPU work after idle run ~15 % slow on these boxes (clock ramp).  A short --steps /
                 # --warmup (the driver runs 20 / 5) would sit entirely inside that ramp, so the headline is preceded by an
@@ -642,20 +704,23 @@ def main():
                 wall = float(w.item())
                 if gathered is not None:
                     assert gathered[0].numel() == n_total and gathered[1].numel() == n_total
-            return wall, kernel_ms, per_launch, R, gathered
+            return wall, kernel_ms, per_launch, R, gathered, last
 
         other = {}
-        single = not use_dist and not args.no_secondary
+        single = args.full and not use_dist and not args.no_secondary
         sec = set(args.secondary.split(",")) if single else set()
         all_legs = "all" in sec
         if "all" in sec:
             sec = {"in_place", "step", "c3_shard", "c4", "c4_pe", "reinmav", "gym1", "vecenv", "policy", "sustained", "cpu_mt", "cpu_py"}
         # the headline measurement: W untimed launches, then exactly K timed ones.  (The first ~5 ms of GPU work
         # after idle run ~15 % slower on these boxes, so the defaults are sized well past that.)
-        with DeviceSampler(dev.index or 0) as sampler:
-            wall, kernel_ms, per_launch, R, gathered = measure(args.mode, args.chunk, args.steps, args.warmup, args.in_place,
-                                                               prewarm_ms=args.prewarm_ms)
-        device_state = sampler.summary()
+        with (DeviceSampler(dev.index or 0) if args.full else contextlib.nullcontext()) as sampler:
+            wall, kernel_ms, per_launch, R, gathered, last = measure(args.mode, args.chunk, args.steps, args.warmup, args.in_place,
+                                                                     prewarm_ms=args.prewarm_ms)
+        device_state = sampler.summary() if args.full else None
+        if args.dump_outputs and rank == 0:   # before any other leg reuses the ring
+            arrays, layout_, ce_ = last()
+            dump_outputs(args.dump_outputs, arrays, layout_, n, ce_)
         # (round 6: the headline is measured FIRST, the long sustained stretch LAST - the other configs' legs used to run ahead of the
         #  headline and left the package at its power limit: the 20 timed launches of the driver's command came out 3 - 8 % below the
         #  sustained rate; and C4's fp64 kernel measured right after 11 s at the power limit loses 15 %)
@@ -666,7 +731,7 @@ def main():
                     key = "step" if n_s == n else f"step_{n_s}"
                     other[key] = step_leg(g, torch, dev, kind, n_s, max(400, 4000 * 65536 // max(n_s, 65536)), 200, tune=tune)
             if args.mode == "rollout" and "in_place" in sec and not args.in_place:
-                w2, k2, pl2, _, _ = measure("rollout", args.chunk, 500, 100, in_place=True)
+                w2, k2, pl2, _, _, _ = measure("rollout", args.chunk, 500, 100, in_place=True)
                 b2 = fused_bytes_per_launch(n, args.chunk, nS, nA)
                 other["rollout_in_place"] = {
                     "note": "one trajectory buffer set rewritten every launch: at 65 536 envs its 256 MB sit in the "
@@ -700,14 +765,14 @@ def main():
             # 2.5 s stretch was missed by all four of the driver's samples)
             k_s = max(args.steps, int(args.sustained_seconds / max(1e-6, kernel_ms * 1e-3)))
             with DeviceSampler(dev.index or 0) as sampler2:
-                w_s, kms_s, pl_s, _, _ = measure(args.mode, args.chunk, k_s, 0, args.in_place, prewarm_ms=0.0)
+                w_s, kms_s, pl_s, _, _, _ = measure(args.mode, args.chunk, k_s, 0, args.in_place, prewarm_ms=0.0)
             other["sustained"] = {"workload": f"the headline launches, back to back for >= {args.sustained_seconds:g} s", "seconds": w_s, "launches": k_s,
                                   "value": n_total * pl_s * k_s / w_s, "unit": "env-steps/s", "ms_per_launch_hip_events": kms_s,
                                   "roofline_frac": fused_bytes_per_launch(n, pl_s, nS, nA) / (kms_s * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                   "device_state": sampler2.summary()}
         totals = env.episode_totals()
         exchange_check = None
-        if use_dist and exchange is not None and args.mode == "rollout":
+        if args.full and use_dist and exchange is not None and args.mode == "rollout":
             # outside the timed region: one more exchange of the final per-env statistics, checked element by element
             # against a plain torch.distributed all-gather of the same buffers (global env order = rank order here)
             during = [t.clone() for t in gathered] if gathered is not None else None   # the timed region's last exchange
@@ -734,7 +799,7 @@ def main():
             exchange_check = bool(okf.item())
         if use_dist:
             totals = all_reduce_totals(totals, device="cpu" if gloo else dev)
-        if use_dist and kind == "quad3d" and args.mode == "rollout" and n != 131072 and not args.no_secondary:
+        if args.full and use_dist and kind == "quad3d" and args.mode == "rollout" and n != 131072 and not args.no_secondary:
             # BASELINE configs[2]'s shape beside the weak-scaling series: 131 072 envs on EVERY rank (world = 8: exactly C3's 1 048 576),
             # sharded by global env id, no exchange in this leg; barrier on both sides, slowest rank counts
             try:
@@ -851,13 +916,13 @@ def main():
         detail["config"] = dict(line["config"], workload=workload_long, parallelism=parallelism_long)
         detail["roofline"] = roof_long
         detail["device_state"] = device_state
-        detail["host_cpus"] = hc = host_cpus()
+        detail["host_cpus"] = hc = host_cpus() if args.full else None
         if other:
             detail["other_modes"] = other
         calib = os.path.join(ROOT, "profiles", "cpu_calibration.json")
-        if os.path.exists(calib):   # build-CPU / reference ratio per kind, measured in the authoring container (oracle/calibrate.py)
+        if args.full and os.path.exists(calib):   # build-CPU / reference ratio per kind (oracle/calibrate.py)
             detail["calibration"] = json.load(open(calib))
-        if world == 1 and not use_dist and args.cpu_seconds > 0 and kind != "reinmav":
+        if args.full and world == 1 and not use_dist and args.cpu_seconds > 0 and kind != "reinmav":
             cb = cpu_baseline(kind, n, args.chunk, lo, hi, args.cpu_seconds, threads=1)
             detail["cpu_baseline"] = cb
             line["cpu_baseline"] = dict(cb, sample=f"{kind} C oracle (fp64 scalar port of the reference step), {n} envs, random actions + auto-reset, "
@@ -894,9 +959,9 @@ def main():
             line["legs"] = legs
         if "sustained" in other:   # the robust figure beside the K timed launches: the same launches over --sustained-seconds
             line["value_sustained"] = float(f"{other['sustained']['value']:.5g}")
-        dpath = args.detail
+        dpath = args.detail if args.full else "-"
         if dpath is None:
-            dpath = os.path.join(ROOT, "gpurun_out", "bench_detail.json" if world == 1 else f"bench_detail_n{world}.json")
+            dpath = os.path.join(ROOT, "bench_out", "bench_detail.json" if world == 1 else f"bench_detail_n{world}.json")
         if dpath != "-":
             try:
                 os.makedirs(os.path.dirname(os.path.abspath(dpath)), exist_ok=True)

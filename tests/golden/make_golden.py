@@ -18,6 +18,7 @@ Contents per kind (all float64 unless noted):
   traj_s, traj_a, traj_s2, traj_r, traj_d  [4 seeds, 400 steps, ...] closed loop control()->step()
                                         with reset-on-done exactly like test/test_quadrotor3d.py:16-22
   (quad2d only) *_A variants of step_d/step_r/traj_* under reading A of quadrotor2d.py:95-98
+reinmav.npz, gravity.npz and random_cases.npz: see make_reinmav, make_gravity and make_random_cases.
 """
 from __future__ import annotations
 
@@ -265,10 +266,46 @@ def make_gravity():
     print("gravity", {k: v.shape for k, v in out.items() if k.endswith("_s")}, os.path.getsize(path), "bytes")
 
 
+def make_random_cases():
+    """Wide random single calls (tests/test_oracle_golden.py, tests/test_reinmav_host.py ::test_oracle_vs_live_reference): per
+    kind 300 x (state U[-2,2), action U[-12,12)) drawn in sequence from RandomState(99), the reference's control() and step()
+    from that state with steps_beyond_done=None; ReinmavEnv: 40 x (initial state + N(0, 0.05), clock U[0,5)) from
+    RandomState(3), one step() each.  Keys: <kind>_s, _a, _ctrl, _s2, _r, _d; reinmav_s, _t, _s2, _t2."""
+    out = {}
+    rng = np.random.RandomState(99)
+    for kind in rh.KINDS:
+        env = rh.RefEnv(kind)
+        S, A, C, S2, R, D = [], [], [], [], [], []
+        for _ in range(300):
+            s = rng.uniform(-2, 2, NS[kind])
+            a = rng.uniform(-12, 12, NA[kind])
+            env.set_state(s, sbd=None)
+            C.append(env.control())
+            o, r, d = env.step(a)
+            S.append(s), A.append(a), S2.append(o), R.append(r), D.append(d)
+        out[kind + "_s"], out[kind + "_a"], out[kind + "_ctrl"] = np.array(S), np.array(A), np.array(C)
+        out[kind + "_s2"], out[kind + "_r"], out[kind + "_d"] = np.array(S2), np.array(R), np.array(D, dtype=bool)
+    env = rh.RefReinmav()
+    rng = np.random.RandomState(3)
+    init = np.array([0, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 0], dtype=np.float64)   # reinmav_env.py:79 (oracle.REINMAV_INIT_STATE)
+    S, T, S2, T2 = [], [], [], []
+    for _ in range(40):
+        s = init + rng.normal(scale=0.05, size=13)
+        t = float(rng.uniform(0, 5))
+        env.set(s, t)
+        s2, _, _, t2 = env.step()
+        S.append(s), T.append(t), S2.append(s2), T2.append(t2)
+    out["reinmav_s"], out["reinmav_t"], out["reinmav_s2"], out["reinmav_t2"] = np.array(S), np.array(T), np.array(S2), np.array(T2)
+    path = os.path.join(HERE, "random_cases.npz")
+    np.savez_compressed(path, **out)
+    print("random_cases", {k: v.shape for k, v in out.items() if k.endswith("_s")}, os.path.getsize(path), "bytes")
+
+
 def main():
     assert rh.available(), "the reference tree is required to regenerate golden vectors"
     make_reinmav()
     make_gravity()
+    make_random_cases()
     errs = rh.selfcheck_quaternion()
     assert max(errs) < 1e-14, errs
     for kind in rh.KINDS:

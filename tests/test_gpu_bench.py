@@ -32,13 +32,14 @@ def _detail(j):
 
 @pytest.mark.timeout(600)
 def test_bench_driver_command_line_is_compact(built, tmp_path):
-    """The driver's own command (python bench.py --gpus 1 --steps 20 --warmup 5, default legs): last stdout line < 4 KB with the
-    contract keys, roofline.frac and cpu_baseline.value; the per-step kernel has a roofline row at 65 536, 262 144 and 1 048 576 envs."""
+    """The driver's own command with --full (python bench.py --gpus 1 --steps 20 --warmup 5 --full, default legs): last stdout line
+    < 4 KB with the contract keys, roofline.frac and cpu_baseline.value; the per-step kernel has a roofline row at 65 536, 262 144 and
+    1 048 576 envs."""
     import time
 
     d = str(tmp_path / "detail.json")
     t0 = time.time()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--detail", d],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--detail", d],
                        capture_output=True, text=True, timeout=550, cwd=ROOT)
     el = time.time() - t0
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -70,9 +71,47 @@ def test_bench_driver_command_line_is_compact(built, tmp_path):
     assert len(r.stderr) < 2000, r.stderr[-2000:]     # stderr stays quiet: the driver's tail appends it to stdout's
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(built, tmp_path):
+    """The plain command (no --full) measures the headline only: the contract keys, exactly --steps timed launches, no secondary
+    leg, no CPU baseline, no detail file, at most 30 s outside its launches.  --dump-outputs writes the last timed launch's
+    trajectory as float32 .npy files (<= 64 MB, a seeded sample of the envs), identical from run to run with the same arguments."""
+    import time
+
+    import numpy as np
+
+    outs = []
+    for i, extra in enumerate(([], [], ["--mode", "step"])):
+        d = str(tmp_path / f"out{i}")
+        t0 = time.time()
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--dump-outputs", d] + extra, capture_output=True, text=True, timeout=550, cwd=ROOT)
+        el = time.time() - t0
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        j = _line(r.stdout)
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+            assert k in j, k
+        for k in ("legs", "cpu_baseline", "cpu_mt", "value_sustained", "detail"):
+            assert k not in j, k
+        assert j["steps"] == 20 and j["warmup"] == 5 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert el - (j["steps"] + j["warmup"]) * j["ms_per_step"] * 1e-3 < 30.0, el
+        files = sorted(os.listdir(d))
+        arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        outs.append(arrays)
+    a0, a1, st = outs
+    assert sorted(a0) == ["actions", "done", "obs", "rew"] and sorted(st) == ["done", "obs", "rew"]
+    k = a0["rew"].shape[1]
+    assert 0 < k < 65536 and a0["obs"].shape == (64, 10, k) and a0["actions"].shape == (64, 4, k) and a0["done"].shape == (64, k)
+    assert set(np.unique(a0["done"])) <= {0.0, 1.0}
+    assert all(np.array_equal(a0[n], a1[n]) for n in a0)                  # same arguments, same outputs
+    assert st["obs"].shape == (10, st["rew"].shape[0]) and st["done"].shape == st["rew"].shape
+
+
 @pytest.mark.timeout(900)
 def test_bench_single_process_line(built):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "50", "--cpu-seconds", "1", "--secondary", "all"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "50", "--full", "--cpu-seconds", "1", "--secondary", "all"],
                        capture_output=True, text=True, timeout=850, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     short = _line(r.stdout)
@@ -116,7 +155,7 @@ def test_bench_two_ranks_on_one_gpu(built):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    common = ["--steps", "12", "--warmup", "3", "--cpu-seconds", "0", "--no-secondary", "--chunk", "32"]
+    common = ["--steps", "12", "--warmup", "3", "--full", "--cpu-seconds", "0", "--no-secondary", "--chunk", "32"]
     env = dict(os.environ, RMAV_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                          "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
@@ -145,7 +184,7 @@ def test_bench_under_torchrun_single_rank_rccl(built):
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40",
-                        "--warmup", "10", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=850, cwd=ROOT)
+                        "--warmup", "10", "--full", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=850, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = _line(r.stdout)
     assert j["n_gpus"] == 1 and j["config"]["gathered_envs_with_a_finished_episode"] > 0
@@ -155,7 +194,7 @@ def test_bench_under_torchrun_single_rank_rccl(built):
     # the torch.distributed exchange (the fallback) gives the same statistics
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                          "127.0.0.1", "--master-port", str(port + 1), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40",
-                         "--warmup", "10", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=850, cwd=ROOT,
+                         "--warmup", "10", "--full", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=850, cwd=ROOT,
                         env=dict(os.environ, RMAV_BENCH_EXCHANGE="torch"))
     assert r2.returncode == 0, r2.stdout[-2000:] + r2.stderr[-3000:]
     j2 = _line(r2.stdout)
@@ -177,7 +216,7 @@ def test_bench_two_gpus_native_exchange(built):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    common = ["--steps", "40", "--warmup", "10", "--prewarm-ms", "0", "--cpu-seconds", "0", "--no-secondary"]
+    common = ["--steps", "40", "--warmup", "10", "--prewarm-ms", "0", "--full", "--cpu-seconds", "0", "--no-secondary"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                          "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
@@ -214,7 +253,7 @@ def test_bench_eight_gpus_is_baseline_c3(built):
             port = s.getsockname()[1]
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                             "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "200", "--warmup", "50",
-                            "--cpu-seconds", "0"] + extra, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
+                            "--full", "--cpu-seconds", "0"] + extra, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
         j = _line(r.stdout)
         c = j["config"]

@@ -174,7 +174,7 @@ def test_bench_two_ranks_one_gpu_native_exchange(stub):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    common = ["--steps", "30", "--warmup", "6", "--prewarm-ms", "0", "--cpu-seconds", "0", "--no-secondary", "--chunk", "32"]
+    common = ["--steps", "30", "--warmup", "6", "--prewarm-ms", "0", "--full", "--cpu-seconds", "0", "--no-secondary", "--chunk", "32"]
     env = dict(os.environ, RMAV_BENCH_BACKEND="gloo", RMAV_BENCH_RCCL_LIB=STUB, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                          "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
@@ -202,7 +202,7 @@ def test_bench_eight_ranks_one_gpu_is_the_eight_gpu_launch(stub):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    common = ["--steps", "16", "--warmup", "4", "--prewarm-ms", "0", "--cpu-seconds", "0", "--no-secondary", "--chunk", "32"]
+    common = ["--steps", "16", "--warmup", "4", "--prewarm-ms", "0", "--full", "--cpu-seconds", "0", "--no-secondary", "--chunk", "32"]
     env = dict(os.environ, RMAV_BENCH_BACKEND="gloo", RMAV_BENCH_RCCL_LIB=STUB, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r8 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
                          "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8",
@@ -225,7 +225,7 @@ def test_bench_eight_ranks_one_gpu_is_the_eight_gpu_launch(stub):
 
 @pytest.mark.timeout(900)
 def test_bench_multi_gpu_line_carries_the_c3_leg(stub):
-    """Without --no-secondary a multi-rank bench line also measures BASELINE configs[2]'s shape: 131 072 envs on every rank,
+    """With --full and without --no-secondary a multi-rank bench line also measures BASELINE configs[2]'s shape: 131 072 envs on every rank,
     barrier-bracketed, slowest rank counts (two ranks sharing the one GPU here, so only the plumbing is checked, not the rate)."""
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -233,7 +233,7 @@ def test_bench_multi_gpu_line_carries_the_c3_leg(stub):
     env = dict(os.environ, RMAV_BENCH_BACKEND="gloo", RMAV_BENCH_RCCL_LIB=STUB, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30",
-                        "--warmup", "6", "--prewarm-ms", "0", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
+                        "--warmup", "6", "--prewarm-ms", "0", "--full", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=850, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["config"]["envs_per_gpu"] == 65536 and j["scaling"] == "weak"

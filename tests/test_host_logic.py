@@ -146,6 +146,39 @@ def test_bench_byte_accounting():
     assert b.HBM_PEAK_GBS == 8000.0
 
 
+def test_bench_dump_outputs_sample_every_layout(tmp_path):
+    """bench.py --dump-outputs: the same envs come out of the plain, batch-major and chunk-major trajectory layouts (a ragged last
+    chunk included) with the env axis last; past the byte budget a seeded sample in env order, the same one every time."""
+    import importlib.util
+
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    T, d, n, ce = 3, 4, 200, 64
+    obs, rew = torch.randn(T, d, n), torch.randn(T, n)
+    C = -(-n // ce)
+    obs_c, rew_c = torch.zeros(C, T, d, ce), torch.zeros(C, T, ce)
+    for e in range(n):
+        obs_c[e // ce, :, :, e % ce], rew_c[e // ce, :, e % ce] = obs[:, :, e], rew[:, e]
+    idx = torch.tensor([0, 5, 63, 64, 130, 199])
+    for layout, o, r in (("soa", obs, rew), ("aos", obs.permute(0, 2, 1).contiguous(), rew), ("chunked", obs_c, rew_c)):
+        assert np.array_equal(b.sample_envs(o, layout, idx, ce), obs[:, :, idx].numpy()), layout
+        assert np.array_equal(b.sample_envs(r, layout, idx, ce), rew[:, idx].numpy()), layout
+    state = np.random.RandomState(0).randn(d, n).astype(np.float32)     # step mode: per-env arrays, host or device, any dtype
+    assert np.array_equal(b.sample_envs(state, "soa", idx), state[:, idx])
+    assert b.sample_envs(torch.ones(n, dtype=torch.uint8), "soa", idx).dtype == np.float32
+    b.DUMP_BYTES = 4 * (T * d + T) * 50                                   # room for 50 of the 200 envs
+    for k in range(2):
+        b.dump_outputs(str(tmp_path / str(k)), {"obs": obs_c, "rew": rew_c}, "chunked", n, ce)
+    o0, o1 = (np.load(tmp_path / str(k) / "obs.npy") for k in range(2))
+    r0 = np.load(tmp_path / "0" / "rew.npy")
+    assert o0.shape == (T, d, 50) and r0.shape == (T, 50) and o0.dtype == r0.dtype == np.float32 and np.array_equal(o0, o1)
+    pick = [int(np.flatnonzero((obs[0, 0] == v).numpy())[0]) for v in torch.from_numpy(o0[0, 0])]
+    assert pick == sorted(set(pick)) and np.array_equal(r0, rew[:, pick].numpy())
+
+
 def test_bench_device_sampler_summary():
     """bench.py's device_state: only samples taken while the GPU was busy count; unreadable sysfs gives None fields."""
     import importlib.util

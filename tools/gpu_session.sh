@@ -3,7 +3,7 @@
 # Usage (from the repo root, via gpurun):  bash tools/gpu_session.sh <tag> <stage> [<stage> ...]
 # Everything is written under gpurun_out/<tag>/; copy what is cited into profiles/.
 #   base      device.txt, smoke(), pytest -m gpu
-#   bench     bench.py with its defaults, and with the driver's --steps 20 --warmup 5
+#   bench     bench.py --full with its defaults, and with the driver's --steps 20 --warmup 5
 #   legs      the other single-GPU BASELINE configs as their own bench lines (C3's shard, C4)
 #   sweep     kernel sweep: kinds x {random, controller} at SWEEP_N (default "65536 131072") -> sweep.md
 #             (SWEEP_TUNE="split=0" adds rmav_set_tuning overrides; SWEEP_TAG names the output: sweep$SWEEP_TAG.md)
@@ -46,8 +46,8 @@ base)
   timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
   ;;
 bench)
-  timeout 900 $B --secondary all --detail $OUT/bench_n1_detail.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "rc=$?"; line $OUT/bench_n1.json
-  ( time timeout 900 $B --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_n1_k20_detail.json > $OUT/bench_n1_k20.json 2> $OUT/bench_n1_k20.err ) 2>&1 | grep real; line $OUT/bench_n1_k20.json
+  timeout 900 $B --full --secondary all --detail $OUT/bench_n1_detail.json > $OUT/bench_n1.json 2> $OUT/bench_n1.err; echo "rc=$?"; line $OUT/bench_n1.json
+  ( time timeout 900 $B --gpus 1 --steps 20 --warmup 5 --full --detail $OUT/bench_n1_k20_detail.json > $OUT/bench_n1_k20.json 2> $OUT/bench_n1_k20.err ) 2>&1 | grep real; line $OUT/bench_n1_k20.json
   ;;
 legs)
   timeout 600 $B --envs-per-gpu 131072 --cpu-seconds 0 --no-secondary > $OUT/bench_c3shard.json 2>/dev/null; line $OUT/bench_c3shard.json
@@ -76,7 +76,7 @@ steplat)
   timeout 900 python tools/step_latency.py quad3d > $OUT/step_latency.txt 2>&1; tail -30 $OUT/step_latency.txt
   ;;
 vecenv)
-  timeout 600 $B --steps 200 --warmup 50 --cpu-seconds 0 --secondary gym1,vecenv,step > $OUT/bench_vecenv.json 2> $OUT/bench_vecenv.err; line $OUT/bench_vecenv.json
+  timeout 600 $B --steps 200 --warmup 50 --full --cpu-seconds 0 --secondary gym1,vecenv,step > $OUT/bench_vecenv.json 2> $OUT/bench_vecenv.err; line $OUT/bench_vecenv.json
   ;;
 sq)
   EXTRA="$EXTRA" bash tools/pmc_sq.sh $TAG/sq > $OUT/sq_counters.txt 2>&1; tail -40 $OUT/sq_counters.txt
@@ -95,7 +95,7 @@ throttle)
   bash tools/throttle_probe.sh $TAG 2>&1 | grep -E "^(rollout|memset|compute)" 
   ;;
 dist1)
-  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 1 --envs-per-gpu 131072 > $OUT/bench_torchrun1_c3shard.json 2> $OUT/bench_dist1.err; echo "rc=$?"; line $OUT/bench_torchrun1_c3shard.json
+  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 1 --envs-per-gpu 131072 --full > $OUT/bench_torchrun1_c3shard.json 2> $OUT/bench_dist1.err; echo "rc=$?"; line $OUT/bench_torchrun1_c3shard.json
   ;;
 *) echo "unknown stage $STAGE";;
 esac

@@ -32,7 +32,7 @@ CASES=(
 # ReinmavEnv (k_rollout<4, 2, 0>) and the policy-in-kernel rollouts of C5's per-GPU shape (k_rollout<2, 3|8|4, 0>, k_rollout_pair<2, *>,
 # k_rollout_pair_shared<2>) - traced under the driver's own command line, so that the averages are comparable with other_modes.*
 if [ -z "$ONLY" ] || [[ " $ONLY " =~ " legs " ]]; then
-  run trace_legs --kernel-trace --stats --output-format csv -d $OUT/trace_legs -- python $REPO/bench.py --steps 20 --warmup 5 --cpu-seconds 0 --secondary c4_pe,reinmav,policy --detail -
+  run trace_legs --kernel-trace --stats --output-format csv -d $OUT/trace_legs -- python $REPO/bench.py --steps 20 --warmup 5 --full --cpu-seconds 0 --secondary c4_pe,reinmav,policy --detail -
 fi
 for c in "${CASES[@]}"; do
   name=${c%%|*}; args=${c#*|}
