@@ -189,6 +189,8 @@ int rmav_set_env_param(rmav_handle h, int which, const float *values, int mem);
 /* Explicit, per-handle overrides of the launch rules (DESIGN.md section 4 states the automatic rules and what was measured).
  * -1 = automatic, the default of every key.  Results never depend on them: every variant writes the same bits
  * (tests/test_gpu_parity.py::test_kernel_selection_variants_give_the_same_bits, ::test_single_step_variants_give_the_same_bits). */
+/* A handle with an episode time limit (rmav_set_time_limit) ignores the split and slice keys: its fused rollouts always run one
+ * wavefront per 64 envs (the two-wavefront kernels have no time-limited variant). */
 enum rmav_tuning_key {
     RMAV_TUNE_SPLIT = 0,        /* fused rollouts: 0 = one wavefront per 64 envs, 1 = (integrator, memory) wavefront pairs */
     RMAV_TUNE_SLICE = 1,        /* batches beyond the pair kernel's capacity: 0 = one launch, 1 = one launch per balanced slice */
@@ -281,6 +283,36 @@ int rmav_episode_totals(rmav_handle h, rmav_ep_totals *out, int clear); /* synch
  * running episode.  Any pointer may be NULL.  This is the payload of the per-rollout all-gather. */
 int rmav_episode_buffers(rmav_handle h, float *last_return, int32_t *last_length,
                          float *cur_return, int32_t *cur_length, int mem);
+
+/* ---- episode time limit (gym's TimeLimit / gym.make(id, max_episode_steps=H), inside the step kernels) ---------------------
+ * The reference registers its ids without max_episode_steps (gym_reinmav/__init__.py:3-26): its episodes end only when |pos| or |vel|
+ * leaves its box, so a hovering policy's never do.  Auto-reset and the episode statistics run inside the kernels, so the limit lives
+ * there too.  Callers detect the feature by these symbols (RMAV_VERSION is unchanged).
+ *   - A per-handle limit H (episode length in steps); H = 0 means no limit and is the default: a handle that never sets one behaves
+ *     exactly as without this feature.
+ *   - An env's running length L counts the steps since its episode began: at creation, at rmav_reset, or after its previous episode
+ *     ended.  A step after which L == H and the dynamics did not terminate is TRUNCATED: done = 1 (the done byte stays 0 or 1), the
+ *     reward is the step's ordinary -dist, steps_beyond_done is untouched (truncation is not termination), and the episode ends as on
+ *     termination - with RMAV_F_TRACK_EPISODES last_return, last_length = H and the totals are updated; with RMAV_F_AUTO_RESET a fresh
+ *     state is drawn by the same Philox counter rule and the reset counter advances.
+ *   - Termination wins: a step that terminates and reaches H is a termination (reference reward and steps_beyond_done, truncated
+ *     flag 0).
+ *   - Without RMAV_F_AUTO_RESET a truncation still ends the episode (statistics recorded, the length restarts from 0) but the state
+ *     is not reset: the next truncation comes H steps later.  gym's TimeLimit differs here - it reports done on every step after
+ *     the limit (stepping past done is undefined behaviour in gym).
+ *   - rmav_seed and rmav_set_step_count keep running lengths; rmav_set_state does not restart an episode.
+ *   - A handle created without RMAV_F_TRACK_EPISODES keeps no episode starts until it has a limit: rmav_set_time_limit (with H > 0)
+ *     starts every env's count at the call, and so does rmav_reset while a limit is set.  Tracking handles keep their exact running
+ *     lengths: an env already at or past H when the limit is set is truncated at its next step (L >= H counts as reaching it).
+ *   - Launches of a time-limited handle run kernels of their own: fused rollouts use the one-wavefront kernels
+ *     (RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk), rmav_rollout_policy supports
+ *     RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA and RMAV_POLICY_F16_SHARED (the others return RMAV_ERR_INVALID).
+ * max_episode_steps in [0, 2^30]; quadrotor kinds only (RMAV_REINMAV ends an episode on every step: RMAV_ERR_INVALID for H > 0). */
+int rmav_set_time_limit(rmav_handle h, int32_t max_episode_steps);
+int rmav_get_time_limit(rmav_handle h, int32_t *out);
+/* N bytes: 1 if the env's most recently finished episode was truncated by the limit, 0 if it terminated or none has finished since
+ * the handle first had a limit (written at every episode end of a time-limited handle, tracked or not). */
+int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,9 @@ int rmav_pack_policy(rmav_handle h, int n_params, const float *const *params, co
  * (gym_reinmav_amd.ppo.pack_policy_weights_f16 is the torch form of the same buffer). */
 int rmav_pack_policy_f16(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
                          const int32_t *idx_hi, int64_t n_out, float *weights_out);
+/* A handle with an episode time limit (rmav_set_time_limit) runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA and RMAV_POLICY_F16_SHARED;
+ * RMAV_POLICY_FP32 and RMAV_POLICY_BF16_MFMA return RMAV_ERR_INVALID there (no time-limited kernel: they already sit at their register
+ * limit).  A truncated step has done = 1 and its ordinary reward: rmav_gae treats it as an episode boundary without a bootstrap. */
 int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out,
                         float *obs_out, float *rew_out, uint8_t *done_out, float *logp_out,
                         float *value_out, int precision);

@@ -209,9 +209,57 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, p, pc);
     } else {
-        hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid_for(h), dim3(block_size(h)), lds, h->stream, a, p, pc);
+        if (h->time_limit > 0) {   // (one launch per chunk of a chunk-major call: launch_rollout_tl_km)
+            // (ACT_BUFFER_CTRL comes here only with n_steps > 1, which no entry point asks for: its single steps run k_step_tl)
+            if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+                const int64_t count = a.slice_count ? (int64_t)a.slice_count : h->n;
+                const dim3 grid((unsigned)((count + block_size(h) - 1) / block_size(h)));
+                hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h));
+            } else {
+                return rmav_fail(RMAV_ERR_INVALID, "no time-limited kernel for action mode %d", MODE);
+            }
+        } else {
+            hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid_for(h), dim3(block_size(h)), lds, h->stream, a, p, pc);
+        }
     }
     return check_rollout_launch(h, a);
+}
+
+// A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
+// variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
+template <int K, int MODE>
+int launch_rollout_tl_km(rmav_handle h, const RolloutArgs &a) {
+    if (h->chunk > 0) {
+        const int64_t per = h->chunk, T = a.n_steps;
+        constexpr int64_t NS = Dims<K>::NS, NA = Dims<K>::NA;
+        for (int64_t first = 0; first < h->n; first += per) {
+            // (the chunk-major pointer arithmetic of launch_rollout_km)
+            RolloutArgs b = a;
+            const int64_t c = first / per;
+            b.slice_first = (uint32_t)first;
+            b.slice_count = (uint32_t)((h->n - first < per) ? h->n - first : per);
+            b.pitch = per;
+            if (a.act_in) b.act_in = a.act_in + c * T * NA * per - first;
+            if (a.act_out) b.act_out = a.act_out + c * T * NA * per - first;
+            if (a.obs_out) b.obs_out = a.obs_out + c * T * NS * per - first;
+            if (a.rew_out) b.rew_out = a.rew_out + c * T * per - first;
+            if (a.done_out) b.done_out = a.done_out + c * T * per - first;
+            int rc;
+            switch (pick_store_policy(h, b, false)) {
+            case ST_WRITE_THROUGH: rc = launch_rollout_kms<K, MODE, ST_WRITE_THROUGH>(h, b); break;
+            case ST_STREAM: rc = launch_rollout_kms<K, MODE, ST_STREAM>(h, b); break;
+            default: rc = launch_rollout_kms<K, MODE, ST_DEFAULT>(h, b); break;
+            }
+            if (rc) return rc;
+        }
+        return RMAV_OK;
+    }
+    switch (pick_store_policy(h, a, false)) {
+    case ST_WRITE_THROUGH: return launch_rollout_kms<K, MODE, ST_WRITE_THROUGH>(h, a);
+    case ST_STREAM: return launch_rollout_kms<K, MODE, ST_STREAM>(h, a);
+    case ST_AOS_LDS: return launch_rollout_kms<K, MODE, ST_AOS_LDS>(h, a);
+    default: return launch_rollout_kms<K, MODE, ST_DEFAULT>(h, a);
+    }
 }
 
 // RMAV_TUNE_SPLIT = 0 | 1 overrides the rule.
@@ -246,6 +294,9 @@ bool use_split(rmav_handle h, const RolloutArgs &a, int action_mode, int *slices
 
 template <int K, int MODE>
 int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
+    if constexpr (K != REINMAV) {
+        if (h->time_limit > 0) return launch_rollout_tl_km<K, MODE>(h, a);
+    }
     {
         if constexpr ((MODE == ACT_RANDOM || MODE == ACT_CONTROLLER || MODE == ACT_BUFFER) && K != REINMAV) {
             constexpr int SMODE = (MODE == ACT_RANDOM) ? ACT_RANDOM_SPLIT : (MODE == ACT_BUFFER) ? ACT_BUFFER_SPLIT : ACT_CONTROLLER_SPLIT;
@@ -339,7 +390,13 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
         if (big) hipLaunchKernelGGL((k_step_big<K, LAZY, ST>), grid, dim3(bs), 0, h->stream, a, p, pc);               \
         else hipLaunchKernelGGL((k_step<K, false, LAZY, ST>), grid, dim3(bs), 0, h->stream, RMAV_STEP_ARGS);          \
     } while (0)
-    if (ctrl) hipLaunchKernelGGL((k_step<K, true>), grid, dim3(bs), 0, h->stream, RMAV_STEP_ARGS);
+    if (h->time_limit > 0) {   // every batch size: the eager record load, k_step's preloaded arguments (k_step_tl)
+        const dim3 grid_tl((unsigned)((h->n + bs - 1) / bs));
+        if (ctrl) hipLaunchKernelGGL((k_step_tl<K, true>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
+        else if (st == ST_STREAM) hipLaunchKernelGGL((k_step_tl<K, false, ST_STREAM>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
+        else if (st == ST_WRITE_THROUGH) hipLaunchKernelGGL((k_step_tl<K, false, ST_WRITE_THROUGH>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
+        else hipLaunchKernelGGL((k_step_tl<K, false>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
+    } else if (ctrl) hipLaunchKernelGGL((k_step<K, true>), grid, dim3(bs), 0, h->stream, RMAV_STEP_ARGS);
     else if (lazy && st == ST_STREAM) RMAV_STEP(true, ST_STREAM);
     else if (lazy && st == ST_WRITE_THROUGH) RMAV_STEP(true, ST_WRITE_THROUGH);
     else if (lazy) RMAV_STEP(true, ST_DEFAULT);
@@ -408,6 +465,34 @@ int launch_reset(rmav_handle h, float *obs_dev, int layout) {
     }
 #undef RMAV_RESET_CASE
     HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// The running episode of every env starts at the handle's clock: ep_start = clock (what k_reset does when the handle tracks episodes).
+int restart_episode_clocks(rmav_handle h) {
+    hipLaunchKernelGGL(k_rec_fill, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->rec, EnvRec{0, 0u, (uint32_t)h->t, 0}, 2,
+                       (int64_t)h->n);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// rmav_reset: k_reset keeps ep_start only when the handle tracks episodes; a time-limited handle that does not gets it restarted by
+// the record fill behind it (k_reset itself is unchanged)
+int launch_reset_tl(rmav_handle h, float *obs_dev, int layout) {
+    if (int rc = launch_reset(h, obs_dev, layout)) return rc;
+    if (h->time_limit > 0 && !(h->flags & RMAV_F_TRACK_EPISODES)) return restart_episode_clocks(h);
+    return RMAV_OK;
+}
+
+// last_trunc on first use: N zero bytes (no episode has been truncated yet)
+int ensure_last_trunc(rmav_handle h) {
+    if (h->last_trunc) return RMAV_OK;
+    if (hipMalloc((void **)&h->last_trunc, (size_t)h->n) != hipSuccess) {
+        (void)hipGetLastError();
+        h->last_trunc = nullptr;
+        return rmav_fail(RMAV_ERR_ALLOC, "device allocation of the truncated flags failed");
+    }
+    HIP_TRY(hipMemsetAsync(h->last_trunc, 0, (size_t)h->n, h->stream));
     return RMAV_OK;
 }
 
@@ -499,6 +584,7 @@ void free_all(rmav_handle h) {
         if (p) (void)hipFree(p);
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->done_flag) (void)hipHostFree(h->done_flag);
+    if (h->last_trunc) (void)hipFree(h->last_trunc);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     h->magic = 0;
     delete h;
@@ -718,7 +804,7 @@ int rmav_destroy(rmav_handle h) {
 // so running episode lengths carry over the jump
 static int move_step_counter(rmav_handle h, uint64_t t) {
     const uint32_t delta = (uint32_t)t - (uint32_t)h->t;
-    if (delta != 0u && (h->flags & RMAV_F_TRACK_EPISODES)) {
+    if (delta != 0u && ((h->flags & RMAV_F_TRACK_EPISODES) || h->time_limit > 0)) {
         hipLaunchKernelGGL(k_shift_ep_start, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->rec, delta, (int64_t)h->n);
         HIP_TRY(hipGetLastError());
     }
@@ -817,15 +903,15 @@ int rmav_reset(rmav_handle h, float *obs_out, int mem, int layout) {
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
     const size_t nobs = (size_t)h->n * kStateDim[h->kind];
-    if (mem == RMAV_DEVICE || !obs_out) return launch_reset(h, obs_out, layout);
+    if (mem == RMAV_DEVICE || !obs_out) return launch_reset_tl(h, obs_out, layout);
     if (nobs * sizeof(float) <= kPinnedMax && ensure_pinned(h, nobs * sizeof(float)) == RMAV_OK) {   // zero-copy
-        if (int rc = launch_reset(h, (float *)h->pinned_dev, layout)) return rc;
+        if (int rc = launch_reset_tl(h, (float *)h->pinned_dev, layout)) return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         memcpy(obs_out, h->pinned, nobs * sizeof(float));
         return RMAV_OK;
     }
     if (int rc = ensure_scratch(h, nobs * sizeof(float))) return rc;
-    if (int rc = launch_reset(h, (float *)h->scratch, layout)) return rc;
+    if (int rc = launch_reset_tl(h, (float *)h->scratch, layout)) return rc;
     return copy_out(h, (const float *)h->scratch, obs_out, nobs, RMAV_HOST);
 }
 
@@ -1100,6 +1186,9 @@ int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, fl
         return rmav_fail(RMAV_ERR_INVALID, "weights, logp_out and value_out are required (device pointers)");
     if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0)
         return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
+    if (h->time_limit > 0 && precision != RMAV_POLICY_FP32_MFMA && precision != RMAV_POLICY_F16_MFMA && precision != RMAV_POLICY_F16_SHARED)
+        return rmav_fail(RMAV_ERR_INVALID, "a time-limited handle runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
+                                           "(the fp32 vector-ALU and bf16 actors have no time-limited kernel)");
     RolloutArgs a = base_args(h);
     a.n_steps = n_steps;
     a.act_out = actions_out;
@@ -1281,6 +1370,36 @@ int rmav_episode_buffers(rmav_handle h, float *last_return, int32_t *last_length
     }
     if (mem == RMAV_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
     return RMAV_OK;
+}
+
+int rmav_set_time_limit(rmav_handle h, int32_t max_episode_steps) {
+    CHECK_HANDLE(h);
+    if (h->kind == RMAV_REINMAV && max_episode_steps != 0)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv ends an episode on every step: it takes no time limit");
+    if (max_episode_steps < 0 || max_episode_steps > (1 << 30))
+        return rmav_fail(RMAV_ERR_INVALID, "max_episode_steps must be in [0, 2^30] (0 = no limit), got %d", (int)max_episode_steps);
+    if (max_episode_steps > 0) {
+        if (int rc = ensure_last_trunc(h)) return rc;
+        // without episode tracking ep_start is not kept up to date: the running episodes count from this call
+        if (!(h->flags & RMAV_F_TRACK_EPISODES))
+            if (int rc = restart_episode_clocks(h)) return rc;
+    }
+    h->time_limit = max_episode_steps;
+    return RMAV_OK;
+}
+
+int rmav_get_time_limit(rmav_handle h, int32_t *out) {
+    CHECK_HANDLE(h);
+    if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
+    *out = h->time_limit;
+    return RMAV_OK;
+}
+
+int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, RMAV_SOA)) return rc;
+    if (int rc = ensure_last_trunc(h)) return rc;
+    return copy_out(h, (const uint8_t *)h->last_trunc, out, (size_t)h->n, mem);
 }
 
 // ---- learner-side helpers on the trajectory ----------------------------------------------------

@@ -79,7 +79,12 @@ struct rmav_env_s {
     } xchg;
     // explicit per-handle overrides of the launch heuristics (rmav_set_tuning); -1 / 0 = automatic
     int tune[RMAV_TUNE_COUNT];
+    // episode time limit (rmav_set_time_limit): 0 = none; > 0 routes every stepping launch to the *_tl kernels.  last_trunc: u8 [N]
+    // truncated flags of the last finished episodes, allocated (zero-filled) on first use
+    int32_t time_limit;
+    uint8_t *last_trunc;
 };
+inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 
 constexpr int kExchangeDepth = 8;   // buffer pairs of the overlapped statistics exchange
 // bounds of k_wait_arrivals, in ticks of the 100 MHz wall clock: 2 s once the armed launch has begun, 10 min overall

@@ -17,6 +17,7 @@ using namespace rmav;
 namespace {
 
 // one wavefront per 64 envs (32 for the fp32-MFMA actor: both half-waves work on the same 32 envs)
+// (time-limited handles: k_rollout_tl, ACT_POLICY_F32M only - rmav_rollout_policy refuses the other one-wavefront actors)
 template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs &a_in) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, MODE == ACT_POLICY_F32M ? 32 : 64);
@@ -25,8 +26,15 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
     const size_t lds = sizeof(float) * (MODE == ACT_POLICY ? (size_t)PolicyLayout<Dims<K>::NS>::TOTAL
                                         : MODE == ACT_POLICY_BF16 ? (size_t)MfmaLayout::TOTAL : (size_t)Mfma32Layout::TOTAL);
     const int64_t per_wg = MODE == ACT_POLICY_F32M ? block_size(h) / 2 : block_size(h);
-    hipLaunchKernelGGL((k_rollout<K, MODE, ST_DEFAULT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(block_size(h)), lds, h->stream,
-                       a, p, pc);
+    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg));
+    bool launched = false;
+    if constexpr (K != REINMAV && MODE == ACT_POLICY_F32M) {
+        if (h->time_limit > 0) {
+            hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h));
+            launched = true;
+        }
+    }
+    if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc);
     return check_rollout_launch(h, a);
 }
 
@@ -42,8 +50,17 @@ template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutAr
     // (one workgroup per CU, weights staged once per CU); 131 072 envs 2 pairs 15.8 - 16.7, 4 pairs 15.5 - 16.3, 1 pair 11.1
     const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : (h->n <= 98304 ? 4 : 2);
     const int64_t per_wg = 64 * g;
-    hipLaunchKernelGGL((k_rollout_pair<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
-                       h->stream, a, p, pc);
+    bool launched = false;
+    if constexpr (K != REINMAV && FMT == FMT_F16) {   // (time-limited handles: RMAV_POLICY_F16_MFMA only)
+        if (h->time_limit > 0) {
+            hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
+                               h->stream, a, p, pc, tl_args(h));
+            launched = true;
+        }
+    }
+    if (!launched)
+        hipLaunchKernelGGL((k_rollout_pair<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
+                           h->stream, a, p, pc);
     return check_rollout_launch(h, a);
 }
 
@@ -57,8 +74,17 @@ template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs
     // measured (profiles/r04/actor_bench.txt): 65 536 envs 1 / 2 / 4 pairs per workgroup 20.8 / 21.5 / 20.4 G env-steps/s, 131 072: 19.9 / 25.9 / 26.1
     const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : 2;
     const int64_t per_wg = 64 * g;
-    hipLaunchKernelGGL((k_rollout_pair_shared<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
-                       h->stream, a, p, pc);
+    bool launched = false;
+    if constexpr (K != REINMAV) {
+        if (h->time_limit > 0) {
+            hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
+                               h->stream, a, p, pc, tl_args(h));
+            launched = true;
+        }
+    }
+    if (!launched)
+        hipLaunchKernelGGL((k_rollout_pair_shared<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
+                           h->stream, a, p, pc);
     return check_rollout_launch(h, a);
 }
 

@@ -130,6 +130,9 @@ PROTOTYPES = {
     "rmav_set_step_count": (C.c_int, [C.c_void_p, C.c_uint64]),
     "rmav_episode_totals": (C.c_int, [C.c_void_p, C.POINTER(EpTotals), C.c_int]),
     "rmav_episode_buffers": (C.c_int, [C.c_void_p, _fp, _vp, _fp, _vp, C.c_int]),
+    "rmav_set_time_limit": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rmav_get_time_limit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
 }
 
 _lib = None

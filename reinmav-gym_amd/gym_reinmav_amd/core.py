@@ -41,7 +41,9 @@ class BatchedQuadrotor:
 
     def __init__(self, kind, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
-                 reading_2d: Optional[str] = None, use_torch_stream: bool = True):
+                 reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None):
+        """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
+        rmav_set_time_limit); None or 0 = no limit."""
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
@@ -62,6 +64,8 @@ class BatchedQuadrotor:
         A.check(self._lib.rmav_create(C.byref(h), self.kind, self.num_envs, self.device, seed & (2**64 - 1),
                                       env_id_base, flags, C.byref(p), stream))
         self._h = h
+        if max_episode_steps:
+            self.max_episode_steps = max_episode_steps
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -102,6 +106,25 @@ class BatchedQuadrotor:
     @params.setter
     def params(self, p: A.Params):
         A.check(self._lib.rmav_set_params(self._h, C.byref(p)))
+
+    @property
+    def max_episode_steps(self) -> Optional[int]:
+        """Episode time limit H, None if there is none.  A step after which an episode has run H steps without terminating
+        ends it as truncated (done = 1, :meth:`episode_truncated`); assignable at any time (None / 0 removes the limit)."""
+        v = C.c_int32()
+        A.check(self._lib.rmav_get_time_limit(self._h, C.byref(v)))
+        return v.value or None
+
+    @max_episode_steps.setter
+    def max_episode_steps(self, h: Optional[int]):
+        A.check(self._lib.rmav_set_time_limit(self._h, int(h or 0)))
+
+    def episode_truncated(self, device_out: bool = False):
+        """u8 [N]: 1 where the env's most recently finished episode was truncated by the time limit, 0 where it terminated
+        (or none has finished yet) - the source of ``info['TimeLimit.truncated']``."""
+        out = self._new((self.num_envs,), np.uint8, device_out)
+        A.check(self._lib.rmav_episode_truncated(self._h, self._ptr(out), A.DEVICE if device_out else A.HOST))
+        return out
 
     @property
     def step_count(self) -> int:

@@ -36,7 +36,7 @@ class NativeQuadrotorEnv(_EnvBase):
     _action_box = None    # (low, high, dtype)
     _reading_2d = None
 
-    def __init__(self, device: int = 0, seed=None):
+    def __init__(self, device: int = 0, seed=None, max_episode_steps=None):
         kind = A.KIND_BY_NAME[self._kind]
         nS, nA = A.STATE_DIM[kind], A.ACTION_DIM[kind]
         lo, hi, dt = self._action_box
@@ -45,9 +45,12 @@ class NativeQuadrotorEnv(_EnvBase):
         self.viewer = None
         self._seed_value = self._fresh_seed() if seed is None else int(seed)
         # gym.Env semantics: no auto-reset, no Monitor; the constructor seeds then resets
-        # (quadrotor3d.py:73-74), which rmav_create does as well.
+        # (quadrotor3d.py:73-74), which rmav_create does as well.  max_episode_steps (gym.make(id, max_episode_steps=H)): the
+        # limit lives in the kernels, and the handle then tracks episodes so that lengths survive seed() / reset() exactly.
+        self._limited = bool(max_episode_steps)
         self._batch = BatchedQuadrotor(kind, 1, device=device, seed=self._seed_value, auto_reset=False,
-                                       track_episodes=False, reading_2d=self._reading_2d)
+                                       track_episodes=self._limited, reading_2d=self._reading_2d,
+                                       max_episode_steps=max_episode_steps)
         self._dim = 2 if nS in (5, 9) else 3
         self._has_load = nS in (9, 16)
         # Lean per-call path: preallocated host arrays and cached ctypes pointers, so a step() is one ABI call
@@ -92,7 +95,12 @@ class NativeQuadrotorEnv(_EnvBase):
         if rc < 0:
             A.check(rc)
         self._ctrl_valid = True
-        return self._o[0].astype(np.float64), float(self._r[0]), bool(self._d[0]), {}
+        done = bool(self._d[0])
+        info = {}
+        if done and self._limited:   # gym's TimeLimit: present (True) only when the limit ended the episode
+            if self._batch.episode_truncated()[0]:
+                info["TimeLimit.truncated"] = True
+        return self._o[0].astype(np.float64), float(self._r[0]), done, info
 
     def control(self):
         if self._ctrl_valid:            # evaluated by the last step()'s launch on the state it left behind

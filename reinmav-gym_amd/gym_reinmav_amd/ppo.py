@@ -440,6 +440,9 @@ class FusedPolicyCollector:
         from . import _abi as A
 
         assert env.auto_reset, "rollouts need VecEnv semantics (auto-reset)"
+        if getattr(env, "max_episode_steps", None) and (bf16_mfma or not (f32_mfma or f16_mfma)):
+            raise ValueError("an env with max_episode_steps runs the fp32 matrix-core actor (the default), f16_mfma=True or a "
+                             "shared-trunk policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no time-limited kernel")
         self.env, self.policy, self.T = env, policy, int(nsteps)
         self.bf16_mfma, self.f32_mfma, self.f16_mfma = bool(bf16_mfma), bool(f32_mfma), bool(f16_mfma)
         self._C, self._A = C, A

@@ -48,10 +48,12 @@ class LazyInfos:
     empty dict per access (never a shared one: a caller that writes ``infos[i]['x'] = ...`` must not touch other envs or later
     steps); a caller that wants such writes to persist asks for ``dict_infos=True``."""
 
-    __slots__ = ("_n", "_done", "_env", "_eps", "_seq", "_t")
+    __slots__ = ("_n", "_done", "_env", "_eps", "_seq", "_t", "_truncated")
 
-    def __init__(self, n, done, env, seq):
+    def __init__(self, n, done, env, seq, truncated=None):
+        """``truncated``: callable -> the env's truncated flags (u8 [N]) or None without a time limit (QuadrotorVecEnv._truncated)"""
         self._n, self._done, self._env, self._eps, self._seq = n, done, env, None, seq
+        self._truncated = truncated
         self._t = round(time.time() - env._tstart, 6)
 
     def _episodes(self):
@@ -64,8 +66,11 @@ class LazyInfos:
             eps = {}
             if len(idx):
                 buf = self._env.env.episode_buffers()
+                trunc = self._truncated() if self._truncated is not None else None
                 for i in idx:
                     eps[int(i)] = {"episode": {"r": float(buf["last_return"][i]), "l": int(buf["last_length"][i]), "t": self._t}}
+                    if trunc is not None:
+                        eps[int(i)]["TimeLimit.truncated"] = bool(trunc[i])
             self._eps = eps
         return self._eps
 
@@ -93,12 +98,14 @@ class LazyInfos:
 
 class QuadrotorVecEnv:
     def __init__(self, env_id: str, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
-                 numpy_io: bool = False, dict_infos=None, reading_2d=None, reuse_buffers: bool = False):
+                 numpy_io: bool = False, dict_infos=None, reading_2d=None, reuse_buffers: bool = False, max_episode_steps=None):
         """``dict_infos``: True = a real ``list[dict]`` per step (default up to 4 096 envs), False = a :class:`LazyInfos` (default
-        beyond): the same contract - ``len(infos) == num_envs``, ``infos[i].get('episode')`` - materialised on first use."""
+        beyond): the same contract - ``len(infos) == num_envs``, ``infos[i].get('episode')`` - materialised on first use.
+        ``max_episode_steps``: episode time limit (gym's ``TimeLimit``, inside the kernels); the info of an env that finished an
+        episode then also carries ``'TimeLimit.truncated'``."""
         kind = ENV_IDS.get(env_id, env_id)
         self.env = BatchedQuadrotor(kind, num_envs, device=device, seed=seed, env_id_base=env_id_base,
-                                    auto_reset=True, track_episodes=True, reading_2d=reading_2d)
+                                    auto_reset=True, track_episodes=True, reading_2d=reading_2d, max_episode_steps=max_episode_steps)
         self.num_envs = int(num_envs)
         self.numpy_io = bool(numpy_io)
         self.dict_infos = (num_envs <= 4096) if dict_infos is None else bool(dict_infos)
@@ -186,19 +193,26 @@ class QuadrotorVecEnv:
         self.step_async(actions)
         return self.step_wait()
 
+    def _truncated(self):
+        """the truncated flags of the last finished episodes (u8 [N], host), None without a time limit"""
+        return self.env.episode_truncated() if self.env.max_episode_steps else None
+
     def _infos(self, done_b):
         if not self.dict_infos:
             # a fresh object per step (~0.3 us): one that is read after a later step sees that its sequence number no longer
             # matches and raises (recycled objects, round 4, passed that check two steps later and answered for the wrong step)
             self._info_seq = seq = self._info_seq + 1
-            return LazyInfos(self.num_envs, done_b, self, seq)
+            return LazyInfos(self.num_envs, done_b, self, seq, self._truncated)
         infos = [{} for _ in range(self.num_envs)]
         idx = np.nonzero(done_b if self.numpy_io else done_b.cpu().numpy())[0]
         if len(idx):
             buf = self.env.episode_buffers()
+            trunc = self._truncated()
             t = round(time.time() - self._tstart, 6)
             for i in idx:
                 infos[int(i)]["episode"] = {"r": float(buf["last_return"][i]), "l": int(buf["last_length"][i]), "t": t}
+                if trunc is not None:
+                    infos[int(i)]["TimeLimit.truncated"] = bool(trunc[i])
         return infos
 
     def close(self):
