@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--reward_scale", type=float, default=0.05)
     ap.add_argument("--actor", default="f16", choices=["fp32", "bf16", "f16"], help="arithmetic of the in-kernel actor")
+    ap.add_argument("--max_episode_steps", type=int, default=0, help="episode time limit H (gym's TimeLimit, inside the kernels); 0 = none")
+    ap.add_argument("--bootstrap_truncated", action="store_true",
+                    help="with --max_episode_steps: value targets of truncated steps are r + gamma V(s_final) instead of r")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -35,14 +38,17 @@ def main():
 
     torch.manual_seed(args.seed)
     kind = g.ENV_IDS[args.env]
-    env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed)
+    if args.bootstrap_truncated and not args.max_episode_steps:
+        ap.error("--bootstrap_truncated needs --max_episode_steps")
+    env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None)
     policy = MlpPolicy(env.nS, env.nA).cuda()
     if args.load_path:                                      # run.py:188 model.load(load_path)
         policy.load_state_dict(torch.load(args.load_path, map_location="cuda"))
     elif kind in ("quad3d", "quad3d_sl"):
         with torch.no_grad():
             policy.pi[2].bias[0] = 9.8                      # start around hover thrust
-    collector = FusedPolicyCollector(env, policy, args.nsteps, bf16_mfma=(args.actor == "bf16"), f16_mfma=(args.actor == "f16"))
+    collector = FusedPolicyCollector(env, policy, args.nsteps, bf16_mfma=(args.actor == "bf16"), f16_mfma=(args.actor == "f16"),
+                                     bootstrap_truncated=args.bootstrap_truncated)
     learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()

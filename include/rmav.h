@@ -314,6 +314,23 @@ int rmav_get_time_limit(rmav_handle h, int32_t *out);
  * the handle first had a limit (written at every episode end of a time-limited handle, tracked or not). */
 int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem);
 
+/* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
+ * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that
+ * bootstraps a truncated episode (target r + gamma V(s_final): a truncated episode is not a failure) needs the state the dynamics
+ * left BEFORE the reset - gym VecEnvs' info['terminal_observation'].  Callers detect the feature by this symbol (RMAV_VERSION is
+ * unchanged); a caller that never calls it runs exactly the kernels it ran before.
+ *
+ * rmav_step, plus:
+ *   final_obs_out  nS*N floats in `layout`; written ONLY for envs whose episode ended with this step (done = 1): the state after the
+ *                  dynamics, before the reset.  Other envs' elements are left untouched (with RMAV_HOST too).  Terminated episodes
+ *                  report their terminal state as well as truncated ones.
+ *   trunc_out      N bytes, written for every env: 1 if the time limit ended the episode with this step, else 0.
+ * Either may be NULL.  Works on every quadrotor handle: without RMAV_F_AUTO_RESET final_obs equals the obs of the finished envs;
+ * without a time limit trunc_out is all zero.  RMAV_HOST and RMAV_DEVICE, both layouts.  obs, rew, done, the state, the episode
+ * records and statistics are bit-identical to rmav_step's.  RMAV_REINMAV (takes no limit, never resets): RMAV_ERR_INVALID. */
+int rmav_step_final(rmav_handle h, const float *actions, float *obs_out, float *rew_out, uint8_t *done_out,
+                    float *final_obs_out, uint8_t *trunc_out, int mem, int layout);
+
 #ifdef __cplusplus
 }
 #endif

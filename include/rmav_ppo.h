@@ -79,10 +79,26 @@ int rmav_pack_policy_f16(rmav_handle h, int n_params, const float *const *params
                          const int32_t *idx_hi, int64_t n_out, float *weights_out);
 /* A handle with an episode time limit (rmav_set_time_limit) runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA and RMAV_POLICY_F16_SHARED;
  * RMAV_POLICY_FP32 and RMAV_POLICY_BF16_MFMA return RMAV_ERR_INVALID there (no time-limited kernel: they already sit at their register
- * limit).  A truncated step has done = 1 and its ordinary reward: rmav_gae treats it as an episode boundary without a bootstrap. */
+ * limit).  A truncated step has done = 1 and its ordinary reward: rmav_gae treats it as an episode boundary without a bootstrap
+ * (rmav_rollout_policy_boot + rmav_gae_boot below add it). */
 int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out,
                         float *obs_out, float *rew_out, uint8_t *done_out, float *logp_out,
                         float *value_out, int precision);
+
+/* rmav_rollout_policy, plus the bootstrap term of truncated steps.  The auto-reset runs inside the launch, so the state a truncated
+ * episode ended in never reaches the caller; here the launch evaluates its own value net on it:
+ *   boot_out  [n_steps][N] (required): V(s_final) where step t was truncated by the time limit (s_final = the state after the
+ *             dynamics, before the reset; the same device function that produces value_out), 0.0f everywhere else - running and
+ *             terminated steps (termination wins over truncation, so a terminated step has boot = 0).
+ *   trunc_out u8 [n_steps][N] (nullable): 1 where the time limit ended the episode with step t.
+ * Needs a time limit on the handle and one of the three precisions a time-limited handle accepts (RMAV_POLICY_FP32_MFMA,
+ * RMAV_POLICY_F16_MFMA, RMAV_POLICY_F16_SHARED); anything else, and RMAV_REINMAV, is RMAV_ERR_INVALID.  Everything else the launch
+ * does - states, actions, rewards, done, logp, values, statistics, reset counters, truncated flags of the handle - is bit-identical
+ * to rmav_rollout_policy on the same handle.  Cost: one 4-byte and one 1-byte store per env-step, and one more value-net pass of a
+ * wavefront on the steps in which one of its envs is truncated (about one step in max_episode_steps). */
+int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out,
+                             float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out,
+                             uint8_t *trunc_out, int precision);
 
 /* ---- learner-side passes over a trajectory (DEVICE pointers, enqueued on the handle's stream) -------- */
 /* Generalised advantage estimation, the backward pass of baselines ppo2 Runner.run():
@@ -94,6 +110,12 @@ int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, fl
  * agrees with a float64 per-env recursion to ~1e-6 relative. */
 int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values,
              float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out);
+/* rmav_gae with the bootstrap term of truncated steps (boot [n_steps][N], what rmav_rollout_policy_boot writes):
+ *   delta_t = reward_scale r_t + gamma ((1 - done_t) V_{t+1} + boot_t) - V_t ;  A_t as in rmav_gae (the recursion still stops at
+ * every done): the return target of a truncated step becomes r + gamma V(s_final) instead of r alone.  boot all zero gives
+ * rmav_gae's values.  RMAV_REINMAV: RMAV_ERR_INVALID. */
+int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
+                  float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out);
 /* x[i] <- (x[i] - mean) * rstd for i < count (x 16-byte aligned): advantage normalisation in place. */
 int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rstd);
 

@@ -409,6 +409,39 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     return RMAV_OK;
 }
 
+// rmav_step_final: k_step_final<K, TL, ST> at k_step_tl's launch shape (eager record load and preloaded leading arguments for every batch size)
+template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, const FinalArgs &fa) {
+    if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;
+    const typename Env<K>::P p = derive_env<K>(h->params);
+    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
+    const int st = step_store(h), bs = step_block(h);
+    const dim3 grid((unsigned)((h->n + bs - 1) / bs));
+    const TimeLimitArgs tl = tl_args(h);
+#define RMAV_STEP_FINAL(TL, ST) \
+    hipLaunchKernelGGL((k_step_final<K, TL, ST>), grid, dim3(bs), 0, h->stream, a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a, p, pc, tl, fa)
+    if (h->time_limit > 0) {
+        if (st == ST_STREAM) RMAV_STEP_FINAL(true, ST_STREAM);
+        else if (st == ST_WRITE_THROUGH) RMAV_STEP_FINAL(true, ST_WRITE_THROUGH);
+        else RMAV_STEP_FINAL(true, ST_DEFAULT);
+    } else {
+        if (st == ST_STREAM) RMAV_STEP_FINAL(false, ST_STREAM);
+        else if (st == ST_WRITE_THROUGH) RMAV_STEP_FINAL(false, ST_WRITE_THROUGH);
+        else RMAV_STEP_FINAL(false, ST_DEFAULT);
+    }
+#undef RMAV_STEP_FINAL
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+int launch_step_final(rmav_handle h, const RolloutArgs &a, const FinalArgs &fa) {
+    switch (h->kind) {
+    case RMAV_QUAD2D: return launch_step_final_k<QUAD2D>(h, a, fa);
+    case RMAV_QUAD2D_SL: return launch_step_final_k<QUAD2D_SL>(h, a, fa);
+    case RMAV_QUAD3D: return launch_step_final_k<QUAD3D>(h, a, fa);
+    case RMAV_QUAD3D_SL: return launch_step_final_k<QUAD3D_SL>(h, a, fa);
+    }
+    return rmav_fail(RMAV_ERR_INVALID, "bad kind");
+}
+
 int launch_rollout(rmav_handle h, int mode, const RolloutArgs &a) {
     if (a.n_steps == 1 && (mode == RMAV_ACT_BUFFER || mode == ACT_BUFFER_CTRL) && h->kind != RMAV_REINMAV) {
         const bool ctrl = mode == ACT_BUFFER_CTRL;
@@ -919,7 +952,9 @@ int rmav_reset(rmav_handle h, float *obs_out, int mem, int layout) {
 // call leaves behind, nA*N floats in `layout` (action_mode must be RMAV_ACT_BUFFER, n_steps 1).
 static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const float *actions_in, float *actions_out,
                         float *obs_out, float *rew_out, uint8_t *done_out, float *ctrl_out, int mem, int layout,
-                        int fused, int64_t pitch = 0) {
+                        int fused, int64_t pitch = 0, bool want_final = false, float *final_out = nullptr, uint8_t *trunc_out = nullptr) {
+    // want_final (rmav_step_final: one step, caller actions, a quadrotor handle): the launch is k_step_final; final_out / trunc_out
+    // are staged like the other outputs, and final_out - of which the kernel rewrites only the finished envs' elements - is staged IN too
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
     if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
@@ -935,14 +970,17 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     const size_t nS = kStateDim[h->kind], nA = kActionDim[h->kind];
     const size_t b_act = T * nA * n * sizeof(float), b_obs = T * nS * n * sizeof(float);
     const size_t b_rew = T * n * sizeof(float), b_done = T * n, b_ctrl = nA * n * sizeof(float);
+    const size_t b_fin = nS * n * sizeof(float), b_trunc = n;
     const bool want_aout = actions_out && action_mode != RMAV_ACT_BUFFER;
 
     const float *d_act_in = actions_in;
     float *d_act_out = actions_out, *d_obs = obs_out, *d_rew = rew_out, *d_ctrl = ctrl_out;
     uint8_t *d_done = done_out;
+    float *d_fin = final_out;
+    uint8_t *d_trunc = trunc_out;
     bool pinned = false;
     char *hbase = nullptr;   // host view of the staging block (pinned path only)
-    size_t o_ain = 0, o_aout = 0, o_obs = 0, o_rew = 0, o_done = 0, o_ctrl = 0;
+    size_t o_ain = 0, o_aout = 0, o_obs = 0, o_rew = 0, o_done = 0, o_ctrl = 0, o_fin = 0, o_trunc = 0;
     if (mem == RMAV_HOST) {
         auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
         size_t off = 0;
@@ -952,6 +990,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
         if (rew_out) { o_rew = off; off += up(b_rew); }
         if (done_out) { o_done = off; off += up(b_done); }
         if (ctrl_out) { o_ctrl = off; off += up(b_ctrl); }
+        if (final_out) { o_fin = off; off += up(b_fin); }
+        if (trunc_out) { o_trunc = off; off += up(b_trunc); }
         if (!off) off = 256;
         char *base;
         if (off <= kPinnedMax && ensure_pinned(h, off) == RMAV_OK) {
@@ -960,11 +1000,13 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
             hbase = (char *)h->pinned;
             base = (char *)h->pinned_dev;
             if (action_mode == RMAV_ACT_BUFFER) memcpy(hbase + o_ain, actions_in, b_act);
+            if (final_out) memcpy(hbase + o_fin, final_out, b_fin);
         } else {   // bulk: stage through device scratch
             if (int rc = ensure_scratch(h, off)) return rc;
             base = (char *)h->scratch;
             if (action_mode == RMAV_ACT_BUFFER)
                 HIP_TRY(hipMemcpyAsync(base + o_ain, actions_in, b_act, hipMemcpyHostToDevice, h->stream));
+            if (final_out) HIP_TRY(hipMemcpyAsync(base + o_fin, final_out, b_fin, hipMemcpyHostToDevice, h->stream));
         }
         d_act_in = action_mode == RMAV_ACT_BUFFER ? (const float *)(base + o_ain) : nullptr;
         d_act_out = want_aout ? (float *)(base + o_aout) : nullptr;
@@ -972,6 +1014,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
         d_rew = rew_out ? (float *)(base + o_rew) : nullptr;
         d_done = done_out ? (uint8_t *)(base + o_done) : nullptr;
         d_ctrl = ctrl_out ? (float *)(base + o_ctrl) : nullptr;
+        d_fin = final_out ? (float *)(base + o_fin) : nullptr;
+        d_trunc = trunc_out ? (uint8_t *)(base + o_trunc) : nullptr;
     }
 
     RolloutArgs a = base_args(h);
@@ -1005,7 +1049,9 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
         a.obs_out = d_obs;
         a.rew_out = d_rew;
         a.done_out = d_done;
-        if (int rc = launch_rollout(h, kmode, a)) return rc;
+        if (want_final) {
+            if (int rc = launch_step_final(h, a, FinalArgs{d_fin, d_trunc})) return rc;
+        } else if (int rc = launch_rollout(h, kmode, a)) return rc;
     } else {
         for (size_t k = 0; k < T; ++k) {
             a.n_steps = 1;
@@ -1042,12 +1088,16 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
             if (rew_out) memcpy(rew_out, hbase + o_rew, b_rew);
             if (done_out) memcpy(done_out, hbase + o_done, b_done);
             if (ctrl_out) memcpy(ctrl_out, hbase + o_ctrl, b_ctrl);
+            if (final_out) memcpy(final_out, hbase + o_fin, b_fin);
+            if (trunc_out) memcpy(trunc_out, hbase + o_trunc, b_trunc);
         } else {
             if (want_aout) HIP_TRY(hipMemcpyAsync(actions_out, d_act_out, b_act, hipMemcpyDeviceToHost, h->stream));
             if (obs_out) HIP_TRY(hipMemcpyAsync(obs_out, d_obs, b_obs, hipMemcpyDeviceToHost, h->stream));
             if (rew_out) HIP_TRY(hipMemcpyAsync(rew_out, d_rew, b_rew, hipMemcpyDeviceToHost, h->stream));
             if (done_out) HIP_TRY(hipMemcpyAsync(done_out, d_done, b_done, hipMemcpyDeviceToHost, h->stream));
             if (ctrl_out) HIP_TRY(hipMemcpyAsync(ctrl_out, d_ctrl, b_ctrl, hipMemcpyDeviceToHost, h->stream));
+            if (final_out) HIP_TRY(hipMemcpyAsync(final_out, d_fin, b_fin, hipMemcpyDeviceToHost, h->stream));
+            if (trunc_out) HIP_TRY(hipMemcpyAsync(trunc_out, d_trunc, b_trunc, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
         }
         if (actions_out && action_mode == RMAV_ACT_BUFFER && actions_out != actions_in)
@@ -1214,6 +1264,49 @@ int rmav_step(rmav_handle h, const float *actions, float *obs_out, float *rew_ou
     if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
     return rmav_rollout(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, mem,
                         layout, 1);
+}
+
+int rmav_step_final(rmav_handle h, const float *actions, float *obs_out, float *rew_out, uint8_t *done_out, float *final_obs_out,
+                    uint8_t *trunc_out, int mem, int layout) {
+    CHECK_HANDLE(h);
+    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
+    if (h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit and never resets: rmav_step's obs is its terminal observation");
+    return rollout_impl(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, nullptr, mem, layout, 1, 0, true, final_obs_out,
+                        trunc_out);
+}
+
+int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out, float *rew_out,
+                             uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out, int precision) {
+    CHECK_HANDLE(h);
+    if (h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap");
+    if (h->time_limit <= 0)
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot needs an episode time limit on the handle (rmav_set_time_limit)");
+    if (precision != RMAV_POLICY_FP32_MFMA && precision != RMAV_POLICY_F16_MFMA && precision != RMAV_POLICY_F16_SHARED)
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
+                                           "(the fp32 vector-ALU and bf16 actors have no time-limited kernel), got precision %d", precision);
+    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
+    if (!weights || !logp_out || !value_out || !boot_out)
+        return rmav_fail(RMAV_ERR_INVALID, "weights, logp_out, value_out and boot_out are required (device pointers)");
+    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0)
+        return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
+    RolloutArgs a = base_args(h);
+    a.n_steps = n_steps;
+    a.act_out = actions_out;
+    a.obs_out = obs_out;
+    a.rew_out = rew_out;
+    a.done_out = done_out;
+    a.policy_w = weights;
+    a.logp_out = logp_out;
+    a.val_out = value_out;
+    const int kmode = precision == RMAV_POLICY_F16_MFMA ? (int)ACT_POLICY_F16 : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
+                                                                                                                : (int)ACT_POLICY_F32M;
+    const BootArgs bt{boot_out, trunc_out};
+    h->xchg.allow = true;
+    if (int rc = rmav_launch_policy_rollout(h, kmode, a, &bt)) return rc;
+    h->t += (uint64_t)n_steps;
+    return RMAV_OK;
 }
 
 int rmav_control(rmav_handle h, float *actions_out, int mem, int layout) {
@@ -1417,6 +1510,30 @@ int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *do
     }
     hipLaunchKernelGGL(k_gae, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, adv_out, ret_out, h->n, n_steps,
                        gamma, lam, reward_scale, partial);
+    HIP_TRY(hipGetLastError());
+    if (sums_out) {
+        hipLaunchKernelGGL(k_gae_fold, dim3(1), dim3(256), 0, h->stream, (const double *)partial, (int)nblk, sums_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return RMAV_OK;
+}
+
+int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
+                  float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    CHECK_HANDLE(h);
+    if (h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (use rmav_gae)");
+    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
+    if (!rew || !done || !values || !boot || !adv_out || !ret_out)
+        return rmav_fail(RMAV_ERR_INVALID, "rew, done, values, boot, adv_out and ret_out are required (device pointers)");
+    const unsigned nblk = (unsigned)((h->n + 255) / 256);
+    double *partial = nullptr;
+    if (sums_out) {
+        if (int rc = ensure_scratch(h, (size_t)nblk * 2 * sizeof(double))) return rc;
+        partial = (double *)h->scratch;
+    }
+    hipLaunchKernelGGL(k_gae_boot, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, adv_out, ret_out, h->n, n_steps, gamma, lam,
+                       reward_scale, partial);
     HIP_TRY(hipGetLastError());
     if (sums_out) {
         hipLaunchKernelGGL(k_gae_fold, dim3(1), dim3(256), 0, h->stream, (const double *)partial, (int)nblk, sums_out);

@@ -89,6 +89,82 @@ __global__ __launch_bounds__(256) void k_gae(const float *__restrict__ rew, cons
     }
 }
 
+// k_gae with the bootstrap term of truncated steps (rmav_gae_boot):
+//   delta_t = rew_scale r_t + gamma ((1 - done_t) V_{t+1} + boot_t) - V_t
+// boot_t = V(s_final) where the time limit ended the episode at step t (the state before the auto-reset; rmav_rollout_policy_boot
+// leaves it), 0 elsewhere; the recursion still stops at every done.  One more coalesced load stream: 13 bytes read + 8 written per
+// sample.  The term enters as one fma on k_gae's own expression, so boot = 0 gives k_gae's values.
+__global__ __launch_bounds__(256) void k_gae_boot(const float *__restrict__ rew, const uint8_t *__restrict__ done,
+                                                  const float *__restrict__ val, const float *__restrict__ boot,
+                                                  float *__restrict__ adv, float *__restrict__ ret, int64_t n, int32_t T, float gamma,
+                                                  float lam, float rew_scale, double *__restrict__ partial) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    float s1 = 0.0f, s2 = 0.0f;
+    if (i < n) {
+        float v_next = val[(int64_t)T * n + i];
+        float last = 0.0f;
+        const float gl = gamma * lam;
+        int32_t t = T - 1;
+        for (; t >= 0 && ((t + 1) % kGaeUnroll) != 0; --t) {
+            const int64_t o = (int64_t)t * n + i;
+            const float nt = done[o] ? 0.0f : 1.0f, v = val[o];
+            const float delta = fmaf(gamma * nt, v_next, fmaf(gamma, boot[o], fmaf(rew[o], rew_scale, -v)));
+            last = fmaf(gl * nt, last, delta);
+            adv[o] = last;
+            ret[o] = last + v;
+            s1 += last;
+            s2 = fmaf(last, last, s2);
+            v_next = v;
+        }
+        for (; t >= 0; t -= kGaeUnroll) {
+            float r[kGaeUnroll], v[kGaeUnroll], nt[kGaeUnroll], b[kGaeUnroll];
+#pragma unroll
+            for (int j = 0; j < kGaeUnroll; ++j) {
+                const int64_t o = (int64_t)(t - j) * n + i;
+                r[j] = rew[o];
+                v[j] = val[o];
+                b[j] = boot[o];
+                nt[j] = done[o] ? 0.0f : 1.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < kGaeUnroll; ++j) {
+                const int64_t o = (int64_t)(t - j) * n + i;
+                const float delta = fmaf(gamma * nt[j], v_next, fmaf(gamma, b[j], fmaf(r[j], rew_scale, -v[j])));
+                last = fmaf(gl * nt[j], last, delta);
+                adv[o] = last;
+                ret[o] = last + v[j];
+                s1 += last;
+                s2 = fmaf(last, last, s2);
+                v_next = v[j];
+            }
+        }
+    }
+    if (partial) {   // block partial of (sum A, sum A^2), as k_gae
+        __shared__ double sh[2][4];
+        double d1 = (double)s1, d2 = (double)s2;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            d1 += __shfl_down(d1, off, 64);
+            d2 += __shfl_down(d2, off, 64);
+        }
+        const int w = threadIdx.x >> 6;
+        if ((threadIdx.x & 63) == 0) {
+            sh[0][w] = d1;
+            sh[1][w] = d2;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double a1 = 0.0, a2 = 0.0;
+            for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
+                a1 += sh[0][k];
+                a2 += sh[1][k];
+            }
+            partial[2 * blockIdx.x] = a1;
+            partial[2 * blockIdx.x + 1] = a2;
+        }
+    }
+}
+
 // one block: sums_out[0..1] = (sum A, sum A^2) over all blocks' partials
 __global__ __launch_bounds__(256) void k_gae_fold(const double *__restrict__ partial, int nblocks, double *__restrict__ sums_out) {
     double a1 = 0.0, a2 = 0.0;

@@ -150,4 +150,5 @@ inline int check_rollout_launch(rmav_handle h, const rmav::RolloutArgs &a) {
 
 // rmav_policy_abi.hip: launches rmav_rollout_policy's kernel for kmode = RMAV_ACT_POLICY | RMAV_ACT_POLICY_BF16 | ACT_POLICY_F32M |
 // ACT_POLICY_F16 | ACT_POLICY_F16_SHARED on the handle's stream
-RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a);
+// bt (rmav_rollout_policy_boot): the launch also leaves the bootstrap term of its truncated steps - the *_boot kernels; nullptr otherwise
+RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt = nullptr);

@@ -218,6 +218,22 @@ struct TimeLimitArgs {
 // running length once (clock0 - ep_start), counts in registers as before, and writes clock0 + n_steps - length back; the
 // single-step kernel touches ep_start only in lanes whose episode ends - no per-step read-modify-write of a length array
 // (8 B of 24 B of bookkeeping traffic per env-step; round 5).  32-bit wrap-around is harmless: only differences are used.
+// What the auto-reset destroys (rmav_step_final; the k_step_final kernels): a trailing kernel argument of its own, as TimeLimitArgs.
+//   final_obs   f32 nS*N in the launch's layout: the state after the dynamics and BEFORE the reset, stored only by the lanes whose
+//               episode ended with this step (one masked store group per finished episode); nullptr = not wanted
+//   trunc_out   u8 [N], every env: 1 if the time limit ended the episode with this step; nullptr = not wanted
+struct FinalArgs {
+    float *final_obs;
+    uint8_t *trunc_out;
+};
+// The bootstrap term of a truncated step (rmav_rollout_policy_boot; the *_boot rollout kernels), trailing as well.
+//   boot_out    f32 [n_steps][N]: V(s_final) of the launch's value net where the step was truncated, 0 elsewhere
+//   trunc_out   u8 [n_steps][N] (nullable): 1 where the time limit ended the episode
+struct BootArgs {
+    float *boot_out;
+    uint8_t *trunc_out;
+};
+
 __device__ __forceinline__ uint32_t ep_clock0(const RolloutArgs &a) { return (uint32_t)a.t0; }
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
@@ -344,8 +360,9 @@ __device__ __forceinline__ void wide_cols(const float *tile, rsrc_t r, uint32_t 
 template <int K, int MODE, int ST = ST_DEFAULT, bool FIXED = false>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                     const ParamsT<double> pc_shared) {
-    constexpr bool TL = false;
+    constexpr bool TL = false, BOOT = false;
     [[maybe_unused]] const TimeLimitArgs tl{};
+    [[maybe_unused]] const BootArgs bt{};
 #include "rmav_rollout_body.inc"
 }
 // The same kernel under an episode time limit (rmav_set_time_limit): separate symbols, so that the kernels of handles without a limit
@@ -354,8 +371,19 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, FIXED = false;
+    constexpr bool TL = true, FIXED = false, BOOT = false;
+    [[maybe_unused]] const BootArgs bt{};
     static_assert(!is_split(MODE) && K != REINMAV, "time-limited launches run the one-wavefront kernels");
+#include "rmav_rollout_body.inc"
+}
+// k_rollout_tl of the fp32 matrix-core actor that also leaves the bootstrap term of its truncated steps (rmav_rollout_policy_boot):
+// on a step with a truncated lane - about one in max_steps - the wavefront runs the value net once more, on the state the reset is
+// about to replace.  A symbol of its own again: k_rollout_tl keeps its instruction stream.
+template <int K, int MODE, int ST = ST_DEFAULT>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                         const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
+    constexpr bool TL = true, FIXED = false, BOOT = true;
+    static_assert(MODE == ACT_POLICY_F32M && K != REINMAV, "the one-wavefront actor of time-limited handles");
 #include "rmav_rollout_body.inc"
 }
 
@@ -427,9 +455,10 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
     float *state; int64_t n; const float *act_in; int64_t pitch; uint32_t block, flags; float *ep_ret; EnvRec *rec;
 };
 // TL: the launch has an episode time limit (tl; k_step_tl) - with the eager record load only: every lane needs ep_start every step.
-template <int K, bool CTRL, bool LAZY, int ST, bool TL = false>
+// FIN: the launch also reports what the auto-reset destroys (fa; k_step_final).
+template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
-                                          const TimeLimitArgs &tl = TimeLimitArgs{}) {
+                                          const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}) {
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
     static_assert(!(TL && LAZY), "a time limit needs every lane's episode start");
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
@@ -593,6 +622,22 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
             rec_st4(make_rsrc(a.rec), li, u32x4_t{(uint32_t)sb, auto_reset ? rc + 1u : rc, es, (uint32_t)ll});
             if constexpr (TL) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(tl.last_trunc), li, 0, 0);
         }
+        // the terminal state of the finishing lanes, under the execution mask, before reset_state_wave() replaces it; the truncated
+        // flag of every lane
+        if constexpr (FIN) {
+            if (fa.final_obs && done) {
+                if (aos) {
+                    float *dst = fa.final_obs + (int64_t)li * NS;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) dst[c] = s[c];
+                } else {
+                    const rsrc_t rf = make_rsrc(fa.final_obs);
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) buf_st_aux<AUX>(rf, off, (uint32_t)c * tcol, s[c]);
+                }
+            }
+            if (fa.trunc_out) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(fa.trunc_out), li, 0, AUX);
+        }
     }
     if (auto_reset)   // wave-uniform; every lane takes part
         reset_state_wave<K>(a.seed, a.env_base + (uint64_t)(gi - (threadIdx.x & 63u)), rc, done && valid, s);
@@ -677,6 +722,23 @@ __global__ __launch_bounds__(kBlock) void k_step_tl(float *state_pl, int64_t n_p
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, CTRL, false, ST, true>(a, block_pl, p_shared, pc_shared, tl);
+}
+
+// rmav_step_final: k_step / k_step_tl (TL) that also store the finishing lanes' terminal state and every lane's truncated flag (FinalArgs).
+// Eager record load for every batch size, as k_step_tl; without a limit `tl` is not read.
+template <int K, bool TL, int ST = ST_DEFAULT>
+__global__ __launch_bounds__(kBlock) void k_step_final(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                       float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST, TL, true>(a, block_pl, p_shared, pc_shared, tl, fa);
 }
 
 // reset() of every env

@@ -1,5 +1,6 @@
 // rmav_pair_body.inc - the body of k_rollout_pair / k_rollout_pair_tl (rmav_policy_pair.hpp), included into both kernels: textually, for the
-// reason rmav_rollout_body.inc gives.  In scope: template parameters K, FMT, the constexpr bool TL and the kernel arguments a, p_shared, pc_shared, tl.
+// reason rmav_rollout_body.inc gives.  In scope: template parameters K, FMT, the constexpr bools TL and BOOT (k_rollout_pair_boot: the launch also
+// leaves the bootstrap term of its truncated steps) and the kernel arguments a, p_shared, pc_shared, tl, bt.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     using L = MfmaLayout;
     using PT = PairTile<NS, NA>;
@@ -15,7 +16,7 @@
     const uint32_t col = (uint32_t)n * 4u, off = li * 4u;
     const int32_t T = a.n_steps;
     const bool track = (a.flags & F_TRACK) != 0, auto_reset = (a.flags & F_AUTO_RESET) != 0;
-    float *tile = lds_w + L::TOTAL + pair * PT::WORDS;   // this pair's hand-over tiles
+    float *tile = lds_w + L::TOTAL + pair * (BOOT ? PairBootTile<NS, NA>::WORDS : PT::WORDS);   // this pair's hand-over tiles
     float *ztile = tile + lane, *otile = tile + PT::Z_WORDS + lane;
 
     if (a.xsend && blockIdx.x == 0 && threadIdx.x == 0)   // armed statistics exchange: this launch has begun (see k_rollout)
@@ -94,6 +95,31 @@
             const float vp = xor32(t1[0]);
             buf_st(make_rsrc(val_out), off, 0, (lane >> 5) ? vp : t0[0]);
             val_out += n;
+            // k_rollout_pair_boot: the actor marks a truncated step with 2.0f in the DONE word and leaves the state its reset replaced in
+            // the terminal area of the row (PairBootTile); the same value net on it is the step's bootstrap term.  Under B(k - 1), the
+            // barrier this wavefront has already passed: a step without a truncation costs one LDS read, one ballot and two stores.
+            if constexpr (BOOT) {
+                if (k > 0) {
+                    using PB = PairBootTile<NS, NA>;
+                    const bool tr = otile[((k - 1) & 1) * PT::O_HALF + PT::DONE] == 2.0f;
+                    float bv = 0.0f;
+                    if (__ballot(tr) != 0) {   // wave-uniform
+                        const float *fin = tile + PB::FIN + ((k - 1) & 1) * PB::FIN_HALF + lane;
+                        float xf[16];
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? fin[c * 64] : 0.0f;
+                        frag f0, f1;
+                        state_frags<FMT>(xf, f0, f1);
+                        float u0[4], u1[4];
+                        mlp_pair<FMT>(f0, f1, (uint32_t)L::NET, u0, u1);
+                        const float up = xor32(u1[0]);
+                        if (tr) bv = (lane >> 5) ? up : u0[0];
+                    }
+                    buf_st(make_rsrc(bt.boot_out + (int64_t)(k - 1) * n), off, 0, bv);
+                    const rsrc_t rT = bt.trunc_out ? make_rsrc(bt.trunc_out + (int64_t)(k - 1) * n) : make_rsrc_bounded(a.state, 0u);
+                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(tr ? 1 : 0), rT, li, 0, 0);
+                }
+            }
             if (k + 1 < T) draw(k + 1);
             if (k < T) __syncthreads();                               // B(k): O(k) handed over, Z(k + 1) in the tile
         }
@@ -185,6 +211,17 @@
             const bool trunc = !done && el + 1 >= tl.max_steps;
             done = done || trunc;
             if (done) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(tl.last_trunc), li, 0, 0);
+            // k_rollout_pair_boot: the critic owns the value net, this wavefront the state - hand the pre-reset state over in the row's
+            // terminal area (only on a step with a truncated lane) and say which lanes in the DONE word
+            if constexpr (BOOT) {
+                using PB = PairBootTile<NS, NA>;
+                if (__ballot(trunc) != 0) {   // wave-uniform
+                    float *fin = tile + PB::FIN + (k & 1) * PB::FIN_HALF + lane;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) fin[c * 64] = s[c];
+                }
+                otile[(k & 1) * PT::O_HALF + PT::DONE] = trunc ? 2.0f : (done ? 1.0f : 0.0f);
+            }
         }
         if (track) {
             er += r;
@@ -222,7 +259,7 @@
 #pragma unroll
         for (int c = 0; c < NS; ++c) row[c * 64] = s[c];
         row[PT::REW] = r;
-        row[PT::DONE] = done ? 1.0f : 0.0f;
+        if constexpr (!BOOT) row[PT::DONE] = done ? 1.0f : 0.0f;
 #pragma unroll
         for (int c = 0; c < NA; ++c) row[PT::ACT + c * 64] = act[c];
         __syncthreads();                                              // B(k)

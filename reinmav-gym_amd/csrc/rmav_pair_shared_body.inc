@@ -1,5 +1,6 @@
 // rmav_pair_shared_body.inc - the body of k_rollout_pair_shared / k_rollout_pair_shared_tl (rmav_policy_pair.hpp), included into both kernels: textually, for the
-// reason rmav_rollout_body.inc gives.  In scope: template parameters K, the constexpr bool TL and the kernel arguments a, p_shared, pc_shared, tl.
+// reason rmav_rollout_body.inc gives.  In scope: template parameters K, the constexpr bools TL and BOOT (k_rollout_pair_shared_boot: the launch also leaves
+// the bootstrap term of its truncated steps) and the kernel arguments a, p_shared, pc_shared, tl, bt.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     using L = MfmaLayout;
     using PT = PairTile<NS, NA>;
@@ -15,7 +16,7 @@
     const uint32_t col = (uint32_t)n * 4u, off = li * 4u;
     const int32_t T = a.n_steps;
     const bool track = (a.flags & F_TRACK) != 0, auto_reset = (a.flags & F_AUTO_RESET) != 0;
-    float *tile = lds_w + kSharedWeights + pair * ST_::WORDS;
+    float *tile = lds_w + kSharedWeights + pair * (BOOT ? SharedBootTile<NS, NA>::WORDS : ST_::WORDS);
     float *ztile = tile + lane, *otile = tile + PT::Z_WORDS + lane, *mtile = tile + ST_::MEAN;
 
     if (a.xsend && blockIdx.x == 0 && threadIdx.x == 0)
@@ -120,11 +121,15 @@
             eval_tile1((k - 1) & 1);                                      // obs before step k
             __syncthreads();                                              // X(k): the means of envs 32..63 are in the tile
             if (k > 0) drain((k - 1) & 1);
+            if constexpr (BOOT) {
+                if (k > 0) shared_boot_tile1<NS, NA>(tile, (k - 1) & 1, bt, (int64_t)(k - 1) * n, make_rsrc_bounded(a.state, 0u), off, li);
+            }
             if (k + 1 < T) draw(k + 1);
             __syncthreads();                                              // Y(k): step k's outputs are in the tile
         }
         eval_tile1((T - 1) & 1);                                          // bootstrap values of envs 32..63
         drain((T - 1) & 1);
+        if constexpr (BOOT) shared_boot_tile1<NS, NA>(tile, (T - 1) & 1, bt, (int64_t)(T - 1) * n, make_rsrc_bounded(a.state, 0u), off, li);
         return;
     }
 
@@ -232,6 +237,31 @@
             const bool trunc = !done && el + 1 >= tl.max_steps;
             done = done || trunc;
             if (done) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(tl.last_trunc), li, 0, 0);
+            // k_rollout_pair_shared_boot: on a step with a truncated lane both wavefronts run the net once more on the state the reset
+            // below replaces - this one for envs 0..31 from its registers (the value of env n leaves lane 32 + n, as eval_tile0's), B
+            // for envs 32..63 from the row's terminal area (SharedBootTile); the DONE word tells B which lanes
+            if constexpr (BOOT) {
+                using SB = SharedBootTile<NS, NA>;
+                float bv = 0.0f;
+                const uint64_t tm = __ballot(trunc);
+                if (tm != 0) {   // wave-uniform
+                    float *fin = tile + SB::FIN + (k & 1) * SB::FIN_HALF + lane;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) fin[c * 64] = s[c];
+                    float xf[8], u4[4];
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float lo = (j < NS) ? s[j] : 0.0f;
+                        float hi = 0.0f;
+                        if (8 + j < NS) hi = xor32(s[8 + j]);
+                        xf[j] = h ? hi : lo;
+                    }
+                    mlp_half_f16(pack_frag_f16(xf), u4);
+                    if (h && ((tm >> (lane & 31u)) & 1ull)) bv = u4[0];
+                }
+                if (vvalid) buf_st(make_rsrc(bt.boot_out + (int64_t)k * n), voff, 0, bv);
+                otile[(k & 1) * PT::O_HALF + PT::DONE] = trunc ? 2.0f : (done ? 1.0f : 0.0f);
+            }
         }
         if (track) {
             er += r;
@@ -269,7 +299,7 @@
 #pragma unroll
         for (int c = 0; c < NS; ++c) row[c * 64] = s[c];
         row[PT::REW] = r;
-        row[PT::DONE] = done ? 1.0f : 0.0f;
+        if constexpr (!BOOT) row[PT::DONE] = done ? 1.0f : 0.0f;
 #pragma unroll
         for (int c = 0; c < NA; ++c) row[PT::ACT + c * 64] = act[c];
         __syncthreads();                                                  // Y(k)

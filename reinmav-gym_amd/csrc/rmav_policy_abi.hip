@@ -18,7 +18,7 @@ namespace {
 
 // one wavefront per 64 envs (32 for the fp32-MFMA actor: both half-waves work on the same 32 envs)
 // (time-limited handles: k_rollout_tl, ACT_POLICY_F32M only - rmav_rollout_policy refuses the other one-wavefront actors)
-template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs &a_in) {
+template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, MODE == ACT_POLICY_F32M ? 32 : 64);
     const typename Env<K>::P p = derive_env<K>(h->params);
@@ -30,7 +30,8 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
     bool launched = false;
     if constexpr (K != REINMAV && MODE == ACT_POLICY_F32M) {
         if (h->time_limit > 0) {
-            hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h));
+            if (bt) hipLaunchKernelGGL((k_rollout_boot<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h), *bt);
+            else hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h));
             launched = true;
         }
     }
@@ -40,7 +41,11 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
 
 // The matrix-core actors as (actor, critic) wavefront pairs (rmav_policy_pair.hpp).  Pairs per workgroup: the pairs of a
 // workgroup share one LDS copy of the weights (30 KB) but also one s_barrier; RMAV_TUNE_PAIR_GROUP = 1 .. 4 overrides.
-template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutArgs &a_in) {
+// (The *_boot kernels' larger tiles - pair_boot_lds_bytes / shared_boot_lds_bytes - fit the 160 KiB of a workgroup at every group
+// count: 4 pairs of the 16-state kind take 113 KiB / 101 KiB.)
+static_assert(pair_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) <= (160u << 10) && shared_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) <= (160u << 10),
+              "the hand-over tiles with their terminal-state areas must fit one workgroup's LDS");
+template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, 64);
     const typename Env<K>::P p = derive_env<K>(h->params);
@@ -53,8 +58,12 @@ template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutAr
     bool launched = false;
     if constexpr (K != REINMAV && FMT == FMT_F16) {   // (time-limited handles: RMAV_POLICY_F16_MFMA only)
         if (h->time_limit > 0) {
-            hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
-                               h->stream, a, p, pc, tl_args(h));
+            if (bt)
+                hipLaunchKernelGGL((k_rollout_pair_boot<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g),
+                                   pair_boot_lds_bytes<K>(g), h->stream, a, p, pc, tl_args(h), *bt);
+            else
+                hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
+                                   h->stream, a, p, pc, tl_args(h));
             launched = true;
         }
     }
@@ -65,7 +74,7 @@ template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutAr
 }
 
 // RMAV_POLICY_F16_SHARED: one trunk, both wavefronts of a pair evaluate it for one 32-env column tile each (k_rollout_pair_shared)
-template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs &a_in) {
+template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, 64);
     const typename Env<K>::P p = derive_env<K>(h->params);
@@ -77,8 +86,12 @@ template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs
     bool launched = false;
     if constexpr (K != REINMAV) {
         if (h->time_limit > 0) {
-            hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
-                               h->stream, a, p, pc, tl_args(h));
+            if (bt)
+                hipLaunchKernelGGL((k_rollout_pair_shared_boot<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g),
+                                   shared_boot_lds_bytes<K>(g), h->stream, a, p, pc, tl_args(h), *bt);
+            else
+                hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
+                                   h->stream, a, p, pc, tl_args(h));
             launched = true;
         }
     }
@@ -88,27 +101,28 @@ template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs
     return check_rollout_launch(h, a);
 }
 
-template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a) {
+template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt) {
+    // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
     switch (kmode) {
-    case RMAV_ACT_POLICY: return launch_policy_1w<K, ACT_POLICY>(h, a);
+    case RMAV_ACT_POLICY: return launch_policy_1w<K, ACT_POLICY>(h, a, nullptr);
     case RMAV_ACT_POLICY_BF16:
-        return h->tune[RMAV_TUNE_POLICY_PAIR] == 0 ? launch_policy_1w<K, ACT_POLICY_BF16>(h, a) : launch_rollout_pair<K, FMT_BF16>(h, a);
-    case ACT_POLICY_F32M: return launch_policy_1w<K, ACT_POLICY_F32M>(h, a);
-    case ACT_POLICY_F16: return launch_rollout_pair<K, FMT_F16>(h, a);
-    case ACT_POLICY_F16_SHARED: return launch_rollout_pair_shared<K>(h, a);
+        return h->tune[RMAV_TUNE_POLICY_PAIR] == 0 ? launch_policy_1w<K, ACT_POLICY_BF16>(h, a, nullptr) : launch_rollout_pair<K, FMT_BF16>(h, a, nullptr);
+    case ACT_POLICY_F32M: return launch_policy_1w<K, ACT_POLICY_F32M>(h, a, bt);
+    case ACT_POLICY_F16: return launch_rollout_pair<K, FMT_F16>(h, a, bt);
+    case ACT_POLICY_F16_SHARED: return launch_rollout_pair_shared<K>(h, a, bt);
     }
     return rmav_fail(RMAV_ERR_INVALID, "unknown policy mode %d", kmode);
 }
 
 }  // namespace
 
-int rmav_launch_policy_rollout(rmav_handle h, int kmode, const RolloutArgs &a) {
+int rmav_launch_policy_rollout(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt) {
     switch (h->kind) {
-    case RMAV_QUAD2D: return launch_policy_k<QUAD2D>(h, kmode, a);
-    case RMAV_QUAD2D_SL: return launch_policy_k<QUAD2D_SL>(h, kmode, a);
-    case RMAV_QUAD3D: return launch_policy_k<QUAD3D>(h, kmode, a);
-    case RMAV_QUAD3D_SL: return launch_policy_k<QUAD3D_SL>(h, kmode, a);
-    case RMAV_REINMAV: return launch_policy_k<REINMAV>(h, kmode, a);
+    case RMAV_QUAD2D: return launch_policy_k<QUAD2D>(h, kmode, a, bt);
+    case RMAV_QUAD2D_SL: return launch_policy_k<QUAD2D_SL>(h, kmode, a, bt);
+    case RMAV_QUAD3D: return launch_policy_k<QUAD3D>(h, kmode, a, bt);
+    case RMAV_QUAD3D_SL: return launch_policy_k<QUAD3D_SL>(h, kmode, a, bt);
+    case RMAV_REINMAV: return launch_policy_k<REINMAV>(h, kmode, a, nullptr);
     }
     return rmav_fail(RMAV_ERR_INVALID, "bad kind");
 }

@@ -155,4 +155,24 @@ __device__ __forceinline__ void policy_forward_mfma32(const float (&x)[16], floa
     value = v.x;
 }
 
+// The value alone: policy_forward_mfma32's input fragment and its value-net call, without the policy net (the bootstrap term of a
+// truncated step, k_rollout_boot: same function, same operands, so the same bits as the value the rollout stores for that state).
+template <int NS>
+__device__ __forceinline__ float value_forward_mfma32(const float (&x)[16]) {
+    constexpr int NSL = (NS + 1) / 2;
+    const uint32_t h = (threadIdx.x & 63u) >> 5;
+    const uint32_t hmask = 0u - h;
+    Mfma32In b;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        if (s < NSL) {
+            const uint32_t lo = __builtin_bit_cast(uint32_t, x[2 * s]), hi = __builtin_bit_cast(uint32_t, x[2 * s + 1]);
+            b.v[s] = __builtin_bit_cast(float, (hi & hmask) | (lo & ~hmask));
+        } else {
+            b.v[s] = 0.0f;
+        }
+    }
+    return mlp_mfma32<NSL, 1>(b, (uint32_t)Mfma32Layout::NET).x;
+}
+
 }  // namespace rmav

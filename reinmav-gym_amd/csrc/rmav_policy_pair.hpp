@@ -55,6 +55,17 @@ template <int NS, int NA> struct PairTile {
     static constexpr int O_HALF = ACT + NA * 64, O_WORDS = 2 * O_HALF;     // (actor -> critic)
     static constexpr int WORDS = Z_WORDS + O_WORDS;
 };
+// ... of the kernels that also leave the bootstrap term of truncated steps (k_rollout_pair_boot): behind the words above - their
+// offsets do not move - every half of the output tile gets a terminal-state area [c][lane], written by the actor only on a step
+// with a truncated lane: the state its reset replaced, for the critic's value net.  A truncated step carries 2.0f in its DONE word.
+template <int NS, int NA> struct PairBootTile {
+    using PT = PairTile<NS, NA>;
+    static constexpr int FIN = PT::WORDS, FIN_HALF = NS * 64;
+    static constexpr int WORDS = PT::WORDS + 2 * FIN_HALF;
+};
+template <int K> constexpr size_t pair_boot_lds_bytes(int g) {
+    return sizeof(float) * ((size_t)MfmaLayout::TOTAL + (size_t)g * PairBootTile<Dims<K>::NS, Dims<K>::NA>::WORDS);
+}
 template <int K> constexpr size_t pair_lds_bytes(int g) {
     return sizeof(float) * ((size_t)MfmaLayout::TOTAL + (size_t)g * PairTile<Dims<K>::NS, Dims<K>::NA>::WORDS);
 }
@@ -219,16 +230,27 @@ __device__ __forceinline__ void state_frags(const float (&x)[16], typename PairO
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                           const ParamsT<double> pc_shared) {
-    constexpr bool TL = false;
+    constexpr bool TL = false, BOOT = false;
     [[maybe_unused]] const TimeLimitArgs tl{};
+    [[maybe_unused]] const BootArgs bt{};
 #include "rmav_pair_body.inc"
 }
 // ... under an episode time limit (separate symbols: see k_rollout_tl)
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true;
+    constexpr bool TL = true, BOOT = false;
+    [[maybe_unused]] const BootArgs bt{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
+#include "rmav_pair_body.inc"
+}
+// ... that also leaves the bootstrap term of its truncated steps (rmav_rollout_policy_boot; PairBootTile)
+template <int K, int FMT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt) {
+    constexpr bool TL = true, BOOT = true;
+    static_assert(K != REINMAV && FMT == FMT_F16, "the (actor, critic) pair of time-limited handles");
 #include "rmav_pair_body.inc"
 }
 
@@ -294,17 +316,62 @@ __device__ __forceinline__ f16x8_t pack_frag_f16(const float (&v)[8]) {
 }
 
 
+// k_rollout_pair_shared_boot: the terminal-state areas behind SharedTile's words (see PairBootTile), and B's share of a truncated step:
+// the net on the terminal states of envs 32..63 from tile half `half` (lane (n, h): components [8h, 8h + 8) of env 32 + n, as
+// eval_tile1); the value of env 32 + n arrives in lane 32 + n, the lane that stores for it.  Every lane stores its truncated flag.
+template <int NS, int NA> struct SharedBootTile {
+    using ST_ = SharedTile<NS, NA>;
+    static constexpr int FIN = ST_::WORDS, FIN_HALF = NS * 64;
+    static constexpr int WORDS = ST_::WORDS + 2 * FIN_HALF;
+};
+template <int K> constexpr size_t shared_boot_lds_bytes(int g) {
+    return sizeof(float) * ((size_t)kSharedWeights + (size_t)g * SharedBootTile<Dims<K>::NS, Dims<K>::NA>::WORDS);
+}
+template <int NS, int NA>
+__device__ __forceinline__ void shared_boot_tile1(const float *tile, int half, const BootArgs &bt, int64_t step_off, rsrc_t r_none,
+                                                  uint32_t off, uint32_t li) {
+    using PT = PairTile<NS, NA>;
+    using SB = SharedBootTile<NS, NA>;
+    const uint32_t lane = threadIdx.x & 63u, h = lane >> 5;
+    const bool tr = tile[PT::Z_WORDS + half * PT::O_HALF + PT::DONE + lane] == 2.0f;
+    float bv = 0.0f;
+    if (__ballot(tr) != 0) {   // wave-uniform
+        const float *fin = tile + SB::FIN + half * SB::FIN_HALF + 32u + (lane & 31u);
+        float x[8], u4[4];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float lo = (j < NS) ? fin[j * 64] : 0.0f, hi = (8 + j < NS) ? fin[(8 + j) * 64] : 0.0f;
+            x[j] = h ? hi : lo;
+        }
+        mlp_half_f16(pack_frag_f16(x), u4);
+        if (h && tr) bv = u4[0];
+    }
+    if (h) buf_st(make_rsrc(bt.boot_out + step_off), off, 0, bv);
+    const rsrc_t rT = bt.trunc_out ? make_rsrc(bt.trunc_out + step_off) : r_none;
+    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(tr ? 1 : 0), rT, li, 0, 0);
+}
+
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                  const ParamsT<double> pc_shared) {
-    constexpr bool TL = false;
+    constexpr bool TL = false, BOOT = false;
     [[maybe_unused]] const TimeLimitArgs tl{};
+    [[maybe_unused]] const BootArgs bt{};
 #include "rmav_pair_shared_body.inc"
 }
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true;
+    constexpr bool TL = true, BOOT = false;
+    [[maybe_unused]] const BootArgs bt{};
+    static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
+#include "rmav_pair_shared_body.inc"
+}
+template <int K>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                                      const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                                      const BootArgs bt) {
+    constexpr bool TL = true, BOOT = true;
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
 #include "rmav_pair_shared_body.inc"
 }

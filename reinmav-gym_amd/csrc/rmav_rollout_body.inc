@@ -2,7 +2,8 @@
 // Textually, not as a shared __device__ function: the optimiser simplifies such a function on its own - with `a` an opaque pointer
 // rather than the kernel's constant argument block - before inlining it, and the kernels came out with a different instruction
 // stream (tools/isa_compare.py, profiles/r07/time_limit.md).  In scope: template parameters K, MODE, ST, FIXED, the constexpr
-// bool TL (the launch has an episode time limit) and the kernel arguments a, p_shared, pc_shared, tl.
+// bool TL (the launch has an episode time limit), the constexpr bool BOOT (it also leaves the bootstrap term of truncated steps:
+// k_rollout_boot) and the kernel arguments a, p_shared, pc_shared, tl, bt.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     constexpr int AUX = StoreAux<ST>::value;
     // ACT_RANDOM_SPLIT: 128-thread workgroups, both wavefronts address the same 64 envs
@@ -716,6 +717,22 @@
                 const bool trunc = !done && el + 1 >= tl.max_steps;
                 done = done || trunc;
                 if (done) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(tl.last_trunc), li, 0, 0);
+                // k_rollout_boot: the bootstrap term of a truncated step = the value net on the state the reset below replaces.  The ballot
+                // is wave-uniform and non-zero on about one step in max_steps; only the value net runs (value_forward_mfma32: the
+                // call that produces val_out, on the same operands).
+                if constexpr (BOOT) {
+                    float bv = 0.0f;
+                    if (__ballot(trunc) != 0) {
+                        float xf[16];
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? s[c] : 0.0f;
+                        const float vf = value_forward_mfma32<NS>(xf);
+                        if (trunc) bv = vf;
+                    }
+                    buf_st(make_rsrc(bt.boot_out + (int64_t)k * n), off, 0, bv);
+                    // (a plain store: a second buffer descriptor here cost the quadrotor2d kernel a stack frame)
+                    if (bt.trunc_out) bt.trunc_out[(int64_t)k * n + li] = (uint8_t)(trunc ? 1 : 0);
+                }
             }
 
             // End of an episode (statistics) and auto-reset.  A lane that terminates again in the same launch has no spare reset

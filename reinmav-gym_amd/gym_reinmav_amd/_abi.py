@@ -133,6 +133,9 @@ PROTOTYPES = {
     "rmav_set_time_limit": (C.c_int, [C.c_void_p, C.c_int32]),
     "rmav_get_time_limit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
+    "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
+    "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),
+    "rmav_gae_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _u8p, _fp, _fp, C.c_float, C.c_float, C.c_float, _fp, _fp, _vp]),
 }
 
 _lib = None

@@ -220,6 +220,31 @@ class BatchedQuadrotor:
             done = done.astype(bool)
         return obs, rew, done
 
+    def step_final(self, actions, layout: str = "aos", out=None):
+        """:meth:`step`, plus what the auto-reset destroys (``rmav_step_final``)
+        -> (obs, reward, done, final_obs, truncated).
+
+        ``final_obs`` (shaped like ``obs``) holds, for the envs whose episode ended with this step, the state after the dynamics and
+        before the reset - gym VecEnvs' ``terminal_observation``; the elements of every other env are NOT written (a fresh buffer
+        holds zeros there, a buffer handed in through ``out`` keeps what it held).  ``truncated`` u8/bool [N] is 1 where the time
+        limit ended the episode.  ``out`` may carry preallocated (obs, rew, done, final_obs, truncated) buffers."""
+        a, mem = self._in(actions, self._shape(self.nA, layout))
+        dev = mem == A.DEVICE
+        if out is None:
+            obs = self._new(self._shape(self.nS, layout), np.float32, dev)
+            rew = self._new((self.num_envs,), np.float32, dev)
+            done = self._new((self.num_envs,), np.uint8, dev)
+            fin = (torch.zeros(self._shape(self.nS, layout), dtype=torch.float32, device=f"cuda:{self.device}") if dev
+                   else np.zeros(self._shape(self.nS, layout), dtype=np.float32))
+            trunc = self._new((self.num_envs,), np.uint8, dev)
+        else:
+            obs, rew, done, fin, trunc = out
+        A.check(self._lib.rmav_step_final(self._h, self._ptr(a), self._ptr(obs), self._ptr(rew), self._ptr(done), self._ptr(fin),
+                                          self._ptr(trunc), mem, _layout(layout)))
+        if not dev and out is None:
+            done, trunc = done.astype(bool), trunc.astype(bool)
+        return obs, rew, done, fin, trunc
+
     def control(self, layout: str = "aos", device_out: bool = False):
         act = self._new(self._shape(self.nA, layout), np.float32, device_out)
         A.check(self._lib.rmav_control(self._h, self._ptr(act), A.DEVICE if device_out else A.HOST, _layout(layout)))
@@ -260,14 +285,20 @@ class BatchedQuadrotor:
         return obs, rew, done, nxt
 
     def gae(self, rew, done, values, gamma: float = 0.99, lam: float = 0.95, reward_scale: float = 1.0, out=None,
-            sums=None):
+            sums=None, boot=None):
         """GAE(lambda) over a time-major device trajectory (``rmav_gae``): rew f32 [T,N], done u8 [T,N],
         values f32 [T+1,N] -> (adv [T,N], returns [T,N]); ``sums`` (f64[2] device tensor, optional) receives
-        (sum A, sum A^2)."""
+        (sum A, sum A^2).  ``boot`` f32 [T,N] (optional): V(s_final) of the truncated steps, 0 elsewhere - their targets become
+        r + gamma V(s_final) (``rmav_gae_boot``)."""
         T = int(rew.shape[0])
         assert tuple(rew.shape) == (T, self.num_envs) and tuple(done.shape) == (T, self.num_envs)
         assert tuple(values.shape) == (T + 1, self.num_envs) and done.dtype == torch.uint8
         adv, ret = out if out is not None else (torch.empty_like(rew), torch.empty_like(rew))
+        if boot is not None:
+            assert tuple(boot.shape) == (T, self.num_envs) and boot.dtype == torch.float32
+            A.check(self._lib.rmav_gae_boot(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), self._ptr(boot), float(gamma),
+                                            float(lam), float(reward_scale), self._ptr(adv), self._ptr(ret), self._ptr(sums)))
+            return adv, ret
         A.check(self._lib.rmav_gae(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), float(gamma), float(lam),
                                    float(reward_scale), self._ptr(adv), self._ptr(ret), self._ptr(sums)))
         return adv, ret

@@ -8,6 +8,10 @@ attributes ``state``, ``steps_beyond_done``, ``mass``, ``dt``, ``g``, ``ref_pos`
 keep that surface; the arithmetic runs in the HIP kernels through ``librmav.so`` (one env, one lane).
 Observations and rewards are returned as float64 / Python float like the reference, but their
 values are the fp32 results of the device path.
+
+These envs never auto-reset, so the obs ``step()`` returns for a finished episode - terminated or truncated by
+``max_episode_steps`` - is already its terminal observation: there is no ``'terminal_observation'`` info key here
+(that, and ``rmav_step_final`` behind it, belong to the auto-resetting ``QuadrotorVecEnv``).
 """
 from __future__ import annotations
 
@@ -47,6 +51,8 @@ class NativeQuadrotorEnv(_EnvBase):
         # gym.Env semantics: no auto-reset, no Monitor; the constructor seeds then resets
         # (quadrotor3d.py:73-74), which rmav_create does as well.  max_episode_steps (gym.make(id, max_episode_steps=H)): the
         # limit lives in the kernels, and the handle then tracks episodes so that lengths survive seed() / reset() exactly.
+        # (No 'terminal_observation' here: this env never auto-resets, so the obs step() returns for a finished episode IS its
+        # terminal observation - rmav_step_final / QuadrotorVecEnv(terminal_observation=True) are for the batched, auto-resetting path.)
         self._limited = bool(max_episode_steps)
         self._batch = BatchedQuadrotor(kind, 1, device=device, seed=self._seed_value, auto_reset=False,
                                        track_episodes=self._limited, reading_2d=self._reading_2d,

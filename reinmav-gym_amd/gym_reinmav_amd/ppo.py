@@ -116,9 +116,22 @@ class MlpPolicy(torch.nn.Module):
 class RolloutCollector:
     """Collects ``nsteps`` transitions of every env into device-resident, time-major, feature-major buffers."""
 
-    def __init__(self, env: BatchedQuadrotor, policy: MlpPolicy, nsteps: int, graph: bool = False):
+    def __init__(self, env: BatchedQuadrotor, policy: MlpPolicy, nsteps: int, graph: bool = False, bootstrap_truncated: bool = False):
+        """``bootstrap_truncated=True`` (needs ``env.max_episode_steps``): the collector also owns ``boot [T, N]`` - the value net on
+        the state a truncated episode ended in (``rmav_step_final``'s ``final_obs``, which the auto-reset has replaced in ``obs``), 0
+        where the step was not truncated - and ``trunc [T, N]``; ``PPO.update`` then targets ``r + gamma V(s_final)`` on those steps.
+        One more policy forward per step, no host synchronisation: ``graph=True`` still captures (the env's ``step_count`` then stays
+        where it was at the capture: the replayed launches carry their episode clock with them, see ``_capture``)."""
         assert env.auto_reset, "rollouts need VecEnv semantics (auto-reset)"
         self.env, self.policy, self.T = env, policy, int(nsteps)
+        self.boot = self.trunc = None
+        if bootstrap_truncated:
+            if not env.max_episode_steps:
+                raise ValueError("bootstrap_truncated=True needs an env with max_episode_steps")
+            dev_ = torch.device("cuda", env.device)
+            self.boot = torch.zeros((self.T, env.num_envs), dtype=torch.float32, device=dev_)
+            self.trunc = torch.zeros((self.T, env.num_envs), dtype=torch.uint8, device=dev_)
+            self._final = torch.zeros((env.nS, env.num_envs), dtype=torch.float32, device=dev_)   # rows of unfinished envs: stale, masked
         dev = torch.device("cuda", env.device)
         N, nS, nA, T = env.num_envs, env.nS, env.nA, self.T
         f32 = dict(dtype=torch.float32, device=dev)
@@ -140,7 +153,11 @@ class RolloutCollector:
         torch.addcmul(mean, noise, torch.exp(self.policy.logstd)[:, None], out=self.act[t])
         self.logp[t] = -0.5 * (noise * noise).sum(0) - self.policy.logstd.sum() - 0.5 * mean.shape[0] * math.log(2 * math.pi)
         self.val[t] = v
-        self.env.step(self.act[t], layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t]))
+        if self.boot is None:
+            self.env.step(self.act[t], layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t]))
+        else:
+            self.env.step_final(self.act[t], layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t], self._final, self.trunc[t]))
+            torch.where(self.trunc[t] != 0, self.policy(self._final)[1], self.boot.new_zeros(()), out=self.boot[t])
 
     def _body(self):
         with torch.no_grad():
@@ -171,6 +188,12 @@ class RolloutCollector:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=side):
                 self._body()
+                if self.boot is not None:
+                    # The episode clock is an argument of every captured launch, so a replay runs steps t0 .. t0 + T - 1 again
+                    # whatever the host counter says.  The time limit compares that clock with the envs' episode starts: the
+                    # graph ends by moving the starts back by T (rmav_set_step_count inside the capture: one small launch), so
+                    # that the running lengths carry over from one replay to the next; collect() then leaves the counter alone.
+                    env.step_count = t0
         self._graph = g
         cur = torch.cuda.current_stream(env.device)
         cur.wait_stream(side)
@@ -182,7 +205,8 @@ class RolloutCollector:
         """Run one rollout; buffers are valid after the current stream's work completes."""
         if self._graph is not None:
             self._graph.replay()
-            self.env.step_count = self.env.step_count + self.T   # the captured launches carry no host-side effects
+            if self.boot is None:
+                self.env.step_count = self.env.step_count + self.T   # the captured launches carry no host-side effects
         else:
             self._body()
         return self
@@ -422,11 +446,15 @@ class FusedPolicyCollector:
     that owns the env (``rmav_rollout_policy``), so nothing but the trajectory touches HBM."""
 
     def __init__(self, env: BatchedQuadrotor, policy: MlpPolicy, nsteps: int, bf16_mfma: bool = False,
-                 f32_mfma: Optional[bool] = None, native_pack: bool = True, f16_mfma: bool = False):
+                 f32_mfma: Optional[bool] = None, native_pack: bool = True, f16_mfma: bool = False, bootstrap_truncated: bool = False):
         """Actor arithmetic: fp32 on the fp32-input matrix instructions (``v_mfma_f32_32x32x2_f32``; the default),
         ``f32_mfma=False`` fp32 FMAs on the vector ALU (same precision class - only the summation order differs - at
         half the speed), ``bf16_mfma=True`` bf16 operands on the matrix cores (~1e-2 on means), ``f16_mfma=True`` f16
-        operands with tanh folded into the next layer (the fastest, ~1e-3 on means; csrc/rmav_policy_pair.hpp)."""
+        operands with tanh folded into the next layer (the fastest, ~1e-3 on means; csrc/rmav_policy_pair.hpp).
+
+        ``bootstrap_truncated=True`` (needs ``env.max_episode_steps``): the launch is ``rmav_rollout_policy_boot`` and the collector
+        also owns ``boot [T, N]`` = the launch's value net on the state a truncated episode ended in (0 where the step was not
+        truncated) and ``trunc [T, N]``; ``PPO.update`` then targets ``r + gamma V(s_final)`` on those steps."""
         import ctypes as C
 
         assert not (bf16_mfma and f16_mfma)
@@ -469,10 +497,17 @@ class FusedPolicyCollector:
         self.native_pack = bool(native_pack)
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         # (the env's handle is read at call time: env.close() clears it, and a cached copy would hand a freed handle to the library)
-        self._call = (A.lib().rmav_rollout_policy, self.T, p(self.weights), p(self.act), p(self.obs[1:]), p(self.rew), p(self.done),
-                      p(self.logp), p(self.val),
+        self.boot = self.trunc = None
+        if bootstrap_truncated:
+            if not getattr(env, "max_episode_steps", None):
+                raise ValueError("bootstrap_truncated=True needs an env with max_episode_steps")
+            self.boot = torch.empty((T, N), **f32)
+            self.trunc = torch.empty((T, N), dtype=torch.uint8, device=dev)
+        self._call = (A.lib().rmav_rollout_policy_boot if bootstrap_truncated else A.lib().rmav_rollout_policy,
+                      self.T, p(self.weights), p(self.act), p(self.obs[1:]), p(self.rew), p(self.done), p(self.logp), p(self.val)) + (
+                      (p(self.boot), p(self.trunc)) if bootstrap_truncated else ()) + (
                       A.POLICY_F16_SHARED if shared else A.POLICY_F16_MFMA if self.f16_mfma else A.POLICY_BF16_MFMA if self.bf16_mfma
-                      else A.POLICY_FP32_MFMA if self.f32_mfma else A.POLICY_FP32)
+                      else A.POLICY_FP32_MFMA if self.f32_mfma else A.POLICY_FP32,)
 
     def _pack(self):
         if self.native_pack:
@@ -492,19 +527,25 @@ class FusedPolicyCollector:
         self.obs[0].copy_(self.obs[self.T])
 
 
-def gae(rew, val, done, gamma: float = 0.99, lam: float = 0.95):
+def gae(rew, val, done, gamma: float = 0.99, lam: float = 0.95, boot=None):
     """Generalised advantage estimation on time-major tensors - the plain torch fp32 form (T small launches per
     call), kept as the reference the HIP kernel (``BatchedQuadrotor.gae`` -> ``rmav_gae``) is tested against and
     for CPU tensors; ``PPO.update`` uses the kernel.
 
     rew [T,N], val [T+1,N] (val[T] = bootstrap value), done [T,N] (1 = the episode ended with step t; the
-    next obs is a fresh reset and must not be bootstrapped from).  Returns (adv [T,N], returns [T,N])."""
+    next obs is a fresh reset and must not be bootstrapped from).  Returns (adv [T,N], returns [T,N]).
+
+    ``boot`` [T,N] (optional): V(s_final) where step t was truncated by the episode time limit, 0 elsewhere:
+    delta_t = r_t + gamma ((1 - done_t) V_{t+1} + boot_t) - V_t, so a truncated step's target is r + gamma V(s_final) instead of r
+    alone; the recursion still stops at every done.  ``None`` is the function without the term."""
     T = rew.shape[0]
     adv = torch.empty_like(rew)
     last = torch.zeros_like(rew[0])
     nonterm = 1.0 - done.to(rew.dtype)
     for t in range(T - 1, -1, -1):
         delta = rew[t] + gamma * val[t + 1] * nonterm[t] - val[t]
+        if boot is not None:
+            delta = delta + gamma * boot[t]
         last = delta + gamma * lam * nonterm[t] * last
         adv[t] = last
     return adv, adv + val[:T]
@@ -551,10 +592,10 @@ class PPO:
     def update(self, ro: RolloutCollector) -> dict:
         T, N = ro.rew.shape
         if ro.rew.is_cuda:   # one HIP launch over the [T][N] trajectory (per-lane reverse scan, csrc/rmav_gae.hpp)
-            adv, ret = ro.env.gae(ro.rew, ro.done, ro.val, self.gamma, self.lam, self.reward_scale)
+            adv, ret = ro.env.gae(ro.rew, ro.done, ro.val, self.gamma, self.lam, self.reward_scale, boot=getattr(ro, "boot", None))
         else:
             rew = ro.rew if self.reward_scale == 1.0 else ro.rew * self.reward_scale
-            adv, ret = gae(rew, ro.val, ro.done, self.gamma, self.lam)
+            adv, ret = gae(rew, ro.val, ro.done, self.gamma, self.lam, boot=getattr(ro, "boot", None))
         obs = ro.obs[:T].permute(1, 0, 2).reshape(ro.obs.shape[1], T * N)   # [nS, T*N] feature-major
         act = ro.act.permute(1, 0, 2).reshape(ro.act.shape[1], T * N)
         logp_old, val_old = ro.logp.reshape(-1), ro.val[:T].reshape(-1)

@@ -48,12 +48,15 @@ class LazyInfos:
     empty dict per access (never a shared one: a caller that writes ``infos[i]['x'] = ...`` must not touch other envs or later
     steps); a caller that wants such writes to persist asks for ``dict_infos=True``."""
 
-    __slots__ = ("_n", "_done", "_env", "_eps", "_seq", "_t", "_truncated")
+    __slots__ = ("_n", "_done", "_env", "_eps", "_seq", "_t", "_truncated", "_terminal")
 
-    def __init__(self, n, done, env, seq, truncated=None):
-        """``truncated``: callable -> the env's truncated flags (u8 [N]) or None without a time limit (QuadrotorVecEnv._truncated)"""
+    def __init__(self, n, done, env, seq, truncated=None, terminal=None):
+        """``truncated``: callable -> the env's truncated flags (u8 [N]) or None without a time limit (QuadrotorVecEnv._truncated).
+        ``terminal``: callable(idx) -> the terminal observations [len(idx), nS] of the finished envs ``idx`` (QuadrotorVecEnv._terminal_rows),
+        None when the VecEnv does not keep them.  It reads the VecEnv's one persistent buffer, which the next step overwrites - under the
+        same staleness check as the episode statistics."""
         self._n, self._done, self._env, self._eps, self._seq = n, done, env, None, seq
-        self._truncated = truncated
+        self._truncated, self._terminal = truncated, terminal
         self._t = round(time.time() - env._tstart, 6)
 
     def _episodes(self):
@@ -67,10 +70,13 @@ class LazyInfos:
             if len(idx):
                 buf = self._env.env.episode_buffers()
                 trunc = self._truncated() if self._truncated is not None else None
-                for i in idx:
+                term = self._terminal(idx) if self._terminal is not None else None
+                for j, i in enumerate(idx):
                     eps[int(i)] = {"episode": {"r": float(buf["last_return"][i]), "l": int(buf["last_length"][i]), "t": self._t}}
                     if trunc is not None:
                         eps[int(i)]["TimeLimit.truncated"] = bool(trunc[i])
+                    if term is not None:
+                        eps[int(i)]["terminal_observation"] = term[j]
             self._eps = eps
         return self._eps
 
@@ -98,11 +104,17 @@ class LazyInfos:
 
 class QuadrotorVecEnv:
     def __init__(self, env_id: str, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
-                 numpy_io: bool = False, dict_infos=None, reading_2d=None, reuse_buffers: bool = False, max_episode_steps=None):
+                 numpy_io: bool = False, dict_infos=None, reading_2d=None, reuse_buffers: bool = False, max_episode_steps=None,
+                 terminal_observation: bool = False):
         """``dict_infos``: True = a real ``list[dict]`` per step (default up to 4 096 envs), False = a :class:`LazyInfos` (default
         beyond): the same contract - ``len(infos) == num_envs``, ``infos[i].get('episode')`` - materialised on first use.
         ``max_episode_steps``: episode time limit (gym's ``TimeLimit``, inside the kernels); the info of an env that finished an
-        episode then also carries ``'TimeLimit.truncated'``."""
+        episode then also carries ``'TimeLimit.truncated'``.
+        ``terminal_observation=True``: the info of an env that finished an episode also carries ``'terminal_observation'`` (float32
+        ``[nS]``): the state the episode ended in, which the auto-reset has already replaced in the returned obs - what a learner
+        bootstraps a truncated episode from.  The steps then run ``rmav_step_final`` into ONE persistent ``[N, nS]`` buffer (on the
+        device; a host array with ``numpy_io``); only the rows of finished envs are copied out, and only when the infos are read.
+        Default ``False``: the steps are ``rmav_step`` and the infos what they were."""
         kind = ENV_IDS.get(env_id, env_id)
         self.env = BatchedQuadrotor(kind, num_envs, device=device, seed=seed, env_id_base=env_id_base,
                                     auto_reset=True, track_episodes=True, reading_2d=reading_2d, max_episode_steps=max_episode_steps)
@@ -120,7 +132,16 @@ class QuadrotorVecEnv:
         # DummyVecEnv (whose Runner keeps the returned reward arrays): slices of blocks of _BLOCK steps.
         self.reuse_buffers = bool(reuse_buffers) and not self.numpy_io
         self._step_fn = self.env._lib.rmav_step
+        self._step_final_fn = self.env._lib.rmav_step_final
         self._hnd = self.env._h
+        self.terminal_observation = bool(terminal_observation)
+        self._final = self._final_ptr = None
+        if self.terminal_observation:
+            if self.numpy_io:
+                self._final = np.zeros((self.num_envs, self.env.nS), np.float32)
+            else:
+                self._final = torch.zeros((self.num_envs, self.env.nS), dtype=torch.float32, device=torch.device("cuda", self.env.device))
+                self._final_ptr = C.c_void_p(self._final.data_ptr())
         self._act_shape = (self.num_envs, self.env.nA)
         self._dev = None if self.numpy_io else torch.device("cuda", self.env.device)
         self._slots, self._cursor = [], 0
@@ -164,7 +185,10 @@ class QuadrotorVecEnv:
 
     def step_async(self, actions):
         if self.numpy_io:
-            self._pending = self.env.step(np.asarray(actions, dtype=np.float32), layout="aos", out=self._host)
+            if self.terminal_observation:
+                self._pending = self.env.step_final(np.asarray(actions, dtype=np.float32), layout="aos", out=self._host + (self._final, None))[:3]
+            else:
+                self._pending = self.env.step(np.asarray(actions, dtype=np.float32), layout="aos", out=self._host)
             return
         if self._hnd is None:
             raise A.RmavError(A.ERR_INVALID, "step on a closed QuadrotorVecEnv")
@@ -174,7 +198,10 @@ class QuadrotorVecEnv:
                 np.asarray(actions, dtype=np.float32), device=self._dev), self._act_shape)   # convert / validate / raise
         slot = self._next_slot()
         # enqueued on the env's stream; the outputs are filled asynchronously
-        rc = self._step_fn(self._hnd, C.c_void_p(actions.data_ptr()), slot[3], slot[4], slot[5], A.DEVICE, A.AOS)
+        if self._final_ptr is not None:
+            rc = self._step_final_fn(self._hnd, C.c_void_p(actions.data_ptr()), slot[3], slot[4], slot[5], self._final_ptr, None, A.DEVICE, A.AOS)
+        else:
+            rc = self._step_fn(self._hnd, C.c_void_p(actions.data_ptr()), slot[3], slot[4], slot[5], A.DEVICE, A.AOS)
         if rc < 0:
             A.check(rc)
         self._pending = slot
@@ -197,22 +224,32 @@ class QuadrotorVecEnv:
         """the truncated flags of the last finished episodes (u8 [N], host), None without a time limit"""
         return self.env.episode_truncated() if self.env.max_episode_steps else None
 
+    def _terminal_rows(self, idx):
+        """float32 [len(idx), nS] (host): the terminal observations of the finished envs ``idx`` of the LAST step - only these rows
+        leave the persistent buffer"""
+        if self.numpy_io:
+            return self._final[idx].copy()
+        return self._final[torch.as_tensor(idx, device=self._final.device)].cpu().numpy()
+
     def _infos(self, done_b):
         if not self.dict_infos:
             # a fresh object per step (~0.3 us): one that is read after a later step sees that its sequence number no longer
             # matches and raises (recycled objects, round 4, passed that check two steps later and answered for the wrong step)
             self._info_seq = seq = self._info_seq + 1
-            return LazyInfos(self.num_envs, done_b, self, seq, self._truncated)
+            return LazyInfos(self.num_envs, done_b, self, seq, self._truncated, self._terminal_rows if self.terminal_observation else None)
         infos = [{} for _ in range(self.num_envs)]
         idx = np.nonzero(done_b if self.numpy_io else done_b.cpu().numpy())[0]
         if len(idx):
             buf = self.env.episode_buffers()
             trunc = self._truncated()
+            term = self._terminal_rows(idx) if self.terminal_observation else None
             t = round(time.time() - self._tstart, 6)
-            for i in idx:
+            for j, i in enumerate(idx):
                 infos[int(i)]["episode"] = {"r": float(buf["last_return"][i]), "l": int(buf["last_length"][i]), "t": t}
                 if trunc is not None:
                     infos[int(i)]["TimeLimit.truncated"] = bool(trunc[i])
+                if term is not None:
+                    infos[int(i)]["terminal_observation"] = term[j]
         return infos
 
     def close(self):
