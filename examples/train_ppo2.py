@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import torch
 
 import gym_reinmav_amd as g
+from gym_reinmav_amd.obs_norm import RunningObsNorm
 from gym_reinmav_amd.ppo import PPO, FusedPolicyCollector, MlpPolicy
 
 
@@ -31,6 +32,9 @@ def main():
     ap.add_argument("--max_episode_steps", type=int, default=0, help="episode time limit H (gym's TimeLimit, inside the kernels); 0 = none")
     ap.add_argument("--bootstrap_truncated", action="store_true",
                     help="with --max_episode_steps: value targets of truncated steps are r + gamma V(s_final) instead of r")
+    ap.add_argument("--normalize-obs", dest="normalize_obs", action="store_true",
+                    help="VecNormalize(ob=True) in front of the nets, inside the rollout kernel (statistics frozen per rollout); "
+                         "with --max_episode_steps it needs --bootstrap_truncated; not with --actor bf16")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -41,9 +45,12 @@ def main():
     if args.bootstrap_truncated and not args.max_episode_steps:
         ap.error("--bootstrap_truncated needs --max_episode_steps")
     env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None)
-    policy = MlpPolicy(env.nS, env.nA).cuda()
+    obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
+    policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()
     if args.load_path:                                      # run.py:188 model.load(load_path)
         policy.load_state_dict(torch.load(args.load_path, map_location="cuda"))
+        if obs_norm is not None and os.path.exists(args.load_path + ".obs_norm"):
+            obs_norm.load_state_dict(torch.load(args.load_path + ".obs_norm"))
     elif kind in ("quad3d", "quad3d_sl"):
         with torch.no_grad():
             policy.pi[2].bias[0] = 9.8                      # start around hover thrust
@@ -65,8 +72,12 @@ def main():
     env.close()
     if args.save_path:                                      # run.py:186 model.save(save_path)
         torch.save(policy.state_dict(), args.save_path)
+        if obs_norm is not None:                            # the statistics belong to the weights
+            torch.save(obs_norm.state_dict(), args.save_path + ".obs_norm")
         print("saved", args.save_path)
     if args.play:                                           # run.py:190-211: obs = env.reset(); loop model.step / env.step
+        if obs_norm is not None:
+            obs_norm.freeze = True                          # evaluation: the policy keeps normalising, the statistics stop moving
         venv = g.QuadrotorVecEnv(args.env, 1, seed=args.seed)
         obs = venv.reset()
         ep_rew = 0.0

@@ -119,6 +119,53 @@ int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_
 /* x[i] <- (x[i] - mean) * rstd for i < count (x 16-byte aligned): advantage normalisation in place. */
 int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rstd);
 
+/* ---- observation normalisation: baselines' VecNormalize(ob=True, ret=False) in front of the nets ------------------------------------
+ * RunningMeanStd (third-party behaviour restated from memory): mean = 0, var = 1, count = epsilon; update(batch of B rows) merges the
+ * batch's mean / population variance / B into them (Chan's parallel formula); normalise(x) = clip((x - mean) / sqrt(var + eps), +-clip).
+ * The four quadrotor kinds; RMAV_REINMAV is RMAV_ERR_INVALID in every call below.
+ *
+ * The statistics live in ONE caller-owned DEVICE buffer of rmav_obs_norm_bytes() bytes, 16-byte aligned (not handle state: several
+ * collectors and a learner share it, and it outlives rmav_destroy).  Every call below is a launch on the handle's stream: nothing
+ * synchronises, and a captured rollout sees the current statistics through the fixed pointer.  Fields (byte offset):
+ *     0  double count          samples seen (starts at count0)
+ *     8  double mean[16]       running mean per feature; features >= nS stay 0
+ *   136  double m2[16]         running sum of squared deviations: var = m2 / count; features >= nS stay at var 1
+ *   264  double eps            the epsilon under the square root
+ *   272  float  clip           the clip (+inf = none), 3 pad words
+ *   288  float  mean_f[16]     \  the tables the kernels read, rewritten by every merge:  mean_f = (float)mean,
+ *   352  float  rstd_f[16]      | rstd_f = (float)(1 / sqrt(var + eps)) (computed in fp64, rounded once); features >= nS: 0 and 1
+ *   416  float  clip_f         /   3 pad words
+ * THE arithmetic, wherever an observation is normalised (rmav_obs_normalize, the rollout below), in fp32, uncontracted, in this order:
+ *     z = (x - mean_f[c]) * rstd_f[c];   z = min(max(z, -clip), clip)
+ * so torch's clamp((obs - mean_f) * rstd_f, -clip, clip) in fp32 reproduces it bit for bit for finite x, and identity statistics
+ * (mean 0, rstd 1, clip +inf) leave the bits of x. */
+int64_t rmav_obs_norm_bytes(void);
+/* mean 0, var 1, count = count0 (baselines: 1e-4), clip > 0 (baselines: 10; +inf allowed), eps >= 0 (baselines: 1e-8); tables from that
+ * state: mean_f = 0, rstd_f = (float)(1 / sqrt(1 + eps)) (= 1.0f for eps <= 5e-8). */
+int rmav_obs_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0);
+/* Batch moments of a stored observation array: batch_out <- 33 doubles on the device (count, mean[16], m2[16]; m2 = sum of squared
+ * deviations from the batch mean; features >= nS zero).  obs: layout RMAV_SOA = [n_rows][nS][pitch] (what the rollouts write; pitch = 0
+ * means N, the first N of every pitch are read) or RMAV_AOS = [n_rows * N][nS] (what rmav_step writes; pitch must be 0).  count =
+ * n_rows * N.  Two stages: per-block fp64 (n, mean, M2) partials combined pairwise (Chan), then a fold; no floating-point atomics - the
+ * same input gives the same bits.  n_rows = 0 leaves an empty record.  Uses the handle's scratch buffer. */
+int rmav_obs_moments(rmav_handle h, const float *obs, int layout, int32_t n_rows, int64_t pitch, double *batch_out);
+/* Merges n_batches consecutive 33-double records (DEVICE) into the running state, in order, with RunningMeanStd's update rule, then
+ * rewrites the tables; empty records are skipped.  n_batches > 1: every rank's record after an all-gather, merged in rank order so that
+ * all ranks end with the same bits.  One tiny launch. */
+int rmav_obs_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches);
+/* out = the arithmetic above applied to in, elementwise (layouts as rmav_obs_moments; out == in allowed; n_rows = 0: no-op). */
+int rmav_obs_normalize(rmav_handle h, const void *stats, const float *in, float *out, int layout, int32_t n_rows, int64_t pitch);
+/* rmav_rollout_policy (handle without a time limit: boot_out and trunc_out must be NULL) or rmav_rollout_policy_boot (handle with one:
+ * boot_out required) with EVERY evaluation of the policy and of the value net - value_out[n_steps] and the bootstrap value of a truncated
+ * episode's terminal state included - fed the normalised observation.  obs_out still holds the RAW state; everything else is laid out as
+ * there.  precision: RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED (the other two have no normalised kernel, for
+ * the reason above: RMAV_ERR_INVALID).  The statistics are FROZEN for the launch - a fused launch has no grid-wide meeting point between
+ * its steps - where baselines updates them every env-step: absorb the rollout afterwards (rmav_obs_moments + rmav_obs_norm_merge on
+ * obs_out).  With identity statistics every output has the bits of rmav_rollout_policy / rmav_rollout_policy_boot. */
+int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weights, const void *stats, float *actions_out, float *obs_out,
+                             float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out,
+                             int precision);
+
 #ifdef __cplusplus
 }
 #endif

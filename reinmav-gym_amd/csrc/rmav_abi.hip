@@ -13,6 +13,7 @@
 
 #include "rmav_handle.hpp"
 #include "rmav_gae.hpp"
+#include "rmav_obs_norm.hpp"
 
 using namespace rmav;
 
@@ -1552,6 +1553,136 @@ int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rst
     if (blocks > 4096) blocks = 4096;   // grid-stride: 16 blocks per CU keep the memory system full
     hipLaunchKernelGGL(k_affine, dim3((unsigned)blocks), dim3(256), 0, h->stream, x, count, mean, rstd);
     HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// ---- observation normalisation (VecNormalize): running statistics on the device, csrc/rmav_obs_norm.hpp ------------------
+namespace {
+int check_norm_handle(rmav_handle h, const char *what) {
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "%s runs the four quadrotor kinds, not RMAV_REINMAV", what);
+    return RMAV_OK;
+}
+int check_stats(const void *stats) {
+    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_obs_norm_bytes() bytes)");
+    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
+    return RMAV_OK;
+}
+// the addressing of an observation array (ObsShape); n_rows >= 1 checked by the caller
+int obs_shape(rmav_handle h, int layout, int32_t n_rows, int64_t pitch, ObsShape &sh) {
+    const int ns = kStateDim[h->kind];
+    if (layout != RMAV_SOA && layout != RMAV_AOS) return rmav_fail(RMAV_ERR_INVALID, "layout must be RMAV_SOA or RMAV_AOS");
+    if (layout == RMAV_SOA) {
+        if (pitch == 0) pitch = h->n;
+        if (pitch < h->n || pitch > (int64_t)0x3fffffff) return rmav_fail(RMAV_ERR_INVALID, "pitch must be 0 (= N) or in [N, 2^30)");
+        sh = ObsShape{h->n, (int64_t)ns * pitch, pitch, 1, n_rows, ns};
+    } else {
+        if (pitch != 0) return rmav_fail(RMAV_ERR_INVALID, "pitch must be 0 with RMAV_AOS");
+        sh = ObsShape{h->n, h->n * ns, 1, ns, n_rows, ns};
+    }
+    return RMAV_OK;
+}
+}  // namespace
+
+int64_t rmav_obs_norm_bytes(void) { return (int64_t)sizeof(ObsNormStats); }
+
+int rmav_obs_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_norm_init")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
+        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    hipLaunchKernelGGL(k_obs_norm_init, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, (int32_t)kStateDim[h->kind], clip, eps, count0);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_obs_moments(rmav_handle h, const float *obs, int layout, int32_t n_rows, int64_t pitch, double *batch_out) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_moments")) return rc;
+    if (!obs || !batch_out) return rmav_fail(RMAV_ERR_INVALID, "obs and batch_out are required (device pointers)");
+    if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
+    ObsShape sh;
+    if (int rc = obs_shape(h, layout, n_rows > 0 ? n_rows : 1, pitch, sh)) return rc;
+    sh.n_rows = n_rows;   // 0 rows: an empty record (count 0), which rmav_obs_norm_merge skips
+    const bool vec = layout == RMAV_SOA && (reinterpret_cast<uintptr_t>(obs) & 15u) == 0 && (sh.feat & 3) == 0;
+    const int64_t cols = vec ? (sh.n + 3) / 4 : sh.n;
+    const int64_t xenv = (cols + 255) / 256;
+    // enough blocks for 256 CUs (8 per CU) when the rows allow it; a thread then walks every rgroups-th row
+    int64_t rgroups = (2048 + xenv * sh.ns - 1) / (xenv * sh.ns);
+    if (rgroups > n_rows) rgroups = n_rows;
+    if (rgroups < 1) rgroups = 1;
+    const int64_t nblk = xenv * rgroups;
+    if (int rc = ensure_scratch(h, (size_t)nblk * sh.ns * sizeof(Moment))) return rc;
+    const dim3 grid((unsigned)nblk, (unsigned)sh.ns);
+    if (vec) hipLaunchKernelGGL(k_obs_moments<true>, grid, dim3(256), 0, h->stream, obs, sh, (int32_t)xenv, (int32_t)rgroups, (Moment *)h->scratch);
+    else hipLaunchKernelGGL(k_obs_moments<false>, grid, dim3(256), 0, h->stream, obs, sh, (int32_t)xenv, (int32_t)rgroups, (Moment *)h->scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_obs_moments_fold, dim3(kNormFeat), dim3(256), 0, h->stream, (const Moment *)h->scratch, (int32_t)nblk, (int32_t)sh.ns, batch_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_obs_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_norm_merge")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
+    if (n_batches == 0) return RMAV_OK;
+    if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 33 doubles on the device)");
+    hipLaunchKernelGGL(k_obs_norm_merge, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, batch, n_batches, (int32_t)kStateDim[h->kind]);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_obs_normalize(rmav_handle h, const void *stats, const float *in, float *out, int layout, int32_t n_rows, int64_t pitch) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_normalize")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
+    if (n_rows == 0) return RMAV_OK;
+    if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
+    ObsShape sh;
+    if (int rc = obs_shape(h, layout, n_rows, pitch, sh)) return rc;
+    const int64_t total = sh.n * sh.ns * (int64_t)n_rows;
+    if ((total + 255) / 256 > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many elements for one launch");
+    hipLaunchKernelGGL(k_obs_normalize, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const ObsNormStats *)stats, in, out, sh);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weights, const void *stats, float *actions_out, float *obs_out,
+                             float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out,
+                             int precision) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_rollout_policy_norm")) return rc;
+    if (precision != RMAV_POLICY_FP32_MFMA && precision != RMAV_POLICY_F16_MFMA && precision != RMAV_POLICY_F16_SHARED)
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_norm runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
+                                           "(the fp32 vector-ALU and bf16 actors have no normalised kernel), got precision %d", precision);
+    if (int rc = check_stats(stats)) return rc;
+    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
+    if (!weights || !logp_out || !value_out)
+        return rmav_fail(RMAV_ERR_INVALID, "weights, logp_out and value_out are required (device pointers)");
+    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
+    if (h->time_limit > 0 && !boot_out)
+        return rmav_fail(RMAV_ERR_INVALID, "boot_out is required on a handle with an episode time limit (as rmav_rollout_policy_boot)");
+    if (h->time_limit <= 0 && (boot_out || trunc_out))
+        return rmav_fail(RMAV_ERR_INVALID, "boot_out / trunc_out need an episode time limit on the handle (rmav_set_time_limit); pass NULL");
+    RolloutArgs a = base_args(h);
+    a.n_steps = n_steps;
+    a.act_out = actions_out;
+    a.obs_out = obs_out;
+    a.rew_out = rew_out;
+    a.done_out = done_out;
+    a.policy_w = weights;
+    a.logp_out = logp_out;
+    a.val_out = value_out;
+    const int kmode = precision == RMAV_POLICY_F16_MFMA ? (int)ACT_POLICY_F16 : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
+                                                                                                                : (int)ACT_POLICY_F32M;
+    const BootArgs bt{boot_out, trunc_out};
+    const NormArgs nm{((const ObsNormStats *)stats)->mean_f};
+    h->xchg.allow = true;
+    if (int rc = rmav_launch_policy_rollout_norm(h, kmode, a, &bt, nm)) return rc;
+    h->t += (uint64_t)n_steps;
     return RMAV_OK;
 }
 

@@ -152,3 +152,7 @@ inline int check_rollout_launch(rmav_handle h, const rmav::RolloutArgs &a) {
 // ACT_POLICY_F16 | ACT_POLICY_F16_SHARED on the handle's stream
 // bt (rmav_rollout_policy_boot): the launch also leaves the bootstrap term of its truncated steps - the *_boot kernels; nullptr otherwise
 RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt = nullptr);
+// ... of rmav_rollout_policy_norm (the *_nrm kernels; kmode = ACT_POLICY_F32M | ACT_POLICY_F16 | ACT_POLICY_F16_SHARED, a quadrotor kind; bt is
+// required when the handle has a time limit and ignored otherwise)
+RMAV_INTERNAL int rmav_launch_policy_rollout_norm(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt,
+                                                  const rmav::NormArgs &nm);

@@ -234,6 +234,38 @@ struct BootArgs {
     uint8_t *trunc_out;
 };
 
+// Observation normalisation (rmav_rollout_policy_norm; the *_nrm rollout kernels), trailing as well.
+//   tab   the fp32 tables of a statistics buffer (rmav_obs_norm.hpp: ObsNormStats::mean_f): mean_f[16] | rstd_f[16] | clip | 3 pad words.
+// Staged once per launch into LDS behind the weights (kNormWords floats); every evaluation of a net reads its operands from there.
+struct NormArgs {
+    const float *tab;
+};
+constexpr int kNormWords = 36;
+// (every block of these kernels has at least 64 threads; a strided loop here instead of the one predicated copy cost the quadrotor2d
+// k_rollout_nrm a stack frame)
+__device__ __forceinline__ void stage_norm(float *dst, const float *tab) {
+    if (threadIdx.x < (unsigned)kNormWords) dst[threadIdx.x] = tab[threadIdx.x];
+}
+// z = clamp((x - mean_f[c]) * rstd_f[c], -clip, clip): subtract, multiply, v_med3_f32, in fp32 (the build is uncontracted) - the
+// order include/rmav_ppo.h fixes.  With the identity tables (mean 0, rstd 1, clip +inf) z has the bits of x.
+__device__ __forceinline__ float norm1(const float *t, int c, float x, float clip) {
+    return __builtin_amdgcn_fmed3f((x - t[c]) * t[16 + c], -clip, clip);
+}
+// the table pointer for one evaluation: opaque to the optimiser, so that the 33 reads stay inside the env-step loop as LDS
+// broadcast reads instead of 33 registers hoisted out of it (the trick of mlp_pair's `net`)
+__device__ __forceinline__ const float *norm_tab(const float *ntab) {
+    uint32_t o = 0u;
+    asm volatile("" : "+v"(o));
+    return ntab + o;
+}
+// the layer-1 input of the actors that take all 16 (padded) components per lane
+template <int NS> __device__ __forceinline__ void norm_state16(const float *ntab, const float (&s)[NS], float (&x)[16]) {
+    const float *t = norm_tab(ntab);
+    const float clip = t[32];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? norm1(t, c, s[c], clip) : 0.0f;
+}
+
 __device__ __forceinline__ uint32_t ep_clock0(const RolloutArgs &a) { return (uint32_t)a.t0; }
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
@@ -360,9 +392,10 @@ __device__ __forceinline__ void wide_cols(const float *tile, rsrc_t r, uint32_t 
 template <int K, int MODE, int ST = ST_DEFAULT, bool FIXED = false>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                     const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false;
+    constexpr bool TL = false, BOOT = false, NORM = false;
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
 #include "rmav_rollout_body.inc"
 }
 // The same kernel under an episode time limit (rmav_set_time_limit): separate symbols, so that the kernels of handles without a limit
@@ -371,8 +404,9 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, FIXED = false, BOOT = false;
+    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false;
     [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
     static_assert(!is_split(MODE) && K != REINMAV, "time-limited launches run the one-wavefront kernels");
 #include "rmav_rollout_body.inc"
 }
@@ -382,8 +416,27 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                          const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
-    constexpr bool TL = true, FIXED = false, BOOT = true;
+    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false;
+    [[maybe_unused]] const NormArgs nm{};
     static_assert(MODE == ACT_POLICY_F32M && K != REINMAV, "the one-wavefront actor of time-limited handles");
+#include "rmav_rollout_body.inc"
+}
+// The fp32 matrix-core actor on NORMALISED observations (rmav_rollout_policy_norm): every evaluation of the policy and the value net -
+// the bootstrap value of the last state and of truncated steps included - takes clamp((s - mean) * rstd, -clip, clip) from the tables
+// in nm; what is stored as obs stays the raw state.  BOOT = the handle has a time limit (such a launch always leaves the bootstrap
+// term: k_rollout_boot's body), otherwise k_rollout's.  Symbols of their own: the kernels above keep their instruction streams.
+template <int K, bool BOOT>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                            const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                            const BootArgs bt) {
+    // The table pointer rides in RolloutArgs::act_in, which the policy modes do not read: the argument block is k_rollout_boot's.  As a
+    // trailing NormArgs (the pair kernels take it that way) the 8 more bytes moved the scalar loads of the argument block, and the
+    // quadrotor2d and quadrotor3d kernels came out with a stack frame (64 / 32 bytes per lane, no VGPR spill: these kernels run out of
+    // scalar registers) wherever the argument was placed (profiles/r09/obs_norm.md).
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
 }
 

@@ -1,6 +1,7 @@
 // rmav_pair_body.inc - the body of k_rollout_pair / k_rollout_pair_tl (rmav_policy_pair.hpp), included into both kernels: textually, for the
-// reason rmav_rollout_body.inc gives.  In scope: template parameters K, FMT, the constexpr bools TL and BOOT (k_rollout_pair_boot: the launch also
-// leaves the bootstrap term of its truncated steps) and the kernel arguments a, p_shared, pc_shared, tl, bt.
+// reason rmav_rollout_body.inc gives.  In scope: template parameters K, FMT, the constexpr bools TL, BOOT (k_rollout_pair_boot: the launch also
+// leaves the bootstrap term of its truncated steps) and NORM (k_rollout_pair_nrm: both nets take normalised observations; the tables sit
+// between the weights and the tiles) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     using L = MfmaLayout;
     using PT = PairTile<NS, NA>;
@@ -16,7 +17,8 @@
     const uint32_t col = (uint32_t)n * 4u, off = li * 4u;
     const int32_t T = a.n_steps;
     const bool track = (a.flags & F_TRACK) != 0, auto_reset = (a.flags & F_AUTO_RESET) != 0;
-    float *tile = lds_w + L::TOTAL + pair * (BOOT ? PairBootTile<NS, NA>::WORDS : PT::WORDS);   // this pair's hand-over tiles
+    [[maybe_unused]] const float *ntab = lds_w + L::TOTAL;
+    float *tile = lds_w + L::TOTAL + (NORM ? kNormWords : 0) + pair * (BOOT ? PairBootTile<NS, NA>::WORDS : PT::WORDS);   // this pair's hand-over tiles
     float *ztile = tile + lane, *otile = tile + PT::Z_WORDS + lane;
 
     if (a.xsend && blockIdx.x == 0 && threadIdx.x == 0)   // armed statistics exchange: this launch has begun (see k_rollout)
@@ -25,6 +27,7 @@
         const float4 *src = reinterpret_cast<const float4 *>(a.policy_w);
         float4 *dst = reinterpret_cast<float4 *>(lds_w);
         for (int q = threadIdx.x; q < L::TOTAL / 4; q += blockDim.x) dst[q] = src[q];
+        if constexpr (NORM) stage_norm(lds_w + L::TOTAL, nm.tab);
         __syncthreads();
         if constexpr (FMT == FMT_F16) fold_biases_f16();
         else scale_biases_for_tanh();
@@ -86,8 +89,12 @@
                 if (done_out) done_out += n;
             }
             float x[16];
+            if constexpr (NORM) {
+                norm_state16<NS>(ntab, s, x);
+            } else {
 #pragma unroll
-            for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+                for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+            }
             frag b0, b1;
             state_frags<FMT>(x, b0, b1);
             float t0[4], t1[4];
@@ -106,8 +113,15 @@
                     if (__ballot(tr) != 0) {   // wave-uniform
                         const float *fin = tile + PB::FIN + ((k - 1) & 1) * PB::FIN_HALF + lane;
                         float xf[16];
+                        if constexpr (NORM) {
+                            float sf[NS];
 #pragma unroll
-                        for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? fin[c * 64] : 0.0f;
+                            for (int c = 0; c < NS; ++c) sf[c] = fin[c * 64];
+                            norm_state16<NS>(ntab, sf, xf);
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? fin[c * 64] : 0.0f;
+                        }
                         frag f0, f1;
                         state_frags<FMT>(xf, f0, f1);
                         float u0[4], u1[4];
@@ -180,8 +194,12 @@
             for (int c = 0; c < NA; ++c) z[c] = zt[c * 64];
         }
         float x[16];
+        if constexpr (NORM) {
+            norm_state16<NS>(ntab, s, x);
+        } else {
 #pragma unroll
-        for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+            for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+        }
         frag b0, b1;
         state_frags<FMT>(x, b0, b1);
         float t0[4], t1[4], act[NA];

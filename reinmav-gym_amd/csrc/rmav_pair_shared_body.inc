@@ -1,6 +1,7 @@
 // rmav_pair_shared_body.inc - the body of k_rollout_pair_shared / k_rollout_pair_shared_tl (rmav_policy_pair.hpp), included into both kernels: textually, for the
-// reason rmav_rollout_body.inc gives.  In scope: template parameters K, the constexpr bools TL and BOOT (k_rollout_pair_shared_boot: the launch also leaves
-// the bootstrap term of its truncated steps) and the kernel arguments a, p_shared, pc_shared, tl, bt.
+// reason rmav_rollout_body.inc gives.  In scope: template parameters K, the constexpr bools TL, BOOT (k_rollout_pair_shared_boot: the launch also leaves
+// the bootstrap term of its truncated steps) and NORM (k_rollout_pair_shared_nrm: the net takes normalised observations; the tables sit between the
+// weights and the tiles) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     using L = MfmaLayout;
     using PT = PairTile<NS, NA>;
@@ -16,7 +17,8 @@
     const uint32_t col = (uint32_t)n * 4u, off = li * 4u;
     const int32_t T = a.n_steps;
     const bool track = (a.flags & F_TRACK) != 0, auto_reset = (a.flags & F_AUTO_RESET) != 0;
-    float *tile = lds_w + kSharedWeights + pair * (BOOT ? SharedBootTile<NS, NA>::WORDS : ST_::WORDS);
+    [[maybe_unused]] const float *ntab = lds_w + kSharedWeights;
+    float *tile = lds_w + kSharedWeights + (NORM ? kNormWords : 0) + pair * (BOOT ? SharedBootTile<NS, NA>::WORDS : ST_::WORDS);
     float *ztile = tile + lane, *otile = tile + PT::Z_WORDS + lane, *mtile = tile + ST_::MEAN;
 
     if (a.xsend && blockIdx.x == 0 && threadIdx.x == 0)
@@ -25,6 +27,7 @@
         const float4 *src = reinterpret_cast<const float4 *>(a.policy_w);
         float4 *dst = reinterpret_cast<float4 *>(lds_w);
         for (int q = threadIdx.x; q < kSharedWeights / 4; q += blockDim.x) dst[q] = src[q];
+        if constexpr (NORM) stage_norm(lds_w + kSharedWeights, nm.tab);
         __syncthreads();
         for (int q = threadIdx.x; q < 160; q += blockDim.x) {   // fold_biases_f16 for net 0 only
             float *w = lds_w;
@@ -75,9 +78,19 @@
         auto eval_tile1 = [&](int half) {
             const float *obs = tile + PT::Z_WORDS + half * PT::O_HALF + 32u + (lane & 31u);
             float x[8];
+            [[maybe_unused]] const float *nt = nullptr;
+            [[maybe_unused]] float nclip = 0.0f;
+            if constexpr (NORM) {
+                nt = norm_tab(ntab);
+                nclip = nt[32];
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float lo = (j < NS) ? obs[j * 64] : 0.0f, hi = (8 + j < NS) ? obs[(8 + j) * 64] : 0.0f;
+                float lo = (j < NS) ? obs[j * 64] : 0.0f, hi = (8 + j < NS) ? obs[(8 + j) * 64] : 0.0f;
+                if constexpr (NORM) {
+                    if (j < NS) lo = norm1(nt, j, lo, nclip);
+                    if (8 + j < NS) hi = norm1(nt, 8 + j, hi, nclip);
+                }
                 x[j] = h ? hi : lo;
             }
             float o4[4];
@@ -122,14 +135,14 @@
             __syncthreads();                                              // X(k): the means of envs 32..63 are in the tile
             if (k > 0) drain((k - 1) & 1);
             if constexpr (BOOT) {
-                if (k > 0) shared_boot_tile1<NS, NA>(tile, (k - 1) & 1, bt, (int64_t)(k - 1) * n, make_rsrc_bounded(a.state, 0u), off, li);
+                if (k > 0) shared_boot_tile1<NS, NA, NORM>(tile, (k - 1) & 1, bt, (int64_t)(k - 1) * n, make_rsrc_bounded(a.state, 0u), off, li, ntab);
             }
             if (k + 1 < T) draw(k + 1);
             __syncthreads();                                              // Y(k): step k's outputs are in the tile
         }
         eval_tile1((T - 1) & 1);                                          // bootstrap values of envs 32..63
         drain((T - 1) & 1);
-        if constexpr (BOOT) shared_boot_tile1<NS, NA>(tile, (T - 1) & 1, bt, (int64_t)(T - 1) * n, make_rsrc_bounded(a.state, 0u), off, li);
+        if constexpr (BOOT) shared_boot_tile1<NS, NA, NORM>(tile, (T - 1) & 1, bt, (int64_t)(T - 1) * n, make_rsrc_bounded(a.state, 0u), off, li, ntab);
         return;
     }
 
@@ -187,11 +200,22 @@
     float *val_out = a.val_out;
     auto eval_tile0 = [&](float (&o4)[4]) {   // lane (n, h): components [8h, 8h + 8) of env n - its own for h = 0, lane n's for h = 1
         float x[8];
+        [[maybe_unused]] const float *nt = nullptr;
+        [[maybe_unused]] float nclip = 0.0f;
+        if constexpr (NORM) {
+            nt = norm_tab(ntab);
+            nclip = nt[32];
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float lo = (j < NS) ? s[j] : 0.0f;
+            float lo = (j < NS) ? s[j] : 0.0f;
             float hi = 0.0f;
-            if (8 + j < NS) hi = xor32(s[8 + j]);   // lanes 32..63 receive lane - 32's component 8 + j  (folded: NS is a constant)
+            if constexpr (NORM) {   // normalised by the lane that owns the env, before the exchange
+                if (j < NS) lo = norm1(nt, j, lo, nclip);
+                if (8 + j < NS) hi = xor32(norm1(nt, 8 + j, s[8 + j], nclip));
+            } else {
+                if (8 + j < NS) hi = xor32(s[8 + j]);   // lanes 32..63 receive lane - 32's component 8 + j  (folded: NS is a constant)
+            }
             x[j] = h ? hi : lo;
         }
         mlp_half_f16(pack_frag_f16(x), o4);
@@ -249,11 +273,22 @@
 #pragma unroll
                     for (int c = 0; c < NS; ++c) fin[c * 64] = s[c];
                     float xf[8], u4[4];
+                    [[maybe_unused]] const float *nt = nullptr;
+                    [[maybe_unused]] float nclip = 0.0f;
+                    if constexpr (NORM) {
+                        nt = norm_tab(ntab);
+                        nclip = nt[32];
+                    }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        const float lo = (j < NS) ? s[j] : 0.0f;
+                        float lo = (j < NS) ? s[j] : 0.0f;
                         float hi = 0.0f;
-                        if (8 + j < NS) hi = xor32(s[8 + j]);
+                        if constexpr (NORM) {
+                            if (j < NS) lo = norm1(nt, j, lo, nclip);
+                            if (8 + j < NS) hi = xor32(norm1(nt, 8 + j, s[8 + j], nclip));
+                        } else {
+                            if (8 + j < NS) hi = xor32(s[8 + j]);
+                        }
                         xf[j] = h ? hi : lo;
                     }
                     mlp_half_f16(pack_frag_f16(xf), u4);

@@ -43,7 +43,8 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
 // workgroup share one LDS copy of the weights (30 KB) but also one s_barrier; RMAV_TUNE_PAIR_GROUP = 1 .. 4 overrides.
 // (The *_boot kernels' larger tiles - pair_boot_lds_bytes / shared_boot_lds_bytes - fit the 160 KiB of a workgroup at every group
 // count: 4 pairs of the 16-state kind take 113 KiB / 101 KiB.)
-static_assert(pair_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) <= (160u << 10) && shared_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) <= (160u << 10),
+static_assert(pair_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + sizeof(float) * kNormWords <= (160u << 10) &&
+                  shared_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + sizeof(float) * kNormWords <= (160u << 10),
               "the hand-over tiles with their terminal-state areas must fit one workgroup's LDS");
 template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
     RolloutArgs a = a_in;
@@ -101,6 +102,50 @@ template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs
     return check_rollout_launch(h, a);
 }
 
+// rmav_rollout_policy_norm: the *_nrm kernels (normalised observations in front of the nets) of the three actors a time-limited handle
+// accepts; a handle with a time limit takes the BOOT variant (bt is required there), one without the plain one.  Same launch shapes
+// as the kernels they derive from, kNormWords more LDS words.
+template <int K> int launch_policy_norm_k(rmav_handle h, int kmode, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs &nm) {
+    if constexpr (K == REINMAV) {
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv has no normalised rollout");
+    } else {
+        RolloutArgs a = a_in;
+        take_armed_exchange(h, a, kmode == ACT_POLICY_F32M ? 32 : 64);
+        const typename Env<K>::P p = derive_env<K>(h->params);
+        const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
+        const bool boot = h->time_limit > 0;
+        const TimeLimitArgs tl = boot ? tl_args(h) : TimeLimitArgs{};
+        const BootArgs b = boot ? *bt : BootArgs{};
+        constexpr size_t nbytes = sizeof(float) * kNormWords;
+        const int forced = h->tune[RMAV_TUNE_PAIR_GROUP];
+        if (kmode == ACT_POLICY_F32M) {
+            const int64_t per_wg = block_size(h) / 2;
+            const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(block_size(h));
+            const size_t lds = sizeof(float) * (size_t)Mfma32Layout::TOTAL + nbytes;
+            a.act_in = nm.tab;   // (k_rollout_nrm takes the tables there: see the kernel)
+            if (boot) hipLaunchKernelGGL((k_rollout_nrm<K, true>), grid, block, lds, h->stream, a, p, pc, tl, b);
+            else hipLaunchKernelGGL((k_rollout_nrm<K, false>), grid, block, lds, h->stream, a, p, pc, tl, b);
+        } else if (kmode == ACT_POLICY_F16) {
+            const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : (h->n <= 98304 ? 4 : 2);   // as launch_rollout_pair
+            const int64_t per_wg = 64 * g;
+            const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
+            if (boot) hipLaunchKernelGGL((k_rollout_pair_nrm<K, true>), grid, block, pair_boot_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
+            else hipLaunchKernelGGL((k_rollout_pair_nrm<K, false>), grid, block, pair_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
+        } else if (kmode == ACT_POLICY_F16_SHARED) {
+            const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : 2;   // as launch_rollout_pair_shared
+            const int64_t per_wg = 64 * g;
+            const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
+            if (boot)
+                hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, true>), grid, block, shared_boot_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
+            else
+                hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, false>), grid, block, shared_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no normalised kernel for policy mode %d", kmode);
+        }
+        return check_rollout_launch(h, a);
+    }
+}
+
 template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt) {
     // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
     switch (kmode) {
@@ -125,4 +170,14 @@ int rmav_launch_policy_rollout(rmav_handle h, int kmode, const RolloutArgs &a, c
     case RMAV_REINMAV: return launch_policy_k<REINMAV>(h, kmode, a, nullptr);
     }
     return rmav_fail(RMAV_ERR_INVALID, "bad kind");
+}
+
+int rmav_launch_policy_rollout_norm(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs &nm) {
+    switch (h->kind) {
+    case RMAV_QUAD2D: return launch_policy_norm_k<QUAD2D>(h, kmode, a, bt, nm);
+    case RMAV_QUAD2D_SL: return launch_policy_norm_k<QUAD2D_SL>(h, kmode, a, bt, nm);
+    case RMAV_QUAD3D: return launch_policy_norm_k<QUAD3D>(h, kmode, a, bt, nm);
+    case RMAV_QUAD3D_SL: return launch_policy_norm_k<QUAD3D_SL>(h, kmode, a, bt, nm);
+    }
+    return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_norm runs the four quadrotor kinds");
 }

@@ -66,6 +66,7 @@ template <int NS, int NA> struct PairBootTile {
 template <int K> constexpr size_t pair_boot_lds_bytes(int g) {
     return sizeof(float) * ((size_t)MfmaLayout::TOTAL + (size_t)g * PairBootTile<Dims<K>::NS, Dims<K>::NA>::WORDS);
 }
+// (the *_nrm kernels: + kNormWords words of tables between the weights and the tiles)
 template <int K> constexpr size_t pair_lds_bytes(int g) {
     return sizeof(float) * ((size_t)MfmaLayout::TOTAL + (size_t)g * PairTile<Dims<K>::NS, Dims<K>::NA>::WORDS);
 }
@@ -230,17 +231,19 @@ __device__ __forceinline__ void state_frags(const float (&x)[16], typename PairO
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                           const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false;
+    constexpr bool TL = false, BOOT = false, NORM = false;
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
 #include "rmav_pair_body.inc"
 }
 // ... under an episode time limit (separate symbols: see k_rollout_tl)
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, BOOT = false;
+    constexpr bool TL = true, BOOT = false, NORM = false;
     [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
 #include "rmav_pair_body.inc"
 }
@@ -249,8 +252,21 @@ template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                const BootArgs bt) {
-    constexpr bool TL = true, BOOT = true;
+    constexpr bool TL = true, BOOT = true, NORM = false;
+    [[maybe_unused]] const NormArgs nm{};
     static_assert(K != REINMAV && FMT == FMT_F16, "the (actor, critic) pair of time-limited handles");
+#include "rmav_pair_body.inc"
+}
+// The f16 pair on NORMALISED observations (rmav_rollout_policy_norm; see k_rollout_nrm): both wavefronts normalise what they feed
+// their net - the actor its registers, the critic the raw state from the hand-over tile, which it also stores.  BOOT = the handle has
+// a time limit (k_rollout_pair_boot's body and tiles), otherwise k_rollout_pair's.  kNormWords more LDS words in front of the tiles.
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                              const BootArgs bt, const NormArgs nm) {
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_body.inc"
 }
 
@@ -327,9 +343,9 @@ template <int NS, int NA> struct SharedBootTile {
 template <int K> constexpr size_t shared_boot_lds_bytes(int g) {
     return sizeof(float) * ((size_t)kSharedWeights + (size_t)g * SharedBootTile<Dims<K>::NS, Dims<K>::NA>::WORDS);
 }
-template <int NS, int NA>
+template <int NS, int NA, bool NORM>
 __device__ __forceinline__ void shared_boot_tile1(const float *tile, int half, const BootArgs &bt, int64_t step_off, rsrc_t r_none,
-                                                  uint32_t off, uint32_t li) {
+                                                  uint32_t off, uint32_t li, [[maybe_unused]] const float *ntab) {
     using PT = PairTile<NS, NA>;
     using SB = SharedBootTile<NS, NA>;
     const uint32_t lane = threadIdx.x & 63u, h = lane >> 5;
@@ -338,9 +354,19 @@ __device__ __forceinline__ void shared_boot_tile1(const float *tile, int half, c
     if (__ballot(tr) != 0) {   // wave-uniform
         const float *fin = tile + SB::FIN + half * SB::FIN_HALF + 32u + (lane & 31u);
         float x[8], u4[4];
+        [[maybe_unused]] const float *nt = nullptr;
+        [[maybe_unused]] float nclip = 0.0f;
+        if constexpr (NORM) {
+            nt = norm_tab(ntab);
+            nclip = nt[32];
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float lo = (j < NS) ? fin[j * 64] : 0.0f, hi = (8 + j < NS) ? fin[(8 + j) * 64] : 0.0f;
+            float lo = (j < NS) ? fin[j * 64] : 0.0f, hi = (8 + j < NS) ? fin[(8 + j) * 64] : 0.0f;
+            if constexpr (NORM) {
+                if (j < NS) lo = norm1(nt, j, lo, nclip);
+                if (8 + j < NS) hi = norm1(nt, 8 + j, hi, nclip);
+            }
             x[j] = h ? hi : lo;
         }
         mlp_half_f16(pack_frag_f16(x), u4);
@@ -354,16 +380,18 @@ __device__ __forceinline__ void shared_boot_tile1(const float *tile, int half, c
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                  const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false;
+    constexpr bool TL = false, BOOT = false, NORM = false;
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
 #include "rmav_pair_shared_body.inc"
 }
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, BOOT = false;
+    constexpr bool TL = true, BOOT = false, NORM = false;
     [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
 #include "rmav_pair_shared_body.inc"
 }
@@ -371,8 +399,18 @@ template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                       const BootArgs bt) {
-    constexpr bool TL = true, BOOT = true;
+    constexpr bool TL = true, BOOT = true, NORM = false;
+    [[maybe_unused]] const NormArgs nm{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
+#include "rmav_pair_shared_body.inc"
+}
+// ... on NORMALISED observations (rmav_rollout_policy_norm; see k_rollout_pair_nrm)
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                                     const BootArgs bt, const NormArgs nm) {
+    constexpr bool TL = BOOT, NORM = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_shared_body.inc"
 }
 

@@ -3,7 +3,8 @@
 // rather than the kernel's constant argument block - before inlining it, and the kernels came out with a different instruction
 // stream (tools/isa_compare.py, profiles/r07/time_limit.md).  In scope: template parameters K, MODE, ST, FIXED, the constexpr
 // bool TL (the launch has an episode time limit), the constexpr bool BOOT (it also leaves the bootstrap term of truncated steps:
-// k_rollout_boot) and the kernel arguments a, p_shared, pc_shared, tl, bt.
+// k_rollout_boot), the constexpr bool NORM (the nets take normalised observations: k_rollout_nrm) and the kernel arguments a,
+// p_shared, pc_shared, tl, bt, nm.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     constexpr int AUX = StoreAux<ST>::value;
     // ACT_RANDOM_SPLIT: 128-thread workgroups, both wavefronts address the same 64 envs
@@ -405,6 +406,7 @@
         const float4 *src = reinterpret_cast<const float4 *>(a.policy_w);
         float4 *dst = reinterpret_cast<float4 *>(lds_w);
         for (int q = threadIdx.x; q < NW4; q += blockDim.x) dst[q] = src[q];
+        if constexpr (NORM) stage_norm(lds_w + Mfma32Layout::TOTAL, nm.tab);   // k_rollout_nrm: the tables, behind the weights
         __syncthreads();
         if constexpr (MODE == ACT_POLICY_BF16) {
             scale_biases_for_tanh();
@@ -594,8 +596,12 @@
             float act[NA];
             if constexpr (is_mfma_policy(MODE)) {
                 float x[16], mean[4], val0, z[4];
+                if constexpr (NORM) {
+                    norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, s, x);
+                } else {
 #pragma unroll
-                for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+                    for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+                }
                 if constexpr (MODE == ACT_POLICY_BF16) policy_forward_mfma(x, mean, val0);
                 else policy_forward_mfma32<NS>(x, mean, val0);
                 gaussian4(a.seed, env_id, a.t0 + (uint64_t)k, z);
@@ -724,8 +730,12 @@
                     float bv = 0.0f;
                     if (__ballot(trunc) != 0) {
                         float xf[16];
+                        if constexpr (NORM) {
+                            norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, s, xf);
+                        } else {
 #pragma unroll
-                        for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? s[c] : 0.0f;
+                            for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? s[c] : 0.0f;
+                        }
                         const float vf = value_forward_mfma32<NS>(xf);
                         if (trunc) bv = vf;
                     }
@@ -906,8 +916,12 @@
 
         if constexpr (is_mfma_policy(MODE)) {   // bootstrap value of the state the rollout ends in
             float x[16], mean[4], val0;
+            if constexpr (NORM) {
+                norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, s, x);
+            } else {
 #pragma unroll
-            for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+                for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
+            }
             if constexpr (MODE == ACT_POLICY_BF16) policy_forward_mfma(x, mean, val0);
             else policy_forward_mfma32<NS>(x, mean, val0);
             buf_st(make_rsrc(val_out), off, 0, val0);

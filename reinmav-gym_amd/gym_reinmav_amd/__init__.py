@@ -9,10 +9,10 @@ from . import _abi
 from ._abi import RmavError
 from .core import BatchedQuadrotor
 from .registration import ENTRY_POINTS, make, register_envs
-from .vec_env import ENV_IDS, QuadrotorVecEnv
+from .vec_env import ENV_IDS, QuadrotorVecEnv, VecNormalize
 
 register_envs()
 
 __all__ = ["BatchedQuadrotor", "QuadrotorVecEnv", "RmavError", "make", "register_envs", "ENTRY_POINTS", "ENV_IDS",
-           "_abi"]
+           "VecNormalize", "_abi"]
 __version__ = "0.1.0"

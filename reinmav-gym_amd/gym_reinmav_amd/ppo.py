@@ -70,11 +70,19 @@ class MlpPolicy(torch.nn.Module):
     ``value_network``: ``'copy'`` (default) = a separate value net of the same shape - baselines' MuJoCo default and its classic
     ``MlpPolicy``; ``'shared'`` = a scalar value head on the policy's latent - what baselines' ``build_policy`` does when
     ``value_network`` is None, i.e. for an env type without a ppo2 defaults entry such as the native envs of gym_reinmav
-    (``run.py:63-68``; third-party behaviour restated from memory).  ``self.vf`` is then the one-layer head."""
+    (``run.py:63-68``; third-party behaviour restated from memory).  ``self.vf`` is then the one-layer head.
 
-    def __init__(self, n_obs: int, n_act: int, hidden: int = 64, init_logstd: float = 0.0, value_network: str = "copy"):
+    ``obs_norm`` (a :class:`~gym_reinmav_amd.obs_norm.RunningObsNorm`): ``forward`` first normalises its input,
+    ``clamp((obs - mean_f) * rstd_f, -clip, clip)`` in fp32 from the statistics buffer's tables - the numbers the in-kernel actors of
+    ``rmav_rollout_policy_norm`` feed their first layer, bit for bit.  No gradient flows into the statistics; the collectors and
+    ``PPO.update`` keep storing and passing RAW observations."""
+
+    def __init__(self, n_obs: int, n_act: int, hidden: int = 64, init_logstd: float = 0.0, value_network: str = "copy", obs_norm=None):
         super().__init__()
         assert value_network in ("copy", "shared")
+        if obs_norm is not None and obs_norm.n_obs != n_obs:
+            raise ValueError("obs_norm was made for another observation size")
+        self.obs_norm = obs_norm
         self.shared = value_network == "shared"
         mk = lambda i, o: torch.nn.Linear(i, o)  # noqa: E731
         self.pi = torch.nn.ModuleList([mk(n_obs, hidden), mk(hidden, hidden), mk(hidden, n_act)])
@@ -100,6 +108,8 @@ class MlpPolicy(torch.nn.Module):
 
     def forward(self, obs_fm: torch.Tensor):
         """obs_fm [nS, N] -> (mean [nA, N], value [N])."""
+        if self.obs_norm is not None:
+            obs_fm = self.obs_norm.normalize(obs_fm)
         if self.shared:
             h = torch.tanh(self._lin(self.pi[1], torch.tanh(self._lin(self.pi[0], obs_fm))))
             return self._lin(self.pi[2], h), self._lin(self.vf[0], h)[0]
@@ -454,7 +464,12 @@ class FusedPolicyCollector:
 
         ``bootstrap_truncated=True`` (needs ``env.max_episode_steps``): the launch is ``rmav_rollout_policy_boot`` and the collector
         also owns ``boot [T, N]`` = the launch's value net on the state a truncated episode ended in (0 where the step was not
-        truncated) and ``trunc [T, N]``; ``PPO.update`` then targets ``r + gamma V(s_final)`` on those steps."""
+        truncated) and ``trunc [T, N]``; ``PPO.update`` then targets ``r + gamma V(s_final)`` on those steps.
+
+        A policy with ``obs_norm`` runs ``rmav_rollout_policy_norm``: both nets see the normalised observation, with the statistics
+        FROZEN for the launch (``obs_norm.py``); ``obs`` stays raw.  The fp32 matrix-core actor, ``f16_mfma=True`` or a shared-trunk
+        policy; on an env with ``max_episode_steps`` the launch always leaves ``boot`` / ``trunc``, so ``bootstrap_truncated`` is
+        required there."""
         import ctypes as C
 
         assert not (bf16_mfma and f16_mfma)
@@ -471,6 +486,16 @@ class FusedPolicyCollector:
         if getattr(env, "max_episode_steps", None) and (bf16_mfma or not (f32_mfma or f16_mfma)):
             raise ValueError("an env with max_episode_steps runs the fp32 matrix-core actor (the default), f16_mfma=True or a "
                              "shared-trunk policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no time-limited kernel")
+        norm = getattr(policy, "obs_norm", None)
+        if norm is not None:
+            if bf16_mfma or not (f32_mfma or f16_mfma):
+                raise ValueError("a policy with obs_norm runs the fp32 matrix-core actor (the default), f16_mfma=True or a shared-trunk "
+                                 "policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no normalised kernel")
+            if getattr(env, "max_episode_steps", None) and not bootstrap_truncated:
+                raise ValueError("a policy with obs_norm on an env with max_episode_steps needs bootstrap_truncated=True "
+                                 "(rmav_rollout_policy_norm always leaves the bootstrap term there)")
+            if norm.buf.device != torch.device("cuda", env.device):
+                raise ValueError("policy.obs_norm must live on the env's device")
         self.env, self.policy, self.T = env, policy, int(nsteps)
         self.bf16_mfma, self.f32_mfma, self.f16_mfma = bool(bf16_mfma), bool(f32_mfma), bool(f16_mfma)
         self._C, self._A = C, A
@@ -503,9 +528,11 @@ class FusedPolicyCollector:
                 raise ValueError("bootstrap_truncated=True needs an env with max_episode_steps")
             self.boot = torch.empty((T, N), **f32)
             self.trunc = torch.empty((T, N), dtype=torch.uint8, device=dev)
-        self._call = (A.lib().rmav_rollout_policy_boot if bootstrap_truncated else A.lib().rmav_rollout_policy,
-                      self.T, p(self.weights), p(self.act), p(self.obs[1:]), p(self.rew), p(self.done), p(self.logp), p(self.val)) + (
-                      (p(self.boot), p(self.trunc)) if bootstrap_truncated else ()) + (
+        self._call = (A.lib().rmav_rollout_policy_norm if norm is not None else
+                      A.lib().rmav_rollout_policy_boot if bootstrap_truncated else A.lib().rmav_rollout_policy,
+                      self.T, p(self.weights)) + ((C.c_void_p(norm.data_ptr()),) if norm is not None else ()) + (
+                      p(self.act), p(self.obs[1:]), p(self.rew), p(self.done), p(self.logp), p(self.val)) + (
+                      (p(self.boot), p(self.trunc)) if bootstrap_truncated else (None, None) if norm is not None else ()) + (
                       A.POLICY_F16_SHARED if shared else A.POLICY_F16_MFMA if self.f16_mfma else A.POLICY_BF16_MFMA if self.bf16_mfma
                       else A.POLICY_FP32_MFMA if self.f32_mfma else A.POLICY_FP32,)
 
@@ -614,6 +641,11 @@ class PPO:
                 torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
                 self.opt.step()
                 stats = {"pg_loss": pg.detach(), "vf_loss": vf.detach(), "ratio_max": ratio.detach().max()}
+        # observation statistics: frozen while the rollout was collected and learned from, now they absorb its T x N observations
+        # (every rank, same order; obs_norm.py explains the difference from baselines)
+        norm = getattr(self.policy, "obs_norm", None)
+        if norm is not None:
+            norm.update(ro.obs[:T], layout="soa", env=ro.env)
         var_y = ret.var()
         stats["explained_variance"] = 1.0 - (ret - val_old).var() / (var_y + 1e-8)
         return {k: float(v) for k, v in stats.items()}

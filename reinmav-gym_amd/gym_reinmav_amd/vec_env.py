@@ -255,3 +255,76 @@ class QuadrotorVecEnv:
     def close(self):
         self._hnd = None
         self.env.close()
+
+
+class VecNormalize:
+    """baselines' ``VecNormalize(venv, ob=True, ret=False)`` around a :class:`QuadrotorVecEnv`: ``reset()`` and ``step_wait()`` first
+    merge the fresh ``[N, nS]`` observation into the running statistics and then return it normalised,
+    ``clip((obs - mean) / sqrt(var + epsilon), -clipob, clipob)`` - baselines' order, every step (this path has a meeting point per
+    step; the fused rollouts freeze the statistics per launch instead, see ``obs_norm.py``).  Three small launches behind the step
+    (``rmav_obs_moments``, ``rmav_obs_norm_merge``, ``rmav_obs_normalize``) on the env's stream, device tensors in and out, no host
+    synchronisation; with ``numpy_io`` the observation makes the round trip through the device.  Rewards, dones and episode infos
+    are the wrapped env's.  An info's ``'terminal_observation'`` is normalised with the same statistics as the step's observation
+    (what stable-baselines3's ``VecNormalize`` does).
+
+    ``ret=True`` (return / reward normalisation, ``cliprew``) raises ``ValueError``: it needs a per-env discounted-return carry that
+    the kernels do not have yet.  ``self.obs_norm`` is the :class:`~gym_reinmav_amd.obs_norm.RunningObsNorm`; hand it to
+    ``MlpPolicy(obs_norm=...)`` only if the policy is to see RAW observations elsewhere - a policy fed by this wrapper needs none."""
+
+    def __init__(self, venv, ob: bool = True, ret: bool = False, clipob: float = 10.0, epsilon: float = 1e-8):
+        if ret:
+            raise ValueError("VecNormalize(ret=True): return / reward normalisation is not implemented (it needs a per-env "
+                             "discounted-return carry in the kernels); only observations are normalised - pass ret=False")
+        from .obs_norm import RunningObsNorm
+
+        self.venv, self.ob = venv, bool(ob)
+        self.num_envs, self.numpy_io = venv.num_envs, venv.numpy_io
+        self.action_space, self.observation_space = venv.action_space, venv.observation_space
+        self._dev = torch.device("cuda", venv.env.device)
+        self.obs_norm = RunningObsNorm(venv.env.nS, self._dev, clip=clipob, eps=epsilon)
+
+    def _obfilt(self, obs):
+        if not self.ob:
+            return obs
+        env = self.venv.env
+        if self.numpy_io:
+            t = torch.from_numpy(np.ascontiguousarray(obs, dtype=np.float32)).to(self._dev)
+            self.obs_norm.update(t, layout="aos", env=env)
+            return self.obs_norm.normalize(t, out=t, layout="aos", env=env).cpu().numpy()
+        self.obs_norm.update(obs, layout="aos", env=env)
+        return self.obs_norm.normalize(obs, layout="aos", env=env)
+
+    def _norm_rows(self, rows):
+        """host rows [k, nS] with the current tables, in the kernels' fp32 arithmetic"""
+        n = self.obs_norm
+        m, r, c = n.mean_f.cpu().numpy(), n.rstd_f.cpu().numpy(), np.float32(n.clip)
+        return np.clip((np.asarray(rows, np.float32) - m) * r, -c, c)
+
+    def reset(self):
+        return self._obfilt(self.venv.reset())
+
+    def step_async(self, actions):
+        self.venv.step_async(actions)
+
+    def step_wait(self):
+        obs, rew, done, infos = self.venv.step_wait()
+        obs = self._obfilt(obs)
+        if self.ob and getattr(self.venv, "terminal_observation", False):
+            if isinstance(infos, LazyInfos):
+                raw = infos._terminal
+                infos._terminal = lambda idx: self._norm_rows(raw(idx))
+            else:
+                for info in infos:
+                    if "terminal_observation" in info:
+                        info["terminal_observation"] = self._norm_rows(info["terminal_observation"][None])[0]
+        return obs, rew, done, infos
+
+    def step(self, actions):
+        self.step_async(actions)
+        return self.step_wait()
+
+    def close(self):
+        self.venv.close()
+
+    def __getattr__(self, name):   # everything else (env, dict_infos, ...) is the wrapped env's
+        return getattr(self.__dict__["venv"], name)
