@@ -174,8 +174,7 @@ template <int K, int MODE, int ST>
 int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, 64, publishes_start(MODE));
-    const typename Env<K>::P p = derive_env<K>(h->params);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
+    const KindParams<K> kp = kind_params<K>(h);
     static_assert(!is_policy(MODE), "the policy-in-kernel rollouts are launched from rmav_policy_abi.hip");
     const size_t lds = (ST == ST_AOS_LDS) ? sizeof(float) * AosTile<Dims<K>::NS>::WORDS * (block_size(h) / 64) : 0;
     if constexpr (is_split(MODE)) {
@@ -204,63 +203,26 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
         bool launched = false;
         if constexpr (ST == ST_WRITE_THROUGH) {   // the usual options, compiled in (k_rollout's FIXED)
             if ((a.flags & (F_AOS | F_TRACK | F_AUTO_RESET)) == (F_TRACK | F_AUTO_RESET)) {
-                hipLaunchKernelGGL((k_rollout<K, MODE, ST, true>), grid, block, lds_per_pair * g, h->stream, a, p, pc);
+                hipLaunchKernelGGL((k_rollout<K, MODE, ST, true>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
                 launched = true;
             }
         }
-        if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, p, pc);
+        if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
     } else {
-        if (h->time_limit > 0) {   // (one launch per chunk of a chunk-major call: launch_rollout_tl_km)
+        if (h->time_limit > 0) {   // (one launch per chunk of a chunk-major call: launch_rollout_km)
             // (ACT_BUFFER_CTRL comes here only with n_steps > 1, which no entry point asks for: its single steps run k_step_tl)
             if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
                 const int64_t count = a.slice_count ? (int64_t)a.slice_count : h->n;
                 const dim3 grid((unsigned)((count + block_size(h) - 1) / block_size(h)));
-                hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h));
+                hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST>), grid, dim3(block_size(h)), lds, h->stream, a, kp.p, kp.pc, tl_args(h));
             } else {
                 return rmav_fail(RMAV_ERR_INVALID, "no time-limited kernel for action mode %d", MODE);
             }
         } else {
-            hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid_for(h), dim3(block_size(h)), lds, h->stream, a, p, pc);
+            hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid_for(h), dim3(block_size(h)), lds, h->stream, a, kp.p, kp.pc);
         }
     }
     return check_rollout_launch(h, a);
-}
-
-// A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
-// variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
-template <int K, int MODE>
-int launch_rollout_tl_km(rmav_handle h, const RolloutArgs &a) {
-    if (h->chunk > 0) {
-        const int64_t per = h->chunk, T = a.n_steps;
-        constexpr int64_t NS = Dims<K>::NS, NA = Dims<K>::NA;
-        for (int64_t first = 0; first < h->n; first += per) {
-            // (the chunk-major pointer arithmetic of launch_rollout_km)
-            RolloutArgs b = a;
-            const int64_t c = first / per;
-            b.slice_first = (uint32_t)first;
-            b.slice_count = (uint32_t)((h->n - first < per) ? h->n - first : per);
-            b.pitch = per;
-            if (a.act_in) b.act_in = a.act_in + c * T * NA * per - first;
-            if (a.act_out) b.act_out = a.act_out + c * T * NA * per - first;
-            if (a.obs_out) b.obs_out = a.obs_out + c * T * NS * per - first;
-            if (a.rew_out) b.rew_out = a.rew_out + c * T * per - first;
-            if (a.done_out) b.done_out = a.done_out + c * T * per - first;
-            int rc;
-            switch (pick_store_policy(h, b, false)) {
-            case ST_WRITE_THROUGH: rc = launch_rollout_kms<K, MODE, ST_WRITE_THROUGH>(h, b); break;
-            case ST_STREAM: rc = launch_rollout_kms<K, MODE, ST_STREAM>(h, b); break;
-            default: rc = launch_rollout_kms<K, MODE, ST_DEFAULT>(h, b); break;
-            }
-            if (rc) return rc;
-        }
-        return RMAV_OK;
-    }
-    switch (pick_store_policy(h, a, false)) {
-    case ST_WRITE_THROUGH: return launch_rollout_kms<K, MODE, ST_WRITE_THROUGH>(h, a);
-    case ST_STREAM: return launch_rollout_kms<K, MODE, ST_STREAM>(h, a);
-    case ST_AOS_LDS: return launch_rollout_kms<K, MODE, ST_AOS_LDS>(h, a);
-    default: return launch_rollout_kms<K, MODE, ST_DEFAULT>(h, a);
-    }
 }
 
 // RMAV_TUNE_SPLIT = 0 | 1 overrides the rule.
@@ -293,58 +255,64 @@ bool use_split(rmav_handle h, const RolloutArgs &a, int action_mode, int *slices
     return forced == 1;   // one launch beyond the capacity: only when asked for
 }
 
+// The launch over the envs [first, first + per) of a call that is cut into several: a slice of the env range, and with chunk-major
+// trajectory arrays [n_chunks][T][dim][chunk] (rmav_rollout_chunked, per = chunk) the slice's chunk is a dense region of its own with
+// column pitch `chunk`; the kernels index columns by the env's index in the handle, so the base pointers are moved back by `first`
+// columns (a multiple of 64 elements: alignment is kept)
+template <int K> RolloutArgs slice_args(rmav_handle h, const RolloutArgs &a, int64_t first, int64_t per) {
+    RolloutArgs b = a;
+    b.slice_first = (uint32_t)first;
+    b.slice_count = (uint32_t)((h->n - first < per) ? h->n - first : per);
+    if (h->chunk > 0) {
+        const int64_t c = first / per, T = a.n_steps;
+        constexpr int64_t NS = Dims<K>::NS, NA = Dims<K>::NA;
+        b.pitch = per;
+        if (a.act_in) b.act_in = a.act_in + c * T * NA * per - first;
+        if (a.act_out) b.act_out = a.act_out + c * T * NA * per - first;
+        if (a.obs_out) b.obs_out = a.obs_out + c * T * NS * per - first;
+        if (a.rew_out) b.rew_out = a.rew_out + c * T * per - first;
+        if (a.done_out) b.done_out = a.done_out + c * T * per - first;
+    }
+    return b;
+}
+
 template <int K, int MODE>
 int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
-    if constexpr (K != REINMAV) {
-        if (h->time_limit > 0) return launch_rollout_tl_km<K, MODE>(h, a);
-    }
-    {
-        if constexpr ((MODE == ACT_RANDOM || MODE == ACT_CONTROLLER || MODE == ACT_BUFFER) && K != REINMAV) {
-            constexpr int SMODE = (MODE == ACT_RANDOM) ? ACT_RANDOM_SPLIT : (MODE == ACT_BUFFER) ? ACT_BUFFER_SPLIT : ACT_CONTROLLER_SPLIT;
-            int slices = 1;
-            if (use_split(h, a, MODE == ACT_CONTROLLER ? RMAV_ACT_CONTROLLER : MODE == ACT_BUFFER ? RMAV_ACT_BUFFER : RMAV_ACT_RANDOM, &slices, MODE == ACT_RANDOM)) {
-                // balanced slices, each a multiple of 64 envs
-                const int64_t per = h->chunk > 0 ? h->chunk : slices > 1 ? (((h->n + slices - 1) / slices + 63) / 64) * 64 : h->n;
-                RolloutArgs ap = a;
-                if (h->chunk > 0) ap.pitch = per;   // chunk-major columns are `chunk` (a multiple of 64) apart whatever N is
-                const int st = pick_store_policy(h, ap, true);
-                for (int64_t first = 0; first < h->n; first += per) {
-                    RolloutArgs b = a;
-                    if (slices > 1 || h->chunk > 0) {
-                        b.slice_first = (uint32_t)first;
-                        b.slice_count = (uint32_t)((h->n - first < per) ? h->n - first : per);
-                    }
-                    if (h->chunk > 0) {
-                        // chunk-major trajectory arrays [n_chunks][T][dim][chunk]: this launch's chunk is a dense region of its own with
-                        // column pitch `chunk`; the kernels index columns by the env's index in the handle, so the base pointers are moved
-                        // back by `first` columns (a multiple of 64 elements: alignment is kept)
-                        const int64_t c = first / per, T = a.n_steps;
-                        constexpr int64_t NS = Dims<K>::NS, NA = Dims<K>::NA;
-                        b.pitch = per;
-                        if (a.act_in) b.act_in = a.act_in + c * T * NA * per - first;
-                        if (a.act_out) b.act_out = a.act_out + c * T * NA * per - first;
-                        if (a.obs_out) b.obs_out = a.obs_out + c * T * NS * per - first;
-                        if (a.rew_out) b.rew_out = a.rew_out + c * T * per - first;
-                        if (a.done_out) b.done_out = a.done_out + c * T * per - first;
-                    }
-                    int rc;
-                    switch (st) {
-                    case ST_STREAM: rc = launch_rollout_kms<K, SMODE, ST_STREAM>(h, b); break;
-                    case ST_DEFAULT: rc = launch_rollout_kms<K, SMODE, ST_DEFAULT>(h, b); break;
-                    default: rc = launch_rollout_kms<K, SMODE, ST_WRITE_THROUGH>(h, b); break;
-                    }
-                    if (rc) return rc;
-                }
-                return RMAV_OK;
+    constexpr bool has_split = (MODE == ACT_RANDOM || MODE == ACT_CONTROLLER || MODE == ACT_BUFFER) && K != REINMAV;
+    // A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
+    // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
+    if (K != REINMAV && h->time_limit > 0) {
+        if (h->chunk > 0) {
+            for (int64_t first = 0; first < h->n; first += h->chunk) {
+                const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
+                // (chunk-major is feature-major: ST_AOS_LDS does not come up)
+                if (int rc = dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(
+                        pick_store_policy(h, b, false), [&](auto st) { return launch_rollout_kms<K, MODE, decltype(st)::value>(h, b); }))
+                    return rc;
             }
+            return RMAV_OK;
         }
-        switch (pick_store_policy(h, a, false)) {
-        case ST_WRITE_THROUGH: return launch_rollout_kms<K, MODE, ST_WRITE_THROUGH>(h, a);
-        case ST_STREAM: return launch_rollout_kms<K, MODE, ST_STREAM>(h, a);
-        case ST_AOS_LDS: return launch_rollout_kms<K, MODE, ST_AOS_LDS>(h, a);
-        default: return launch_rollout_kms<K, MODE, ST_DEFAULT>(h, a);
+    } else if constexpr (has_split) {
+        constexpr int SMODE = (MODE == ACT_RANDOM) ? ACT_RANDOM_SPLIT : (MODE == ACT_BUFFER) ? ACT_BUFFER_SPLIT : ACT_CONTROLLER_SPLIT;
+        int slices = 1;
+        if (use_split(h, a, MODE == ACT_CONTROLLER ? RMAV_ACT_CONTROLLER : MODE == ACT_BUFFER ? RMAV_ACT_BUFFER : RMAV_ACT_RANDOM, &slices, MODE == ACT_RANDOM)) {
+            // balanced slices, each a multiple of 64 envs
+            const int64_t per = h->chunk > 0 ? h->chunk : slices > 1 ? (((h->n + slices - 1) / slices + 63) / 64) * 64 : h->n;
+            RolloutArgs ap = a;
+            if (h->chunk > 0) ap.pitch = per;   // chunk-major columns are `chunk` (a multiple of 64) apart whatever N is
+            const int st = pick_store_policy(h, ap, true);
+            for (int64_t first = 0; first < h->n; first += per) {
+                const RolloutArgs b = (slices > 1 || h->chunk > 0) ? slice_args<K>(h, a, first, per) : a;
+                if (int rc = dispatch_store<ST_WRITE_THROUGH, ST_STREAM, ST_DEFAULT>(
+                        st, [&](auto s) { return launch_rollout_kms<K, SMODE, decltype(s)::value>(h, b); }))
+                    return rc;
+            }
+            return RMAV_OK;
         }
     }
+    // one launch of the one-wavefront kernel: every store policy
+    return dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM, ST_AOS_LDS>(
+        pick_store_policy(h, a, false), [&](auto st) { return launch_rollout_kms<K, MODE, decltype(st)::value>(h, a); });
 }
 
 template <int K> int launch_rollout_k(rmav_handle h, int mode, const RolloutArgs &a) {
@@ -375,37 +343,38 @@ inline int step_store(rmav_handle h) {
     return v >= 0 ? v : ((h->n >= 196608 && h->n < 786432) ? (int)ST_STREAM : (int)ST_DEFAULT);
 }
 
+// k_step / k_step_tl / k_step_final at `bs` threads per workgroup.  The leading scalars are what the kernel's first loads need:
+// preloaded into scalar registers, see StepHot in rmav_kernels.hpp; `tail` is what the kernel takes behind k_step's arguments.
+template <int K, typename Kernel, typename... Tail>
+void launch_step_hot(rmav_handle h, const RolloutArgs &a, const KindParams<K> &kp, int bs, Kernel kernel, const Tail &...tail) {
+    const dim3 grid((unsigned)((h->n + bs - 1) / bs));
+    hipLaunchKernelGGL(kernel, grid, dim3(bs), 0, h->stream, a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a, kp.p, kp.pc, tail...);
+}
+
 // n_steps == 1 with caller actions: the latency-cut single-step kernel
 template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctrl) {
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
-    const typename Env<K>::P p = derive_env<K>(h->params);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
+    const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    const bool lazy = step_lazy(h);
-    const dim3 grid((unsigned)((h->n + bs - 1) / bs));
-    const bool big = h->n >= 786432;   // no argument preloading for the big batches (k_step_big in rmav_kernels.hpp says why)
-    // (the leading scalars are what the kernel's first loads need: preloaded into scalar registers, see StepHot in rmav_kernels.hpp)
-#define RMAV_STEP_ARGS a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a, p, pc
-#define RMAV_STEP(LAZY, ST)                                                                                           \
-    do {                                                                                                              \
-        if (big) hipLaunchKernelGGL((k_step_big<K, LAZY, ST>), grid, dim3(bs), 0, h->stream, a, p, pc);               \
-        else hipLaunchKernelGGL((k_step<K, false, LAZY, ST>), grid, dim3(bs), 0, h->stream, RMAV_STEP_ARGS);          \
-    } while (0)
     if (h->time_limit > 0) {   // every batch size: the eager record load, k_step's preloaded arguments (k_step_tl)
-        const dim3 grid_tl((unsigned)((h->n + bs - 1) / bs));
-        if (ctrl) hipLaunchKernelGGL((k_step_tl<K, true>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
-        else if (st == ST_STREAM) hipLaunchKernelGGL((k_step_tl<K, false, ST_STREAM>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
-        else if (st == ST_WRITE_THROUGH) hipLaunchKernelGGL((k_step_tl<K, false, ST_WRITE_THROUGH>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
-        else hipLaunchKernelGGL((k_step_tl<K, false>), grid_tl, dim3(bs), 0, h->stream, RMAV_STEP_ARGS, tl_args(h));
-    } else if (ctrl) hipLaunchKernelGGL((k_step<K, true>), grid, dim3(bs), 0, h->stream, RMAV_STEP_ARGS);
-    else if (lazy && st == ST_STREAM) RMAV_STEP(true, ST_STREAM);
-    else if (lazy && st == ST_WRITE_THROUGH) RMAV_STEP(true, ST_WRITE_THROUGH);
-    else if (lazy) RMAV_STEP(true, ST_DEFAULT);
-    else if (st == ST_WRITE_THROUGH) RMAV_STEP(false, ST_WRITE_THROUGH);
-    else if (st == ST_STREAM) RMAV_STEP(false, ST_STREAM);
-    else RMAV_STEP(false, ST_DEFAULT);
-#undef RMAV_STEP
-#undef RMAV_STEP_ARGS
+        const TimeLimitArgs tl = tl_args(h);
+        if (ctrl) launch_step_hot(h, a, kp, bs, k_step_tl<K, true>, tl);
+        else dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(st, [&](auto s) { launch_step_hot(h, a, kp, bs, k_step_tl<K, false, decltype(s)::value>, tl); });
+    } else if (ctrl) {
+        launch_step_hot(h, a, kp, bs, k_step<K, true>);
+    } else {
+        const bool big = h->n >= 786432;   // no argument preloading for the big batches (k_step_big in rmav_kernels.hpp says why)
+        dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(st, [&](auto s) {
+            constexpr int ST = decltype(s)::value;
+            auto launch = [&](auto lazy) {
+                constexpr bool LAZY = decltype(lazy)::value;
+                if (big) hipLaunchKernelGGL((k_step_big<K, LAZY, ST>), dim3((unsigned)((h->n + bs - 1) / bs)), dim3(bs), 0, h->stream, a, kp.p, kp.pc);
+                else launch_step_hot(h, a, kp, bs, k_step<K, false, LAZY, ST>);
+            };
+            if (step_lazy(h)) launch(std::true_type{});
+            else launch(std::false_type{});
+        });
+    }
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
 }
@@ -413,54 +382,25 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
 // rmav_step_final: k_step_final<K, TL, ST> at k_step_tl's launch shape (eager record load and preloaded leading arguments for every batch size)
 template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, const FinalArgs &fa) {
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;
-    const typename Env<K>::P p = derive_env<K>(h->params);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
-    const int st = step_store(h), bs = step_block(h);
-    const dim3 grid((unsigned)((h->n + bs - 1) / bs));
+    const KindParams<K> kp = kind_params<K>(h);
+    const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-#define RMAV_STEP_FINAL(TL, ST) \
-    hipLaunchKernelGGL((k_step_final<K, TL, ST>), grid, dim3(bs), 0, h->stream, a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a, p, pc, tl, fa)
-    if (h->time_limit > 0) {
-        if (st == ST_STREAM) RMAV_STEP_FINAL(true, ST_STREAM);
-        else if (st == ST_WRITE_THROUGH) RMAV_STEP_FINAL(true, ST_WRITE_THROUGH);
-        else RMAV_STEP_FINAL(true, ST_DEFAULT);
-    } else {
-        if (st == ST_STREAM) RMAV_STEP_FINAL(false, ST_STREAM);
-        else if (st == ST_WRITE_THROUGH) RMAV_STEP_FINAL(false, ST_WRITE_THROUGH);
-        else RMAV_STEP_FINAL(false, ST_DEFAULT);
-    }
-#undef RMAV_STEP_FINAL
+    dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(step_store(h), [&](auto s) {
+        constexpr int ST = decltype(s)::value;
+        if (h->time_limit > 0) launch_step_hot(h, a, kp, bs, k_step_final<K, true, ST>, tl, fa);
+        else launch_step_hot(h, a, kp, bs, k_step_final<K, false, ST>, tl, fa);
+    });
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
 }
 int launch_step_final(rmav_handle h, const RolloutArgs &a, const FinalArgs &fa) {
-    switch (h->kind) {
-    case RMAV_QUAD2D: return launch_step_final_k<QUAD2D>(h, a, fa);
-    case RMAV_QUAD2D_SL: return launch_step_final_k<QUAD2D_SL>(h, a, fa);
-    case RMAV_QUAD3D: return launch_step_final_k<QUAD3D>(h, a, fa);
-    case RMAV_QUAD3D_SL: return launch_step_final_k<QUAD3D_SL>(h, a, fa);
-    }
-    return rmav_fail(RMAV_ERR_INVALID, "bad kind");
+    return dispatch_kind<QUAD_KINDS>(h->kind, [&](auto k) { return launch_step_final_k<decltype(k)::value>(h, a, fa); });
 }
 
 int launch_rollout(rmav_handle h, int mode, const RolloutArgs &a) {
-    if (a.n_steps == 1 && (mode == RMAV_ACT_BUFFER || mode == ACT_BUFFER_CTRL) && h->kind != RMAV_REINMAV) {
-        const bool ctrl = mode == ACT_BUFFER_CTRL;
-        switch (h->kind) {
-        case RMAV_QUAD2D: return launch_step_k<QUAD2D>(h, a, ctrl);
-        case RMAV_QUAD2D_SL: return launch_step_k<QUAD2D_SL>(h, a, ctrl);
-        case RMAV_QUAD3D: return launch_step_k<QUAD3D>(h, a, ctrl);
-        case RMAV_QUAD3D_SL: return launch_step_k<QUAD3D_SL>(h, a, ctrl);
-        }
-    }
-    switch (h->kind) {
-    case RMAV_QUAD2D: return launch_rollout_k<QUAD2D>(h, mode, a);
-    case RMAV_QUAD2D_SL: return launch_rollout_k<QUAD2D_SL>(h, mode, a);
-    case RMAV_QUAD3D: return launch_rollout_k<QUAD3D>(h, mode, a);
-    case RMAV_QUAD3D_SL: return launch_rollout_k<QUAD3D_SL>(h, mode, a);
-    case RMAV_REINMAV: return launch_rollout_k<REINMAV>(h, mode, a);
-    }
-    return rmav_fail(RMAV_ERR_INVALID, "bad kind");
+    if (a.n_steps == 1 && (mode == RMAV_ACT_BUFFER || mode == ACT_BUFFER_CTRL) && h->kind != RMAV_REINMAV)
+        return dispatch_kind<QUAD_KINDS>(h->kind, [&](auto k) { return launch_step_k<decltype(k)::value>(h, a, mode == ACT_BUFFER_CTRL); });
+    return dispatch_kind<ALL_KINDS>(h->kind, [&](auto k) { return launch_rollout_k<decltype(k)::value>(h, mode, a); });
 }
 
 RolloutArgs base_args(rmav_handle h) {
@@ -487,19 +427,12 @@ RolloutArgs base_args(rmav_handle h) {
 
 int launch_reset(rmav_handle h, float *obs_dev, int layout) {
     const uint32_t fl = (h->flags & F_TRACK) | (layout == RMAV_AOS ? F_AOS : 0u);
-#define RMAV_RESET_CASE(KIND)                                                                      \
-    hipLaunchKernelGGL((k_reset<KIND>), grid_for(h), dim3(block_size(h)), 0, h->stream, h->state,      \
-                       h->n, h->rec, h->ep_ret, (uint32_t)h->t, obs_dev, h->seed, h->env_base, fl)
-    switch (h->kind) {
-    case RMAV_QUAD2D: RMAV_RESET_CASE(QUAD2D); break;
-    case RMAV_QUAD2D_SL: RMAV_RESET_CASE(QUAD2D_SL); break;
-    case RMAV_QUAD3D: RMAV_RESET_CASE(QUAD3D); break;
-    case RMAV_QUAD3D_SL: RMAV_RESET_CASE(QUAD3D_SL); break;
-    case RMAV_REINMAV: RMAV_RESET_CASE(REINMAV); break;
-    }
-#undef RMAV_RESET_CASE
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
+    return dispatch_kind<ALL_KINDS>(h->kind, [&](auto k) {
+        hipLaunchKernelGGL((k_reset<decltype(k)::value>), grid_for(h), dim3(block_size(h)), 0, h->stream, h->state, h->n, h->rec, h->ep_ret,
+                           (uint32_t)h->t, obs_dev, h->seed, h->env_base, fl);
+        HIP_TRY(hipGetLastError());
+        return (int)RMAV_OK;
+    });
 }
 
 // The running episode of every env starts at the handle's clock: ep_start = clock (what k_reset does when the handle tracks episodes).
@@ -532,23 +465,17 @@ int ensure_last_trunc(rmav_handle h) {
 
 int launch_control(rmav_handle h, float *act_dev, int layout) {
     const uint32_t fl = (layout == RMAV_AOS ? F_AOS : 0u);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
-#define RMAV_CTRL_CASE(KIND)                                                                       \
-    hipLaunchKernelGGL((k_control<KIND>), grid_for(h), dim3(block_size(h)), 0, h->stream, h->state,    \
-                       h->n, act_dev, fl, pc, h->pe[0], h->pe[1], h->pe[2])
-    switch (h->kind) {
-    case RMAV_QUAD2D: RMAV_CTRL_CASE(QUAD2D); break;
-    case RMAV_QUAD2D_SL: RMAV_CTRL_CASE(QUAD2D_SL); break;
-    case RMAV_QUAD3D: RMAV_CTRL_CASE(QUAD3D); break;
-    case RMAV_QUAD3D_SL: RMAV_CTRL_CASE(QUAD3D_SL); break;
-    case RMAV_REINMAV:
-        hipLaunchKernelGGL(k_control_reinmav, grid_for(h), dim3(block_size(h)), 0, h->stream, h->state,
-                           h->env_time, h->n, act_dev, fl, derive_reinmav(h->params));
-        break;
-    }
-#undef RMAV_CTRL_CASE
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
+    return dispatch_kind<ALL_KINDS>(h->kind, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        if constexpr (K == REINMAV)
+            hipLaunchKernelGGL(k_control_reinmav, grid_for(h), dim3(block_size(h)), 0, h->stream, h->state, h->env_time, h->n, act_dev, fl,
+                               derive_reinmav(h->params));
+        else
+            hipLaunchKernelGGL((k_control<K>), grid_for(h), dim3(block_size(h)), 0, h->stream, h->state, h->n, act_dev, fl,
+                               derive<double>(h->params, K == QUAD2D || K == QUAD2D_SL), h->pe[0], h->pe[1], h->pe[2]);
+        HIP_TRY(hipGetLastError());
+        return (int)RMAV_OK;
+    });
 }
 
 int check_mem_layout(int mem, int layout) {
@@ -584,6 +511,21 @@ template <typename T> int copy_in(rmav_handle h, T *dev, const T *in, size_t cou
     return RMAV_OK;
 }
 
+// A kernel writes `bytes` to a device destination and the caller may have passed a host pointer: launch(dst) runs on the caller's device
+// pointer, on the pinned block (zero-copy: up to kPinnedMax) or on device scratch that is then copied out.
+template <typename F> int write_via_host(rmav_handle h, void *out, size_t bytes, int mem, F &&launch) {
+    if (mem == RMAV_DEVICE || !out) return launch(out);
+    if (bytes <= kPinnedMax && ensure_pinned(h, bytes) == RMAV_OK) {
+        if (int rc = launch(h->pinned_dev)) return rc;
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        memcpy(out, h->pinned, bytes);
+        return RMAV_OK;
+    }
+    if (int rc = ensure_scratch(h, bytes)) return rc;
+    if (int rc = launch(h->scratch)) return rc;
+    return copy_out(h, (const char *)h->scratch, (char *)out, bytes, RMAV_HOST);
+}
+
 // One 32-bit field of the per-env records (EnvRec: 0 sbd, 1 reset_cnt, 2 ep_start, 3 last_len) as a dense array: the state accessors
 // of the ABI gather / scatter it with one small kernel (host pointers: through device scratch)
 int rec_field_get(rmav_handle h, int field, uint32_t *out, int mem) {
@@ -609,6 +551,20 @@ int rec_field_set(rmav_handle h, int field, const uint32_t *in, int mem) {
     }
     hipLaunchKernelGGL(k_rec_set, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->rec, src, field, (int64_t)n);
     HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// The handle's stream: the caller's, or one of its own when hip_stream is NULL.
+int adopt_stream(rmav_handle h, void *hip_stream) {
+    h->own_stream = false;
+    if (hip_stream) {
+        // (void*)1 names the legacy default stream, whose real handle is 0: use that (some runtime entry points -
+        // hipEventRecord - do not accept the hipStreamLegacy constant)
+        h->stream = (hip_stream == (void *)1) ? nullptr : (hipStream_t)hip_stream;
+        return RMAV_OK;
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->own_stream = true;
     return RMAV_OK;
 }
 
@@ -742,18 +698,10 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
     h->flags = flags;
     h->params = pr;
     for (int i = 0; i < RMAV_TUNE_COUNT; ++i) h->tune[i] = -1;
-    if (hip_stream) {
-        // (void*)1 names the legacy default stream, whose real handle is 0: use that (some runtime entry points -
-        // hipEventRecord - do not accept the hipStreamLegacy constant)
-        h->stream = (hip_stream == (void *)1) ? nullptr : (hipStream_t)hip_stream;
-        h->own_stream = false;
-    } else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            (void)hipGetLastError();
-            free_all(h);
-            return rmav_fail(RMAV_ERR_HIP, "hipStreamCreate failed");
-        }
-        h->own_stream = true;
+    if (adopt_stream(h, hip_stream)) {
+        (void)hipGetLastError();
+        free_all(h);
+        return rmav_fail(RMAV_ERR_HIP, "hipStreamCreate failed");
     }
     const size_t n = (size_t)n_envs;
     const int nS = kStateDim[kind];
@@ -873,19 +821,8 @@ int rmav_set_params(rmav_handle h, const rmav_params *in) {
 int rmav_set_stream(rmav_handle h, void *hip_stream) {
     CHECK_HANDLE(h);
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->own_stream) {
-        (void)hipStreamDestroy(h->stream);
-        h->own_stream = false;
-    }
-    if (hip_stream) {
-        // (void*)1 names the legacy default stream, whose real handle is 0: use that (some runtime entry points -
-        // hipEventRecord - do not accept the hipStreamLegacy constant)
-        h->stream = (hip_stream == (void *)1) ? nullptr : (hipStream_t)hip_stream;
-    } else {
-        HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return RMAV_OK;
+    if (h->own_stream) (void)hipStreamDestroy(h->stream);
+    return adopt_stream(h, hip_stream);
 }
 
 int rmav_set_env_param(rmav_handle h, int which, const float *values, int mem) {
@@ -936,17 +873,8 @@ int rmav_sync(rmav_handle h) {
 int rmav_reset(rmav_handle h, float *obs_out, int mem, int layout) {
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
-    const size_t nobs = (size_t)h->n * kStateDim[h->kind];
-    if (mem == RMAV_DEVICE || !obs_out) return launch_reset_tl(h, obs_out, layout);
-    if (nobs * sizeof(float) <= kPinnedMax && ensure_pinned(h, nobs * sizeof(float)) == RMAV_OK) {   // zero-copy
-        if (int rc = launch_reset_tl(h, (float *)h->pinned_dev, layout)) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        memcpy(obs_out, h->pinned, nobs * sizeof(float));
-        return RMAV_OK;
-    }
-    if (int rc = ensure_scratch(h, nobs * sizeof(float))) return rc;
-    if (int rc = launch_reset_tl(h, (float *)h->scratch, layout)) return rc;
-    return copy_out(h, (const float *)h->scratch, obs_out, nobs, RMAV_HOST);
+    return write_via_host(h, obs_out, (size_t)h->n * kStateDim[h->kind] * sizeof(float), mem,
+                          [&](void *dst) { return launch_reset_tl(h, (float *)dst, layout); });
 }
 
 // rmav_rollout / rmav_step / rmav_step_control / rmav_control_step.  ctrl_out (nullable): control() of the state the
@@ -974,25 +902,32 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     const size_t b_fin = nS * n * sizeof(float), b_trunc = n;
     const bool want_aout = actions_out && action_mode != RMAV_ACT_BUFFER;
 
-    const float *d_act_in = actions_in;
-    float *d_act_out = actions_out, *d_obs = obs_out, *d_rew = rew_out, *d_ctrl = ctrl_out;
-    uint8_t *d_done = done_out;
-    float *d_fin = final_out;
-    uint8_t *d_trunc = trunc_out;
+    // The arrays of the call: what the kernels get (dev: the caller's pointers with RMAV_DEVICE) and, with RMAV_HOST, how each array that
+    // is present is staged - its place in the staging block, copied in before the launches and / or out behind them.
+    enum { S_ACT_IN, S_ACT_OUT, S_OBS, S_REW, S_DONE, S_CTRL, S_FINAL, S_TRUNC, S_COUNT };
+    struct Staged {
+        void *host;   // nullptr: not staged
+        size_t bytes;
+        bool in, out;
+        size_t off;
+    } stg[S_COUNT] = {{action_mode == RMAV_ACT_BUFFER ? const_cast<float *>(actions_in) : nullptr, b_act, true, false, 0},
+                      {want_aout ? actions_out : nullptr, b_act, false, true, 0},
+                      {obs_out, b_obs, false, true, 0},
+                      {rew_out, b_rew, false, true, 0},
+                      {done_out, b_done, false, true, 0},
+                      {ctrl_out, b_ctrl, false, true, 0},
+                      {final_out, b_fin, true, true, 0},
+                      {trunc_out, b_trunc, false, true, 0}};
+    void *dev[S_COUNT] = {const_cast<float *>(actions_in), actions_out, obs_out, rew_out, done_out, ctrl_out, final_out, trunc_out};
     bool pinned = false;
     char *hbase = nullptr;   // host view of the staging block (pinned path only)
-    size_t o_ain = 0, o_aout = 0, o_obs = 0, o_rew = 0, o_done = 0, o_ctrl = 0, o_fin = 0, o_trunc = 0;
     if (mem == RMAV_HOST) {
-        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
         size_t off = 0;
-        if (action_mode == RMAV_ACT_BUFFER) { o_ain = off; off += up(b_act); }
-        if (want_aout) { o_aout = off; off += up(b_act); }
-        if (obs_out) { o_obs = off; off += up(b_obs); }
-        if (rew_out) { o_rew = off; off += up(b_rew); }
-        if (done_out) { o_done = off; off += up(b_done); }
-        if (ctrl_out) { o_ctrl = off; off += up(b_ctrl); }
-        if (final_out) { o_fin = off; off += up(b_fin); }
-        if (trunc_out) { o_trunc = off; off += up(b_trunc); }
+        for (Staged &g : stg)
+            if (g.host) {
+                g.off = off;
+                off += (g.bytes + 255) & ~(size_t)255;
+            }
         if (!off) off = 256;
         char *base;
         if (off <= kPinnedMax && ensure_pinned(h, off) == RMAV_OK) {
@@ -1000,24 +935,20 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
             pinned = true;
             hbase = (char *)h->pinned;
             base = (char *)h->pinned_dev;
-            if (action_mode == RMAV_ACT_BUFFER) memcpy(hbase + o_ain, actions_in, b_act);
-            if (final_out) memcpy(hbase + o_fin, final_out, b_fin);
+            for (const Staged &g : stg)
+                if (g.host && g.in) memcpy(hbase + g.off, g.host, g.bytes);
         } else {   // bulk: stage through device scratch
             if (int rc = ensure_scratch(h, off)) return rc;
             base = (char *)h->scratch;
-            if (action_mode == RMAV_ACT_BUFFER)
-                HIP_TRY(hipMemcpyAsync(base + o_ain, actions_in, b_act, hipMemcpyHostToDevice, h->stream));
-            if (final_out) HIP_TRY(hipMemcpyAsync(base + o_fin, final_out, b_fin, hipMemcpyHostToDevice, h->stream));
+            for (const Staged &g : stg)
+                if (g.host && g.in) HIP_TRY(hipMemcpyAsync(base + g.off, g.host, g.bytes, hipMemcpyHostToDevice, h->stream));
         }
-        d_act_in = action_mode == RMAV_ACT_BUFFER ? (const float *)(base + o_ain) : nullptr;
-        d_act_out = want_aout ? (float *)(base + o_aout) : nullptr;
-        d_obs = obs_out ? (float *)(base + o_obs) : nullptr;
-        d_rew = rew_out ? (float *)(base + o_rew) : nullptr;
-        d_done = done_out ? (uint8_t *)(base + o_done) : nullptr;
-        d_ctrl = ctrl_out ? (float *)(base + o_ctrl) : nullptr;
-        d_fin = final_out ? (float *)(base + o_fin) : nullptr;
-        d_trunc = trunc_out ? (uint8_t *)(base + o_trunc) : nullptr;
+        for (int i = 0; i < S_COUNT; ++i) dev[i] = stg[i].host ? base + stg[i].off : nullptr;
     }
+    const float *const d_act_in = (const float *)dev[S_ACT_IN];
+    float *const d_act_out = (float *)dev[S_ACT_OUT], *const d_obs = (float *)dev[S_OBS], *const d_rew = (float *)dev[S_REW];
+    uint8_t *const d_done = (uint8_t *)dev[S_DONE];
+    float *const d_ctrl = (float *)dev[S_CTRL];
 
     RolloutArgs a = base_args(h);
     if (layout == RMAV_AOS) a.flags |= F_AOS;
@@ -1051,7 +982,7 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
         a.rew_out = d_rew;
         a.done_out = d_done;
         if (want_final) {
-            if (int rc = launch_step_final(h, a, FinalArgs{d_fin, d_trunc})) return rc;
+            if (int rc = launch_step_final(h, a, FinalArgs{(float *)dev[S_FINAL], (uint8_t *)dev[S_TRUNC]})) return rc;
         } else if (int rc = launch_rollout(h, kmode, a)) return rc;
     } else {
         for (size_t k = 0; k < T; ++k) {
@@ -1084,21 +1015,11 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
                 __atomic_thread_fence(__ATOMIC_ACQUIRE);
             }
             if (!seen) HIP_TRY(hipStreamSynchronize(h->stream));
-            if (want_aout) memcpy(actions_out, hbase + o_aout, b_act);
-            if (obs_out) memcpy(obs_out, hbase + o_obs, b_obs);
-            if (rew_out) memcpy(rew_out, hbase + o_rew, b_rew);
-            if (done_out) memcpy(done_out, hbase + o_done, b_done);
-            if (ctrl_out) memcpy(ctrl_out, hbase + o_ctrl, b_ctrl);
-            if (final_out) memcpy(final_out, hbase + o_fin, b_fin);
-            if (trunc_out) memcpy(trunc_out, hbase + o_trunc, b_trunc);
+            for (const Staged &g : stg)
+                if (g.host && g.out) memcpy(g.host, hbase + g.off, g.bytes);
         } else {
-            if (want_aout) HIP_TRY(hipMemcpyAsync(actions_out, d_act_out, b_act, hipMemcpyDeviceToHost, h->stream));
-            if (obs_out) HIP_TRY(hipMemcpyAsync(obs_out, d_obs, b_obs, hipMemcpyDeviceToHost, h->stream));
-            if (rew_out) HIP_TRY(hipMemcpyAsync(rew_out, d_rew, b_rew, hipMemcpyDeviceToHost, h->stream));
-            if (done_out) HIP_TRY(hipMemcpyAsync(done_out, d_done, b_done, hipMemcpyDeviceToHost, h->stream));
-            if (ctrl_out) HIP_TRY(hipMemcpyAsync(ctrl_out, d_ctrl, b_ctrl, hipMemcpyDeviceToHost, h->stream));
-            if (final_out) HIP_TRY(hipMemcpyAsync(final_out, d_fin, b_fin, hipMemcpyDeviceToHost, h->stream));
-            if (trunc_out) HIP_TRY(hipMemcpyAsync(trunc_out, d_trunc, b_trunc, hipMemcpyDeviceToHost, h->stream));
+            for (int i = 0; i < S_COUNT; ++i)
+                if (stg[i].host && stg[i].out) HIP_TRY(hipMemcpyAsync(stg[i].host, dev[i], stg[i].bytes, hipMemcpyDeviceToHost, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
         }
         if (actions_out && action_mode == RMAV_ACT_BUFFER && actions_out != actions_in)
@@ -1172,14 +1093,7 @@ int rmav_control_step(rmav_handle h, float *actions_out, float *obs_out, float *
 }
 
 int64_t rmav_policy_weight_count(int kind) {
-    switch (kind) {
-    case RMAV_QUAD2D: return PolicyLayout<5>::TOTAL;
-    case RMAV_QUAD2D_SL: return PolicyLayout<9>::TOTAL;
-    case RMAV_QUAD3D: return PolicyLayout<10>::TOTAL;
-    case RMAV_QUAD3D_SL: return PolicyLayout<16>::TOTAL;
-    case RMAV_REINMAV: return PolicyLayout<13>::TOTAL;
-    }
-    return rmav_fail(RMAV_ERR_INVALID, "bad kind %d", kind);
+    return dispatch_kind<ALL_KINDS>(kind, [](auto k) { return (int64_t)PolicyLayout<Dims<decltype(k)::value>::NS>::TOTAL; });
 }
 
 int64_t rmav_policy_weight_count_bf16(void) { return MfmaLayout::TOTAL; }
@@ -1226,20 +1140,23 @@ int rmav_pack_policy_f16(rmav_handle h, int n_params, const float *const *params
     return pack_policy_impl(h, n_params, params, sizes, idx_lo, idx_hi, n_out, weights_out, true);
 }
 
-int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out,
-                        float *obs_out, float *rew_out, uint8_t *done_out, float *logp_out,
-                        float *value_out, int precision) {
-    CHECK_HANDLE(h);
-    if (precision < RMAV_POLICY_FP32 || precision > RMAV_POLICY_F16_SHARED)
-        return rmav_fail(RMAV_ERR_INVALID, "precision must be one of RMAV_POLICY_FP32 ... RMAV_POLICY_F16_SHARED (rmav_policy_precision)");
+// ---- rmav_rollout_policy / _boot / _norm: the checks all three make, in the order they make them, and the launch ------------------
+// the actors with time-limited (and *_boot, *_nrm) kernels; the fp32 vector-ALU and bf16 actors have none
+static bool limit_capable(int precision) {
+    return precision == RMAV_POLICY_FP32_MFMA || precision == RMAV_POLICY_F16_MFMA || precision == RMAV_POLICY_F16_SHARED;
+}
+// boot_out: checked (and named) only when the entry point requires it
+static int check_policy_args(int32_t n_steps, const float *weights, const float *logp_out, const float *value_out, bool need_boot, const float *boot_out) {
     if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!weights || !logp_out || !value_out)
-        return rmav_fail(RMAV_ERR_INVALID, "weights, logp_out and value_out are required (device pointers)");
-    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0)
-        return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
-    if (h->time_limit > 0 && precision != RMAV_POLICY_FP32_MFMA && precision != RMAV_POLICY_F16_MFMA && precision != RMAV_POLICY_F16_SHARED)
-        return rmav_fail(RMAV_ERR_INVALID, "a time-limited handle runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
-                                           "(the fp32 vector-ALU and bf16 actors have no time-limited kernel)");
+    if (!weights || !logp_out || !value_out || (need_boot && !boot_out))
+        return rmav_fail(RMAV_ERR_INVALID, need_boot ? "weights, logp_out, value_out and boot_out are required (device pointers)"
+                                                     : "weights, logp_out and value_out are required (device pointers)");
+    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
+    return RMAV_OK;
+}
+// one fused launch over all envs (it may carry an armed exchange's snapshot), then the step counter
+static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out, float *rew_out,
+                              uint8_t *done_out, float *logp_out, float *value_out, int precision, const BootArgs *bt, const NormArgs *nm) {
     RolloutArgs a = base_args(h);
     a.n_steps = n_steps;
     a.act_out = actions_out;
@@ -1255,9 +1172,22 @@ int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, fl
                       : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
                                                            : (int)ACT_POLICY_F32M;
     h->xchg.allow = true;
-    if (int rc = rmav_launch_policy_rollout(h, kmode, a)) return rc;
+    if (int rc = rmav_launch_policy_rollout(h, kmode, a, bt, nm)) return rc;
     h->t += (uint64_t)n_steps;
     return RMAV_OK;
+}
+
+int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out,
+                        float *obs_out, float *rew_out, uint8_t *done_out, float *logp_out,
+                        float *value_out, int precision) {
+    CHECK_HANDLE(h);
+    if (precision < RMAV_POLICY_FP32 || precision > RMAV_POLICY_F16_SHARED)
+        return rmav_fail(RMAV_ERR_INVALID, "precision must be one of RMAV_POLICY_FP32 ... RMAV_POLICY_F16_SHARED (rmav_policy_precision)");
+    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
+    if (h->time_limit > 0 && !limit_capable(precision))
+        return rmav_fail(RMAV_ERR_INVALID, "a time-limited handle runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
+                                           "(the fp32 vector-ALU and bf16 actors have no time-limited kernel)");
+    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, nullptr, nullptr);
 }
 
 int rmav_step(rmav_handle h, const float *actions, float *obs_out, float *rew_out,
@@ -1284,47 +1214,20 @@ int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weight
         return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap");
     if (h->time_limit <= 0)
         return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot needs an episode time limit on the handle (rmav_set_time_limit)");
-    if (precision != RMAV_POLICY_FP32_MFMA && precision != RMAV_POLICY_F16_MFMA && precision != RMAV_POLICY_F16_SHARED)
+    if (!limit_capable(precision))
         return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
                                            "(the fp32 vector-ALU and bf16 actors have no time-limited kernel), got precision %d", precision);
-    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!weights || !logp_out || !value_out || !boot_out)
-        return rmav_fail(RMAV_ERR_INVALID, "weights, logp_out, value_out and boot_out are required (device pointers)");
-    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0)
-        return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
-    RolloutArgs a = base_args(h);
-    a.n_steps = n_steps;
-    a.act_out = actions_out;
-    a.obs_out = obs_out;
-    a.rew_out = rew_out;
-    a.done_out = done_out;
-    a.policy_w = weights;
-    a.logp_out = logp_out;
-    a.val_out = value_out;
-    const int kmode = precision == RMAV_POLICY_F16_MFMA ? (int)ACT_POLICY_F16 : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
-                                                                                                                : (int)ACT_POLICY_F32M;
+    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, true, boot_out)) return rc;
     const BootArgs bt{boot_out, trunc_out};
-    h->xchg.allow = true;
-    if (int rc = rmav_launch_policy_rollout(h, kmode, a, &bt)) return rc;
-    h->t += (uint64_t)n_steps;
-    return RMAV_OK;
+    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, nullptr);
 }
 
 int rmav_control(rmav_handle h, float *actions_out, int mem, int layout) {
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
     if (!actions_out) return rmav_fail(RMAV_ERR_INVALID, "actions_out is NULL");
-    const size_t nact = (size_t)h->n * kActionDim[h->kind];
-    if (mem == RMAV_DEVICE) return launch_control(h, actions_out, layout);
-    if (nact * sizeof(float) <= kPinnedMax && ensure_pinned(h, nact * sizeof(float)) == RMAV_OK) {   // zero-copy
-        if (int rc = launch_control(h, (float *)h->pinned_dev, layout)) return rc;
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        memcpy(actions_out, h->pinned, nact * sizeof(float));
-        return RMAV_OK;
-    }
-    if (int rc = ensure_scratch(h, nact * sizeof(float))) return rc;
-    if (int rc = launch_control(h, (float *)h->scratch, layout)) return rc;
-    return copy_out(h, (const float *)h->scratch, actions_out, nact, RMAV_HOST);
+    return write_via_host(h, actions_out, (size_t)h->n * kActionDim[h->kind] * sizeof(float), mem,
+                          [&](void *dst) { return launch_control(h, (float *)dst, layout); });
 }
 
 int rmav_get_state(rmav_handle h, float *out, int mem, int layout) {
@@ -1497,20 +1400,25 @@ int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem) {
 }
 
 // ---- learner-side helpers on the trajectory ----------------------------------------------------
-int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values,
-             float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
-    CHECK_HANDLE(h);
+// with_boot (rmav_gae_boot): k_gae_boot, which adds the bootstrap term `boot` of the truncated steps
+static int gae_impl(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, bool with_boot, const float *boot,
+                    float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
     if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!rew || !done || !values || !adv_out || !ret_out)
-        return rmav_fail(RMAV_ERR_INVALID, "rew, done, values, adv_out and ret_out are required (device pointers)");
+    if (!rew || !done || !values || (with_boot && !boot) || !adv_out || !ret_out)
+        return rmav_fail(RMAV_ERR_INVALID, with_boot ? "rew, done, values, boot, adv_out and ret_out are required (device pointers)"
+                                                     : "rew, done, values, adv_out and ret_out are required (device pointers)");
     const unsigned nblk = (unsigned)((h->n + 255) / 256);
     double *partial = nullptr;
     if (sums_out) {
         if (int rc = ensure_scratch(h, (size_t)nblk * 2 * sizeof(double))) return rc;
         partial = (double *)h->scratch;
     }
-    hipLaunchKernelGGL(k_gae, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, adv_out, ret_out, h->n, n_steps,
-                       gamma, lam, reward_scale, partial);
+    if (with_boot)
+        hipLaunchKernelGGL(k_gae_boot, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, adv_out, ret_out, h->n, n_steps, gamma, lam,
+                           reward_scale, partial);
+    else
+        hipLaunchKernelGGL(k_gae, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, adv_out, ret_out, h->n, n_steps, gamma, lam, reward_scale,
+                           partial);
     HIP_TRY(hipGetLastError());
     if (sums_out) {
         hipLaunchKernelGGL(k_gae_fold, dim3(1), dim3(256), 0, h->stream, (const double *)partial, (int)nblk, sums_out);
@@ -1519,28 +1427,18 @@ int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *do
     return RMAV_OK;
 }
 
+int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values,
+             float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    CHECK_HANDLE(h);
+    return gae_impl(h, n_steps, rew, done, values, false, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
+}
+
 int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
                   float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
     CHECK_HANDLE(h);
     if (h->kind == RMAV_REINMAV)
         return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (use rmav_gae)");
-    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!rew || !done || !values || !boot || !adv_out || !ret_out)
-        return rmav_fail(RMAV_ERR_INVALID, "rew, done, values, boot, adv_out and ret_out are required (device pointers)");
-    const unsigned nblk = (unsigned)((h->n + 255) / 256);
-    double *partial = nullptr;
-    if (sums_out) {
-        if (int rc = ensure_scratch(h, (size_t)nblk * 2 * sizeof(double))) return rc;
-        partial = (double *)h->scratch;
-    }
-    hipLaunchKernelGGL(k_gae_boot, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, adv_out, ret_out, h->n, n_steps, gamma, lam,
-                       reward_scale, partial);
-    HIP_TRY(hipGetLastError());
-    if (sums_out) {
-        hipLaunchKernelGGL(k_gae_fold, dim3(1), dim3(256), 0, h->stream, (const double *)partial, (int)nblk, sums_out);
-        HIP_TRY(hipGetLastError());
-    }
-    return RMAV_OK;
+    return gae_impl(h, n_steps, rew, done, values, true, boot, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
 }
 
 int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rstd) {
@@ -1655,35 +1553,18 @@ int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weight
                              int precision) {
     CHECK_HANDLE(h);
     if (int rc = check_norm_handle(h, "rmav_rollout_policy_norm")) return rc;
-    if (precision != RMAV_POLICY_FP32_MFMA && precision != RMAV_POLICY_F16_MFMA && precision != RMAV_POLICY_F16_SHARED)
+    if (!limit_capable(precision))
         return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_norm runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
                                            "(the fp32 vector-ALU and bf16 actors have no normalised kernel), got precision %d", precision);
     if (int rc = check_stats(stats)) return rc;
-    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!weights || !logp_out || !value_out)
-        return rmav_fail(RMAV_ERR_INVALID, "weights, logp_out and value_out are required (device pointers)");
-    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
+    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
     if (h->time_limit > 0 && !boot_out)
         return rmav_fail(RMAV_ERR_INVALID, "boot_out is required on a handle with an episode time limit (as rmav_rollout_policy_boot)");
     if (h->time_limit <= 0 && (boot_out || trunc_out))
         return rmav_fail(RMAV_ERR_INVALID, "boot_out / trunc_out need an episode time limit on the handle (rmav_set_time_limit); pass NULL");
-    RolloutArgs a = base_args(h);
-    a.n_steps = n_steps;
-    a.act_out = actions_out;
-    a.obs_out = obs_out;
-    a.rew_out = rew_out;
-    a.done_out = done_out;
-    a.policy_w = weights;
-    a.logp_out = logp_out;
-    a.val_out = value_out;
-    const int kmode = precision == RMAV_POLICY_F16_MFMA ? (int)ACT_POLICY_F16 : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
-                                                                                                                : (int)ACT_POLICY_F32M;
     const BootArgs bt{boot_out, trunc_out};
     const NormArgs nm{((const ObsNormStats *)stats)->mean_f};
-    h->xchg.allow = true;
-    if (int rc = rmav_launch_policy_rollout_norm(h, kmode, a, &bt, nm)) return rc;
-    h->t += (uint64_t)n_steps;
-    return RMAV_OK;
+    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, &nm);
 }
 
 // ---- the path's one collective, behind the C ABI: RCCL all-gather of per-env episode statistics ---------------

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include <rccl/rccl.h>   // types only: the RCCL entry points are resolved with dlopen/dlsym on first use
 
@@ -148,11 +149,57 @@ inline int check_rollout_launch(rmav_handle h, const rmav::RolloutArgs &a) {
     return rmav_fail(RMAV_ERR_HIP, "rollout kernel launch failed: %s", hipGetErrorString(e));
 }
 
-// rmav_policy_abi.hip: launches rmav_rollout_policy's kernel for kmode = RMAV_ACT_POLICY | RMAV_ACT_POLICY_BF16 | ACT_POLICY_F32M |
-// ACT_POLICY_F16 | ACT_POLICY_F16_SHARED on the handle's stream
-// bt (rmav_rollout_policy_boot): the launch also leaves the bootstrap term of its truncated steps - the *_boot kernels; nullptr otherwise
-RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt = nullptr);
-// ... of rmav_rollout_policy_norm (the *_nrm kernels; kmode = ACT_POLICY_F32M | ACT_POLICY_F16 | ACT_POLICY_F16_SHARED, a quadrotor kind; bt is
-// required when the handle has a time limit and ignored otherwise)
-RMAV_INTERNAL int rmav_launch_policy_rollout_norm(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt,
-                                                  const rmav::NormArgs &nm);
+// ---- runtime value -> compile-time constant ------------------------------------------------------------------------------------
+// The handle's kind as std::integral_constant<int, K>: f is a generic lambda, `constexpr int K = decltype(k)::value` inside it.
+// ALL_KINDS = the four quadrotor kinds and ReinmavEnv, QUAD_KINDS = the quadrotor kinds only (no kernel of f's family exists for
+// ReinmavEnv, and f is not instantiated for it).  A plain switch over inlined lambdas: nothing is stored, nothing allocates.
+enum KindSet : bool { QUAD_KINDS = false, ALL_KINDS = true };
+template <KindSet SET, typename F> inline auto dispatch_kind(int kind, F &&f) -> decltype(f(std::integral_constant<int, rmav::QUAD2D>{})) {
+    switch (kind) {
+    case RMAV_QUAD2D: return f(std::integral_constant<int, rmav::QUAD2D>{});
+    case RMAV_QUAD2D_SL: return f(std::integral_constant<int, rmav::QUAD2D_SL>{});
+    case RMAV_QUAD3D: return f(std::integral_constant<int, rmav::QUAD3D>{});
+    case RMAV_QUAD3D_SL: return f(std::integral_constant<int, rmav::QUAD3D_SL>{});
+    case RMAV_REINMAV:
+        if constexpr (SET == ALL_KINDS) return f(std::integral_constant<int, rmav::REINMAV>{});
+        break;
+    }
+    return rmav_fail(RMAV_ERR_INVALID, "bad kind %d", kind);
+}
+// A store policy (rmav_kernels.hpp: ST_*) as std::integral_constant<int, ST>.  The call site names the policies its kernel family is
+// instantiated for: FALLBACK, which also takes every value outside the set, then the others.  f is instantiated for those only.
+template <int FALLBACK, int... OTHERS, typename F> inline auto dispatch_store(int st, F &&f) {
+    constexpr auto allowed = [](int v) { return ((v == OTHERS) || ...); };
+    switch (st) {
+    case rmav::ST_DEFAULT:
+        if constexpr (allowed(rmav::ST_DEFAULT)) return f(std::integral_constant<int, rmav::ST_DEFAULT>{});
+        break;
+    case rmav::ST_WRITE_THROUGH:
+        if constexpr (allowed(rmav::ST_WRITE_THROUGH)) return f(std::integral_constant<int, rmav::ST_WRITE_THROUGH>{});
+        break;
+    case rmav::ST_STREAM:
+        if constexpr (allowed(rmav::ST_STREAM)) return f(std::integral_constant<int, rmav::ST_STREAM>{});
+        break;
+    case rmav::ST_AOS_LDS:
+        if constexpr (allowed(rmav::ST_AOS_LDS)) return f(std::integral_constant<int, rmav::ST_AOS_LDS>{});
+        break;
+    }
+    return f(std::integral_constant<int, FALLBACK>{});
+}
+
+// The per-kind constants every stepping kernel takes: the env's own (Env<K>::P) and the fp64 controller's.
+template <int K> struct KindParams {
+    typename rmav::Env<K>::P p;
+    rmav::ParamsT<double> pc;
+};
+template <int K> RMAV_INTERNAL inline KindParams<K> kind_params(const rmav_env_s *h) {
+    return {rmav::derive_env<K>(h->params), rmav::derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL)};
+}
+
+// rmav_policy_abi.hip: launches the kernel of rmav_rollout_policy / _boot / _norm for kmode = RMAV_ACT_POLICY | RMAV_ACT_POLICY_BF16 |
+// ACT_POLICY_F32M | ACT_POLICY_F16 | ACT_POLICY_F16_SHARED on the handle's stream.
+// bt (rmav_rollout_policy_boot): the launch also leaves the bootstrap term of its truncated steps - the *_boot kernels; nullptr otherwise.
+// nm (rmav_rollout_policy_norm): the *_nrm kernels; kmode = ACT_POLICY_F32M | ACT_POLICY_F16 | ACT_POLICY_F16_SHARED, a quadrotor kind; bt is
+// required with it when the handle has a time limit and ignored otherwise.
+RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt = nullptr,
+                                             const rmav::NormArgs *nm = nullptr);

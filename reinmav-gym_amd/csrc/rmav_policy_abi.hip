@@ -16,26 +16,42 @@ using namespace rmav;
 
 namespace {
 
+// Which of an actor's kernels a launch runs.  A handle with a time limit takes the time-limited kernel, the *_boot one when the call
+// wants the bootstrap term (bt); rmav_rollout_policy_norm (nm) takes the *_nrm kernels, whose BOOT variant is the one of a handle with
+// a time limit (bt is required there).  Only the three actors a time-limited handle accepts - fp32-MFMA, f16 pair, shared-trunk pair,
+// on a quadrotor kind - have other kernels than the plain one.
+enum PolicyVariant { V_PLAIN, V_TL, V_BOOT, V_NRM, V_NRM_BOOT };
+inline PolicyVariant policy_variant(rmav_handle h, const BootArgs *bt, const NormArgs *nm) {
+    const bool limited = h->time_limit > 0;
+    return nm ? (limited ? V_NRM_BOOT : V_NRM) : limited ? (bt ? V_BOOT : V_TL) : V_PLAIN;
+}
+// the trailing arguments of those kernels: zero where the variant does not read them
+inline TimeLimitArgs variant_tl(rmav_handle h) { return h->time_limit > 0 ? tl_args(h) : TimeLimitArgs{}; }
+inline BootArgs variant_boot(rmav_handle h, const BootArgs *bt) { return (h->time_limit > 0 && bt) ? *bt : BootArgs{}; }
+constexpr size_t kNormBytes = sizeof(float) * kNormWords;   // the *_nrm kernels' tables, in LDS behind the weights
+
 // one wavefront per 64 envs (32 for the fp32-MFMA actor: both half-waves work on the same 32 envs)
 // (time-limited handles: k_rollout_tl, ACT_POLICY_F32M only - rmav_rollout_policy refuses the other one-wavefront actors)
-template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
+template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, MODE == ACT_POLICY_F32M ? 32 : 64);
-    const typename Env<K>::P p = derive_env<K>(h->params);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
+    const KindParams<K> kp = kind_params<K>(h);
     const size_t lds = sizeof(float) * (MODE == ACT_POLICY ? (size_t)PolicyLayout<Dims<K>::NS>::TOTAL
                                         : MODE == ACT_POLICY_BF16 ? (size_t)MfmaLayout::TOTAL : (size_t)Mfma32Layout::TOTAL);
     const int64_t per_wg = MODE == ACT_POLICY_F32M ? block_size(h) / 2 : block_size(h);
-    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg));
-    bool launched = false;
+    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(block_size(h));
+    PolicyVariant v = V_PLAIN;
     if constexpr (K != REINMAV && MODE == ACT_POLICY_F32M) {
-        if (h->time_limit > 0) {
-            if (bt) hipLaunchKernelGGL((k_rollout_boot<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h), *bt);
-            else hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc, tl_args(h));
-            launched = true;
-        }
+        v = policy_variant(h, bt, nm);
+        const TimeLimitArgs tl = variant_tl(h);
+        const BootArgs b = variant_boot(h, bt);
+        if (nm) a.act_in = nm->tab;   // (k_rollout_nrm takes the tables there: see the kernel)
+        if (v == V_TL) hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
+        else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_boot<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl, b);
+        else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b);
+        else if (v == V_NRM_BOOT) hipLaunchKernelGGL((k_rollout_nrm<K, true>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b);
     }
-    if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST_DEFAULT>), grid, dim3(block_size(h)), lds, h->stream, a, p, pc);
+    if (v == V_PLAIN) hipLaunchKernelGGL((k_rollout<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc);
     return check_rollout_launch(h, a);
 }
 
@@ -43,141 +59,81 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
 // workgroup share one LDS copy of the weights (30 KB) but also one s_barrier; RMAV_TUNE_PAIR_GROUP = 1 .. 4 overrides.
 // (The *_boot kernels' larger tiles - pair_boot_lds_bytes / shared_boot_lds_bytes - fit the 160 KiB of a workgroup at every group
 // count: 4 pairs of the 16-state kind take 113 KiB / 101 KiB.)
-static_assert(pair_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + sizeof(float) * kNormWords <= (160u << 10) &&
-                  shared_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + sizeof(float) * kNormWords <= (160u << 10),
+static_assert(pair_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + kNormBytes <= (160u << 10) &&
+                  shared_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + kNormBytes <= (160u << 10),
               "the hand-over tiles with their terminal-state areas must fit one workgroup's LDS");
-template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
+inline int pairs_per_workgroup(rmav_handle h, int measured) {
+    const int forced = h->tune[RMAV_TUNE_PAIR_GROUP];
+    return (forced >= 1 && forced <= kPairGroupMax) ? forced : measured;
+}
+template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, 64);
-    const typename Env<K>::P p = derive_env<K>(h->params);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
-    const int forced = h->tune[RMAV_TUNE_PAIR_GROUP];
+    const KindParams<K> kp = kind_params<K>(h);
     // measured (profiles/r04/actor_bench.txt, quadrotor3d x 32 steps): 65 536 envs 4 pairs 15.0 G env-steps/s, 2 pairs 14.1, 1 pair 13.7
     // (one workgroup per CU, weights staged once per CU); 131 072 envs 2 pairs 15.8 - 16.7, 4 pairs 15.5 - 16.3, 1 pair 11.1
-    const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : (h->n <= 98304 ? 4 : 2);
+    const int g = pairs_per_workgroup(h, h->n <= 98304 ? 4 : 2);
     const int64_t per_wg = 64 * g;
-    bool launched = false;
+    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
+    PolicyVariant v = V_PLAIN;
     if constexpr (K != REINMAV && FMT == FMT_F16) {   // (time-limited handles: RMAV_POLICY_F16_MFMA only)
-        if (h->time_limit > 0) {
-            if (bt)
-                hipLaunchKernelGGL((k_rollout_pair_boot<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g),
-                                   pair_boot_lds_bytes<K>(g), h->stream, a, p, pc, tl_args(h), *bt);
-            else
-                hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
-                                   h->stream, a, p, pc, tl_args(h));
-            launched = true;
-        }
+        v = policy_variant(h, bt, nm);
+        const TimeLimitArgs tl = variant_tl(h);
+        const BootArgs b = variant_boot(h, bt);
+        const size_t lds = pair_lds_bytes<K>(g), lds_boot = pair_boot_lds_bytes<K>(g);
+        if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
+        else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_pair_boot<K, FMT>), grid, block, lds_boot, h->stream, a, kp.p, kp.pc, tl, b);
+        else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
+        else if (v == V_NRM_BOOT)
+            hipLaunchKernelGGL((k_rollout_pair_nrm<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
     }
-    if (!launched)
-        hipLaunchKernelGGL((k_rollout_pair<K, FMT>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), pair_lds_bytes<K>(g),
-                           h->stream, a, p, pc);
+    if (v == V_PLAIN) hipLaunchKernelGGL((k_rollout_pair<K, FMT>), grid, block, pair_lds_bytes<K>(g), h->stream, a, kp.p, kp.pc);
     return check_rollout_launch(h, a);
 }
 
 // RMAV_POLICY_F16_SHARED: one trunk, both wavefronts of a pair evaluate it for one 32-env column tile each (k_rollout_pair_shared)
-template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt) {
+template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
     RolloutArgs a = a_in;
     take_armed_exchange(h, a, 64);
-    const typename Env<K>::P p = derive_env<K>(h->params);
-    const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
-    const int forced = h->tune[RMAV_TUNE_PAIR_GROUP];
+    const KindParams<K> kp = kind_params<K>(h);
     // measured (profiles/r04/actor_bench.txt): 65 536 envs 1 / 2 / 4 pairs per workgroup 20.8 / 21.5 / 20.4 G env-steps/s, 131 072: 19.9 / 25.9 / 26.1
-    const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : 2;
+    const int g = pairs_per_workgroup(h, 2);
     const int64_t per_wg = 64 * g;
-    bool launched = false;
+    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
+    PolicyVariant v = V_PLAIN;
     if constexpr (K != REINMAV) {
-        if (h->time_limit > 0) {
-            if (bt)
-                hipLaunchKernelGGL((k_rollout_pair_shared_boot<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g),
-                                   shared_boot_lds_bytes<K>(g), h->stream, a, p, pc, tl_args(h), *bt);
-            else
-                hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
-                                   h->stream, a, p, pc, tl_args(h));
-            launched = true;
-        }
+        v = policy_variant(h, bt, nm);
+        const TimeLimitArgs tl = variant_tl(h);
+        const BootArgs b = variant_boot(h, bt);
+        const size_t lds = shared_lds_bytes<K>(g), lds_boot = shared_boot_lds_bytes<K>(g);
+        if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
+        else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_pair_shared_boot<K>), grid, block, lds_boot, h->stream, a, kp.p, kp.pc, tl, b);
+        else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
+        else if (v == V_NRM_BOOT)
+            hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
     }
-    if (!launched)
-        hipLaunchKernelGGL((k_rollout_pair_shared<K>), dim3((unsigned)((h->n + per_wg - 1) / per_wg)), dim3(128 * g), shared_lds_bytes<K>(g),
-                           h->stream, a, p, pc);
+    if (v == V_PLAIN) hipLaunchKernelGGL((k_rollout_pair_shared<K>), grid, block, shared_lds_bytes<K>(g), h->stream, a, kp.p, kp.pc);
     return check_rollout_launch(h, a);
 }
 
-// rmav_rollout_policy_norm: the *_nrm kernels (normalised observations in front of the nets) of the three actors a time-limited handle
-// accepts; a handle with a time limit takes the BOOT variant (bt is required there), one without the plain one.  Same launch shapes
-// as the kernels they derive from, kNormWords more LDS words.
-template <int K> int launch_policy_norm_k(rmav_handle h, int kmode, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs &nm) {
-    if constexpr (K == REINMAV) {
-        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv has no normalised rollout");
-    } else {
-        RolloutArgs a = a_in;
-        take_armed_exchange(h, a, kmode == ACT_POLICY_F32M ? 32 : 64);
-        const typename Env<K>::P p = derive_env<K>(h->params);
-        const ParamsT<double> pc = derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL);
-        const bool boot = h->time_limit > 0;
-        const TimeLimitArgs tl = boot ? tl_args(h) : TimeLimitArgs{};
-        const BootArgs b = boot ? *bt : BootArgs{};
-        constexpr size_t nbytes = sizeof(float) * kNormWords;
-        const int forced = h->tune[RMAV_TUNE_PAIR_GROUP];
-        if (kmode == ACT_POLICY_F32M) {
-            const int64_t per_wg = block_size(h) / 2;
-            const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(block_size(h));
-            const size_t lds = sizeof(float) * (size_t)Mfma32Layout::TOTAL + nbytes;
-            a.act_in = nm.tab;   // (k_rollout_nrm takes the tables there: see the kernel)
-            if (boot) hipLaunchKernelGGL((k_rollout_nrm<K, true>), grid, block, lds, h->stream, a, p, pc, tl, b);
-            else hipLaunchKernelGGL((k_rollout_nrm<K, false>), grid, block, lds, h->stream, a, p, pc, tl, b);
-        } else if (kmode == ACT_POLICY_F16) {
-            const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : (h->n <= 98304 ? 4 : 2);   // as launch_rollout_pair
-            const int64_t per_wg = 64 * g;
-            const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
-            if (boot) hipLaunchKernelGGL((k_rollout_pair_nrm<K, true>), grid, block, pair_boot_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
-            else hipLaunchKernelGGL((k_rollout_pair_nrm<K, false>), grid, block, pair_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
-        } else if (kmode == ACT_POLICY_F16_SHARED) {
-            const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : 2;   // as launch_rollout_pair_shared
-            const int64_t per_wg = 64 * g;
-            const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
-            if (boot)
-                hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, true>), grid, block, shared_boot_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
-            else
-                hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, false>), grid, block, shared_lds_bytes<K>(g) + nbytes, h->stream, a, p, pc, tl, b, nm);
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no normalised kernel for policy mode %d", kmode);
-        }
-        return check_rollout_launch(h, a);
-    }
-}
-
-template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt) {
+template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs *nm) {
     // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
+    if (nm && (K == REINMAV || (kmode != ACT_POLICY_F32M && kmode != ACT_POLICY_F16 && kmode != ACT_POLICY_F16_SHARED)))
+        return rmav_fail(RMAV_ERR_INVALID, "no normalised kernel for policy mode %d", kmode);
     switch (kmode) {
-    case RMAV_ACT_POLICY: return launch_policy_1w<K, ACT_POLICY>(h, a, nullptr);
+    case RMAV_ACT_POLICY: return launch_policy_1w<K, ACT_POLICY>(h, a, nullptr, nullptr);
     case RMAV_ACT_POLICY_BF16:
-        return h->tune[RMAV_TUNE_POLICY_PAIR] == 0 ? launch_policy_1w<K, ACT_POLICY_BF16>(h, a, nullptr) : launch_rollout_pair<K, FMT_BF16>(h, a, nullptr);
-    case ACT_POLICY_F32M: return launch_policy_1w<K, ACT_POLICY_F32M>(h, a, bt);
-    case ACT_POLICY_F16: return launch_rollout_pair<K, FMT_F16>(h, a, bt);
-    case ACT_POLICY_F16_SHARED: return launch_rollout_pair_shared<K>(h, a, bt);
+        return h->tune[RMAV_TUNE_POLICY_PAIR] == 0 ? launch_policy_1w<K, ACT_POLICY_BF16>(h, a, nullptr, nullptr)
+                                                   : launch_rollout_pair<K, FMT_BF16>(h, a, nullptr, nullptr);
+    case ACT_POLICY_F32M: return launch_policy_1w<K, ACT_POLICY_F32M>(h, a, bt, nm);
+    case ACT_POLICY_F16: return launch_rollout_pair<K, FMT_F16>(h, a, bt, nm);
+    case ACT_POLICY_F16_SHARED: return launch_rollout_pair_shared<K>(h, a, bt, nm);
     }
     return rmav_fail(RMAV_ERR_INVALID, "unknown policy mode %d", kmode);
 }
 
 }  // namespace
 
-int rmav_launch_policy_rollout(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt) {
-    switch (h->kind) {
-    case RMAV_QUAD2D: return launch_policy_k<QUAD2D>(h, kmode, a, bt);
-    case RMAV_QUAD2D_SL: return launch_policy_k<QUAD2D_SL>(h, kmode, a, bt);
-    case RMAV_QUAD3D: return launch_policy_k<QUAD3D>(h, kmode, a, bt);
-    case RMAV_QUAD3D_SL: return launch_policy_k<QUAD3D_SL>(h, kmode, a, bt);
-    case RMAV_REINMAV: return launch_policy_k<REINMAV>(h, kmode, a, nullptr);
-    }
-    return rmav_fail(RMAV_ERR_INVALID, "bad kind");
-}
-
-int rmav_launch_policy_rollout_norm(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs &nm) {
-    switch (h->kind) {
-    case RMAV_QUAD2D: return launch_policy_norm_k<QUAD2D>(h, kmode, a, bt, nm);
-    case RMAV_QUAD2D_SL: return launch_policy_norm_k<QUAD2D_SL>(h, kmode, a, bt, nm);
-    case RMAV_QUAD3D: return launch_policy_norm_k<QUAD3D>(h, kmode, a, bt, nm);
-    case RMAV_QUAD3D_SL: return launch_policy_norm_k<QUAD3D_SL>(h, kmode, a, bt, nm);
-    }
-    return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_norm runs the four quadrotor kinds");
+int rmav_launch_policy_rollout(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs *nm) {
+    return dispatch_kind<ALL_KINDS>(h->kind, [&](auto k) { return launch_policy_k<decltype(k)::value>(h, kmode, a, bt, nm); });
 }
