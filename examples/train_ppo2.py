@@ -18,6 +18,7 @@ import torch
 import gym_reinmav_amd as g
 from gym_reinmav_amd.obs_norm import RunningObsNorm
 from gym_reinmav_amd.ppo import PPO, FusedPolicyCollector, MlpPolicy
+from gym_reinmav_amd.ret_norm import RunningReturnNorm
 
 
 def main():
@@ -27,7 +28,7 @@ def main():
     ap.add_argument("--num_timesteps", type=float, default=2e7)
     ap.add_argument("--nsteps", type=int, default=64, help="env-steps per env and rollout")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--reward_scale", type=float, default=0.05)
+    ap.add_argument("--reward_scale", type=float, default=None, help="default 0.05, or 1 with --normalize-reward")
     ap.add_argument("--actor", default="f16", choices=["fp32", "bf16", "f16"], help="arithmetic of the in-kernel actor")
     ap.add_argument("--max_episode_steps", type=int, default=0, help="episode time limit H (gym's TimeLimit, inside the kernels); 0 = none")
     ap.add_argument("--bootstrap_truncated", action="store_true",
@@ -35,10 +36,14 @@ def main():
     ap.add_argument("--normalize-obs", dest="normalize_obs", action="store_true",
                     help="VecNormalize(ob=True) in front of the nets, inside the rollout kernel (statistics frozen per rollout); "
                          "with --max_episode_steps it needs --bootstrap_truncated; not with --actor bf16")
+    ap.add_argument("--normalize-reward", dest="normalize_reward", action="store_true",
+                    help="VecNormalize(ret=True) in front of GAE: rewards divided by the running std of the discounted return")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
     args = ap.parse_args()
+    if args.reward_scale is None:
+        args.reward_scale = 1.0 if args.normalize_reward else 0.05
 
     torch.manual_seed(args.seed)
     kind = g.ENV_IDS[args.env]
@@ -46,17 +51,20 @@ def main():
         ap.error("--bootstrap_truncated needs --max_episode_steps")
     env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None)
     obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
+    ret_norm = RunningReturnNorm(f"cuda:{env.device}") if args.normalize_reward else None   # ... and its ret=True half
     policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()
     if args.load_path:                                      # run.py:188 model.load(load_path)
         policy.load_state_dict(torch.load(args.load_path, map_location="cuda"))
         if obs_norm is not None and os.path.exists(args.load_path + ".obs_norm"):
             obs_norm.load_state_dict(torch.load(args.load_path + ".obs_norm"))
+        if ret_norm is not None and os.path.exists(args.load_path + ".ret_norm"):
+            ret_norm.load_state_dict(torch.load(args.load_path + ".ret_norm"))
     elif kind in ("quad3d", "quad3d_sl"):
         with torch.no_grad():
             policy.pi[2].bias[0] = 9.8                      # start around hover thrust
     collector = FusedPolicyCollector(env, policy, args.nsteps, bf16_mfma=(args.actor == "bf16"), f16_mfma=(args.actor == "f16"),
                                      bootstrap_truncated=args.bootstrap_truncated)
-    learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale)
+    learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()
     for it in range(iters):
@@ -74,6 +82,8 @@ def main():
         torch.save(policy.state_dict(), args.save_path)
         if obs_norm is not None:                            # the statistics belong to the weights
             torch.save(obs_norm.state_dict(), args.save_path + ".obs_norm")
+        if ret_norm is not None:
+            torch.save(ret_norm.state_dict(), args.save_path + ".ret_norm")
         print("saved", args.save_path)
     if args.play:                                           # run.py:190-211: obs = env.reset(); loop model.step / env.step
         if obs_norm is not None:

@@ -166,6 +166,55 @@ int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weight
                              float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out,
                              int precision);
 
+/* ---- return normalisation: the reward half of baselines' VecNormalize(ret=True) in front of GAE -------------------------------------
+ * baselines (third-party behaviour restated from memory), per env-step and per env:
+ *     R = R * gamma + rew                    R: one float per env, 0 after reset(); gamma = 0.99
+ *     ret_rms.update(R)                      ONE scalar RunningMeanStd (mean 0, var 1, count 1e-4; Chan's merge) over all envs
+ *     rew = clip(rew / sqrt(ret_rms.var + eps), +-cliprew)         cliprew = 10; the mean is NOT subtracted
+ *     R[done] = 0
+ * --reward_scale acts inside each env, in front of the wrapper: R accumulates reward_scale * r.  All five env kinds.
+ *
+ * The statistics live in ONE caller-owned DEVICE buffer of rmav_ret_norm_bytes() bytes, 16-byte aligned (not handle state, as the
+ * observation statistics above).  Every call below is a launch on the handle's stream: nothing synchronises.  Fields (byte offset):
+ *     0  double count          returns seen (starts at count0)
+ *     8  double mean           running mean of R (kept for RunningMeanStd's merge; the normalisation does not use it)
+ *    16  double m2             running sum of squared deviations: var = m2 / count
+ *    24  double eps            the epsilon under the square root
+ *    32  float  clip           the clip (+inf = none), 3 pad words
+ *    48  float  rstd_f         \  the table the kernels read, rewritten by every merge:
+ *    52  float  clip_f         /  rstd_f = (float)(1 / sqrt(var + eps)) (computed in fp64, rounded once); 2 pad words
+ * THE arithmetic, wherever a reward is normalised (rmav_ret_normalize, rmav_gae_norm), in fp32, uncontracted, in this order:
+ *     z = (reward_scale * r) * rstd_f;   z = min(max(z, -clip), clip)
+ * so torch's clamp((rew * scale) * rstd_f, -clip, clip) in fp32 reproduces it bit for bit for finite r, and identity statistics
+ * (rstd 1, clip +inf) with reward_scale = 1 leave the bits of r. */
+int64_t rmav_ret_norm_bytes(void);
+/* mean 0, var 1, count = count0 (baselines: 1e-4), clip > 0 (baselines: 10; +inf allowed), eps >= 0 (baselines: 1e-8); table from that
+ * state: rstd_f = (float)(1 / sqrt(1 + eps)) (= 1.0f for eps <= 5e-8). */
+int rmav_ret_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0);
+/* The forward scan over a stored trajectory: rew [n_steps][N], done u8 [n_steps][N] (what the rollouts write), carry float [N] = R of
+ * every env before the first step (in) and after the last one (out; zero it when the envs are reset).  Per step, in fp32:
+ *     R = fmaf(gamma, R, reward_scale * r_t);   R enters the moments;   R = 0 where done_t
+ * batch_out <- 3 doubles on the device (count = n_steps * N, mean, m2 = sum of squared deviations from the batch mean), accumulated
+ * per env in fp64 and combined pairwise (Chan) per block, then folded - no floating-point atomics: the same input gives the same
+ * bits.  n_steps = 0 leaves an empty record (count 0) and does not touch carry.  Reads 5 bytes per sample.  Uses the handle's scratch
+ * buffer. */
+int rmav_ret_moments(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, float reward_scale, float gamma, float *carry,
+                     double *batch_out);
+/* Merges n_batches consecutive 3-double records (DEVICE) into the running state, in order, with RunningMeanStd's update rule, then
+ * rewrites the table; empty records are skipped.  n_batches > 1: every rank's record after an all-gather, merged in rank order so that
+ * all ranks end with the same bits.  One tiny launch. */
+int rmav_ret_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches);
+/* out[i] = the arithmetic above applied to in[i], i < count (out == in allowed; count = 0: no-op). */
+int rmav_ret_normalize(rmav_handle h, const void *stats, const float *in, float *out, int64_t count, float reward_scale);
+/* rmav_gae (boot NULL) / rmav_gae_boot (boot [n_steps][N]) with the arithmetic above applied to every reward as it is loaded:
+ *   delta_t = z_t + gamma ((1 - done_t) V_{t+1} [+ boot_t]) - V_t,  z_t = clamp((reward_scale r_t) * rstd_f, -clip, clip)
+ * rstd_f / clip_f are read from `stats` inside the launch (no host read of the scale), and the normalised rewards are never stored:
+ * the launch moves the bytes of rmav_gae / rmav_gae_boot.  Outputs, sums_out included, have the bits of rmav_gae / rmav_gae_boot
+ * with reward_scale = 1 on the output of rmav_ret_normalize; identity statistics and reward_scale = 1 give their bits on the raw
+ * rewards.  boot non-NULL follows rmav_gae_boot's rules (RMAV_REINMAV: RMAV_ERR_INVALID), boot NULL rmav_gae's. */
+int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
+                  const void *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out);
+
 #ifdef __cplusplus
 }
 #endif

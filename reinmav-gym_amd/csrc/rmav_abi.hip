@@ -14,6 +14,7 @@
 #include "rmav_handle.hpp"
 #include "rmav_gae.hpp"
 #include "rmav_obs_norm.hpp"
+#include "rmav_ret_norm.hpp"
 
 using namespace rmav;
 
@@ -1400,9 +1401,10 @@ int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem) {
 }
 
 // ---- learner-side helpers on the trajectory ----------------------------------------------------
-// with_boot (rmav_gae_boot): k_gae_boot, which adds the bootstrap term `boot` of the truncated steps
+// The one launcher of the GAE family.  with_boot (rmav_gae_boot): k_gae_boot, which adds the bootstrap term `boot` of the truncated steps;
+// stats (rmav_gae_norm): k_gae_norm<with_boot>, which normalises every reward as it is loaded (csrc/rmav_ret_norm.hpp)
 static int gae_impl(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, bool with_boot, const float *boot,
-                    float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+                    const RetNormStats *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
     if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
     if (!rew || !done || !values || (with_boot && !boot) || !adv_out || !ret_out)
         return rmav_fail(RMAV_ERR_INVALID, with_boot ? "rew, done, values, boot, adv_out and ret_out are required (device pointers)"
@@ -1413,7 +1415,13 @@ static int gae_impl(rmav_handle h, int32_t n_steps, const float *rew, const uint
         if (int rc = ensure_scratch(h, (size_t)nblk * 2 * sizeof(double))) return rc;
         partial = (double *)h->scratch;
     }
-    if (with_boot)
+    if (stats && with_boot)
+        hipLaunchKernelGGL(k_gae_norm<true>, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, stats, adv_out, ret_out, h->n, n_steps,
+                           gamma, lam, reward_scale, partial);
+    else if (stats)
+        hipLaunchKernelGGL(k_gae_norm<false>, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, stats, adv_out, ret_out, h->n, n_steps,
+                           gamma, lam, reward_scale, partial);
+    else if (with_boot)
         hipLaunchKernelGGL(k_gae_boot, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, adv_out, ret_out, h->n, n_steps, gamma, lam,
                            reward_scale, partial);
     else
@@ -1430,7 +1438,7 @@ static int gae_impl(rmav_handle h, int32_t n_steps, const float *rew, const uint
 int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values,
              float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
     CHECK_HANDLE(h);
-    return gae_impl(h, n_steps, rew, done, values, false, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
+    return gae_impl(h, n_steps, rew, done, values, false, nullptr, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
 }
 
 int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
@@ -1438,7 +1446,7 @@ int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_
     CHECK_HANDLE(h);
     if (h->kind == RMAV_REINMAV)
         return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (use rmav_gae)");
-    return gae_impl(h, n_steps, rew, done, values, true, boot, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
+    return gae_impl(h, n_steps, rew, done, values, true, boot, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
 }
 
 int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rstd) {
@@ -1546,6 +1554,79 @@ int rmav_obs_normalize(rmav_handle h, const void *stats, const float *in, float 
     hipLaunchKernelGGL(k_obs_normalize, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const ObsNormStats *)stats, in, out, sh);
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
+}
+
+// ---- return normalisation (the reward half of VecNormalize): one scalar RunningMeanStd on the device, csrc/rmav_ret_norm.hpp -----------
+namespace {
+int check_ret_stats(const void *stats) {
+    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_ret_norm_bytes() bytes)");
+    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
+    return RMAV_OK;
+}
+}  // namespace
+
+int64_t rmav_ret_norm_bytes(void) { return (int64_t)sizeof(RetNormStats); }
+
+int rmav_ret_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
+    CHECK_HANDLE(h);
+    if (int rc = check_ret_stats(stats)) return rc;
+    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
+        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    hipLaunchKernelGGL(k_ret_norm_init, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, clip, eps, count0);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ret_moments(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, float reward_scale, float gamma, float *carry,
+                     double *batch_out) {
+    CHECK_HANDLE(h);
+    if (n_steps < 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be >= 0");
+    if (!batch_out) return rmav_fail(RMAV_ERR_INVALID, "batch_out is required (3 doubles on the device)");
+    if (n_steps > 0 && (!rew || !done || !carry)) return rmav_fail(RMAV_ERR_INVALID, "rew, done and carry are required (device pointers)");
+    const unsigned nblk = n_steps > 0 ? (unsigned)((h->n + 255) / 256) : 0u;   // 0 steps: an empty record, carry untouched
+    if (nblk) {
+        if (int rc = ensure_scratch(h, (size_t)nblk * sizeof(Moment))) return rc;
+        hipLaunchKernelGGL(k_ret_moments, dim3(nblk), dim3(256), 0, h->stream, rew, done, carry, h->n, n_steps, reward_scale, gamma,
+                           (Moment *)h->scratch);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ret_moments_fold, dim3(1), dim3(256), 0, h->stream, (const Moment *)h->scratch, (int32_t)nblk, batch_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ret_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
+    CHECK_HANDLE(h);
+    if (int rc = check_ret_stats(stats)) return rc;
+    if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
+    if (n_batches == 0) return RMAV_OK;
+    if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 3 doubles on the device)");
+    hipLaunchKernelGGL(k_ret_norm_merge, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, batch, n_batches);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ret_normalize(rmav_handle h, const void *stats, const float *in, float *out, int64_t count, float reward_scale) {
+    CHECK_HANDLE(h);
+    if (int rc = check_ret_stats(stats)) return rc;
+    if (count < 0) return rmav_fail(RMAV_ERR_INVALID, "count must be >= 0");
+    if (count == 0) return RMAV_OK;
+    if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
+    if ((count + 255) / 256 > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many elements for one launch");
+    hipLaunchKernelGGL(k_ret_normalize, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (const RetNormStats *)stats, in, out, count,
+                       reward_scale);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
+                  const void *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    CHECK_HANDLE(h);
+    if (boot && h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (pass boot = NULL)");
+    if (int rc = check_ret_stats(stats)) return rc;
+    return gae_impl(h, n_steps, rew, done, values, boot != nullptr, boot, (const RetNormStats *)stats, gamma, lam, reward_scale, adv_out, ret_out,
+                    sums_out);
 }
 
 int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weights, const void *stats, float *actions_out, float *obs_out,

@@ -285,17 +285,25 @@ class BatchedQuadrotor:
         return obs, rew, done, nxt
 
     def gae(self, rew, done, values, gamma: float = 0.99, lam: float = 0.95, reward_scale: float = 1.0, out=None,
-            sums=None, boot=None):
+            sums=None, boot=None, ret_norm=None):
         """GAE(lambda) over a time-major device trajectory (``rmav_gae``): rew f32 [T,N], done u8 [T,N],
         values f32 [T+1,N] -> (adv [T,N], returns [T,N]); ``sums`` (f64[2] device tensor, optional) receives
         (sum A, sum A^2).  ``boot`` f32 [T,N] (optional): V(s_final) of the truncated steps, 0 elsewhere - their targets become
-        r + gamma V(s_final) (``rmav_gae_boot``)."""
+        r + gamma V(s_final) (``rmav_gae_boot``).  ``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`, optional):
+        every reward is scaled by its current statistics as it is loaded, ``clamp((reward_scale r) * rstd_f, -clip, clip)``
+        (``rmav_gae_norm``: the scale is read on the device, ``rew`` itself stays raw)."""
         T = int(rew.shape[0])
         assert tuple(rew.shape) == (T, self.num_envs) and tuple(done.shape) == (T, self.num_envs)
         assert tuple(values.shape) == (T + 1, self.num_envs) and done.dtype == torch.uint8
         adv, ret = out if out is not None else (torch.empty_like(rew), torch.empty_like(rew))
         if boot is not None:
             assert tuple(boot.shape) == (T, self.num_envs) and boot.dtype == torch.float32
+        if ret_norm is not None:
+            A.check(self._lib.rmav_gae_norm(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), self._ptr(boot),
+                                            C.c_void_p(ret_norm.data_ptr()), float(gamma), float(lam), float(reward_scale), self._ptr(adv),
+                                            self._ptr(ret), self._ptr(sums)))
+            return adv, ret
+        if boot is not None:
             A.check(self._lib.rmav_gae_boot(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), self._ptr(boot), float(gamma),
                                             float(lam), float(reward_scale), self._ptr(adv), self._ptr(ret), self._ptr(sums)))
             return adv, ret

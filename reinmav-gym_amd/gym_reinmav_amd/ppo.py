@@ -584,8 +584,14 @@ class PPO:
 
     def __init__(self, policy: MlpPolicy, lr: float = 3e-4, clip: float = 0.2, epochs: int = 4, minibatches: int = 4,
                  vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5, gamma: float = 0.99,
-                 lam: float = 0.95, reward_scale: float = 1.0):
+                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None):
+        """``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`): baselines' ``VecNormalize(ret=True)`` in front of
+        GAE - ``update`` first merges the rollout's discounted returns into it, then computes the advantages from rewards scaled by
+        the statistics that already include them (``ret_norm.py``); ``ro.rew`` stays raw.  ``self.adv`` / ``self.ret`` keep the
+        ``[T, N]`` advantages / returns of the last ``update``."""
         self.policy = policy
+        self.ret_norm = ret_norm
+        self.adv = self.ret = None
         self.reward_scale = float(reward_scale)   # baselines' --reward_scale (gym_reinmav/run.py:76)
         self.opt = torch.optim.Adam(policy.parameters(), lr=lr, eps=1e-5)
         self.clip, self.epochs, self.minibatches = clip, epochs, minibatches
@@ -618,11 +624,18 @@ class PPO:
 
     def update(self, ro: RolloutCollector) -> dict:
         T, N = ro.rew.shape
+        rn = self.ret_norm
+        if rn is not None:   # return statistics first: rollout k's rewards are scaled with statistics that include rollout k (ret_norm.py)
+            rn.update(ro.rew, ro.done, env=getattr(ro, "env", None), reward_scale=self.reward_scale)
         if ro.rew.is_cuda:   # one HIP launch over the [T][N] trajectory (per-lane reverse scan, csrc/rmav_gae.hpp)
-            adv, ret = ro.env.gae(ro.rew, ro.done, ro.val, self.gamma, self.lam, self.reward_scale, boot=getattr(ro, "boot", None))
+            adv, ret = ro.env.gae(ro.rew, ro.done, ro.val, self.gamma, self.lam, self.reward_scale, boot=getattr(ro, "boot", None), ret_norm=rn)
         else:
-            rew = ro.rew if self.reward_scale == 1.0 else ro.rew * self.reward_scale
+            if rn is not None:
+                rew = rn.normalize(ro.rew, self.reward_scale)
+            else:
+                rew = ro.rew if self.reward_scale == 1.0 else ro.rew * self.reward_scale
             adv, ret = gae(rew, ro.val, ro.done, self.gamma, self.lam, boot=getattr(ro, "boot", None))
+        self.adv, self.ret = adv, ret
         obs = ro.obs[:T].permute(1, 0, 2).reshape(ro.obs.shape[1], T * N)   # [nS, T*N] feature-major
         act = ro.act.permute(1, 0, 2).reshape(ro.act.shape[1], T * N)
         logp_old, val_old = ro.logp.reshape(-1), ro.val[:T].reshape(-1)

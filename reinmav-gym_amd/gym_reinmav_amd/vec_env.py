@@ -267,14 +267,22 @@ class VecNormalize:
     are the wrapped env's.  An info's ``'terminal_observation'`` is normalised with the same statistics as the step's observation
     (what stable-baselines3's ``VecNormalize`` does).
 
-    ``ret=True`` (return / reward normalisation, ``cliprew``) raises ``ValueError``: it needs a per-env discounted-return carry that
-    the kernels do not have yet.  ``self.obs_norm`` is the :class:`~gym_reinmav_amd.obs_norm.RunningObsNorm`; hand it to
-    ``MlpPolicy(obs_norm=...)`` only if the policy is to see RAW observations elsewhere - a policy fed by this wrapper needs none."""
+    ``norm_reward=True`` (stable-baselines3's spelling, with ``clip_reward`` and ``gamma``): return normalisation, baselines'
+    ``ret=True``.  ``step_wait()`` then runs three more small launches behind the step, on the env's stream, in baselines' exact
+    per-step order: ``rmav_ret_moments(n_steps=1)`` (``R = gamma R + rew`` per env, its moments, ``R = 0`` where done) ->
+    ``rmav_ret_norm_merge`` -> ``rmav_ret_normalize`` on the ``[N]`` reward: ``clip(rew / sqrt(var(R) + epsilon), +-clip_reward)``.
+    ``reset()`` zeroes the carry ``R``.  ``self.ret_norm`` is the :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm` (``None``
+    without ``norm_reward``).  The episode infos keep the RAW returns, as ``Monitor`` sits inside the wrapper in the reference.
 
-    def __init__(self, venv, ob: bool = True, ret: bool = False, clipob: float = 10.0, epsilon: float = 1e-8):
+    baselines' own spelling ``ret=True`` still raises ``ValueError`` (pass ``norm_reward=True``).  ``self.obs_norm`` is the
+    :class:`~gym_reinmav_amd.obs_norm.RunningObsNorm`; hand it to ``MlpPolicy(obs_norm=...)`` only if the policy is to see RAW
+    observations elsewhere - a policy fed by this wrapper needs none."""
+
+    def __init__(self, venv, ob: bool = True, ret: bool = False, clipob: float = 10.0, epsilon: float = 1e-8, norm_reward: bool = False,
+                 clip_reward: float = 10.0, gamma: float = 0.99):
         if ret:
-            raise ValueError("VecNormalize(ret=True): return / reward normalisation is not implemented (it needs a per-env "
-                             "discounted-return carry in the kernels); only observations are normalised - pass ret=False")
+            raise ValueError("VecNormalize(ret=True): return / reward normalisation is spelled norm_reward=True here (with clip_reward= "
+                             "and gamma=, as in stable-baselines3); pass ret=False")
         from .obs_norm import RunningObsNorm
 
         self.venv, self.ob = venv, bool(ob)
@@ -282,6 +290,22 @@ class VecNormalize:
         self.action_space, self.observation_space = venv.action_space, venv.observation_space
         self._dev = torch.device("cuda", venv.env.device)
         self.obs_norm = RunningObsNorm(venv.env.nS, self._dev, clip=clipob, eps=epsilon)
+        self.norm_reward, self.ret_norm = bool(norm_reward), None
+        if self.norm_reward:
+            from .ret_norm import RunningReturnNorm
+
+            self.ret_norm = RunningReturnNorm(self._dev, gamma=gamma, clip=clip_reward, eps=epsilon)
+
+    def _rewfilt(self, rew, done):
+        """update with this step's returns, then normalise this step's rewards (baselines' order)"""
+        env, rn = self.venv.env, self.ret_norm
+        if self.numpy_io:
+            r = torch.from_numpy(np.ascontiguousarray(rew, dtype=np.float32)).to(self._dev)
+            d = torch.from_numpy(np.ascontiguousarray(done).astype(np.uint8)).to(self._dev)
+            rn.update(r, d, env=env)
+            return rn.normalize(r, env=env, out=r).cpu().numpy()
+        rn.update(rew, done, env=env)
+        return rn.normalize(rew, env=env)
 
     def _obfilt(self, obs):
         if not self.ob:
@@ -301,7 +325,10 @@ class VecNormalize:
         return np.clip((np.asarray(rows, np.float32) - m) * r, -c, c)
 
     def reset(self):
-        return self._obfilt(self.venv.reset())
+        obs = self.venv.reset()
+        if self.norm_reward:
+            self.ret_norm.carry(self.venv.env).zero_()
+        return self._obfilt(obs)
 
     def step_async(self, actions):
         self.venv.step_async(actions)
@@ -309,6 +336,8 @@ class VecNormalize:
     def step_wait(self):
         obs, rew, done, infos = self.venv.step_wait()
         obs = self._obfilt(obs)
+        if self.norm_reward:
+            rew = self._rewfilt(rew, done)
         if self.ob and getattr(self.venv, "terminal_observation", False):
             if isinstance(infos, LazyInfos):
                 raw = infos._terminal
