@@ -38,6 +38,9 @@ def main():
                          "with --max_episode_steps it needs --bootstrap_truncated; not with --actor bf16")
     ap.add_argument("--normalize-reward", dest="normalize_reward", action="store_true",
                     help="VecNormalize(ret=True) in front of GAE: rewards divided by the running std of the discounted return")
+    ap.add_argument("--randomize", action="append", default=[], metavar="NAME=LO:HI",
+                    help="per-episode domain randomisation inside the kernels, e.g. mass=0.8:1.2 (mass | load_mass | tether_length; "
+                         "repeatable); not with --actor bf16")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -49,7 +52,16 @@ def main():
     kind = g.ENV_IDS[args.env]
     if args.bootstrap_truncated and not args.max_episode_steps:
         ap.error("--bootstrap_truncated needs --max_episode_steps")
-    env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None)
+    randomize = {}
+    for item in args.randomize:
+        try:
+            name, rng = item.split("=")
+            lo, hi = (float(v) for v in rng.split(":"))
+        except ValueError:
+            ap.error(f"--randomize wants NAME=LO:HI, got {item!r}")
+        randomize[name] = (lo, hi)
+    env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None,
+                             randomize=randomize or None)
     obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
     ret_norm = RunningReturnNorm(f"cuda:{env.device}") if args.normalize_reward else None   # ... and its ret=True half
     policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()

@@ -68,6 +68,9 @@
  *           c2 = low 32 bits of b, c3 = (2<<24) | (bits 32..47 of b) << 8 ; component i = fma(act_hi-act_lo, u_i, act_lo)
  *   policy noise (rmav_rollout_policy): as "action" with tag 3; (r0,r1) and (r2,r3) -> Box-Muller:
  *           u1 = ((r>>8)+1) * 2^-24, u2 = (r'>>8) * 2^-24, z = sqrt(-2 ln u1) * (cos, sin)(2 pi u2)
+ *   env constants (rmav_set_env_param_range): ONE block per env and reset, c2 = index of this env's reset (the c2 of the fresh state
+ *           of that reset), c3 = (4<<24); word `which` (enum rmav_env_param) gives u = (x>>8) * 2^-24 and
+ *           value = fma(hi - lo, u, lo) in fp32
  */
 #ifndef RMAV_H
 #define RMAV_H
@@ -186,6 +189,41 @@ int rmav_set_stream(rmav_handle h, void *hip_stream);
  * or NULL to go back to the shared value of rmav_params.  Quadrotor kinds only. */
 enum rmav_env_param { RMAV_PARAM_MASS = 0, RMAV_PARAM_LOAD_MASS = 1, RMAV_PARAM_TETHER_LENGTH = 2 };
 int rmav_set_env_param(rmav_handle h, int which, const float *values, int mem);
+/* N floats: the value every env runs with NOW - its element of the per-env array, or the shared value of rmav_params (rounded to
+ * fp32) where the parameter has no array.  Quadrotor kinds only. */
+int rmav_get_env_param(rmav_handle h, int which, float *out, int mem);
+
+/* ---- per-episode domain randomisation (env constants redrawn at every reset, inside the step kernels) -----------------------
+ * rmav_set_env_param gives every env its own constants, frozen for life.  Domain randomisation as RL users mean it draws new ones for
+ * every episode; auto-reset runs inside the kernels (a fused launch carries an env through several episodes), so the redraw lives
+ * there too.  Callers detect the feature by these symbols (RMAV_VERSION is unchanged).
+ *   - A per-handle range [lo, hi] per parameter; none is the default: a handle that never sets one behaves exactly as without this
+ *     feature and launches the kernels it launched before.
+ *   - While parameter `which` has a range, the value of env i during an episode is a pure function of (seed, global env id, the reset
+ *     index of that episode, which): the "env constants" stream of the RNG table above.  The reset index of an episode is the one its
+ *     fresh state was drawn with (0 for the reset of rmav_create; the running episode's = rmav_get_reset_counts - 1, modulo 2^32).
+ *     Global env ids make the values independent of sharding.
+ *   - The values are env state, held in the per-env arrays of rmav_set_env_param, and are redrawn exactly when the env's state is: at
+ *     rmav_reset and at every in-kernel auto-reset, by termination or by time-limit truncation.  rmav_set_env_param_range itself
+ *     draws parameter `which` for every env's running episode (and allocates the array if there is none).  rmav_seed, rmav_set_state,
+ *     rmav_set_reset_counts and rmav_set_step_count do not touch them.  Without RMAV_F_AUTO_RESET only rmav_reset redraws.
+ *   - The step that ends an episode uses the old episode's constants; everything evaluated on the post-reset state - the next step,
+ *     the trailing control() of rmav_step_control - the new ones.  What the kernels derive from the constants (1/mass,
+ *     1/(mass + load_mass), mass * tether_length) is re-derived in fp64 from the new values, as at the start of a launch.
+ *   - rmav_set_env_param(values) on a ranged parameter overwrites the values in force until each env's next reset; the range stays.
+ *     rmav_set_env_param(NULL) clears both the range and the array.  A checkpoint is the ranges plus rmav_get_env_param: restore the
+ *     ranges first, then the values.
+ *   - lo == hi == v gives fma(0, u, v) = v: such a handle produces, in every launch, the bits of a handle given N copies of v through
+ *     rmav_set_env_param.
+ *   - Launches of a ranged handle run kernels of their own: fused rollouts use the one-wavefront kernels
+ *     (RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE / RMAV_TUNE_STEP_LAZY / RMAV_TUNE_STEP_STORE do not apply; a chunk-major call is one launch
+ *     per chunk; results never depend on that), rmav_rollout_policy / _boot / _norm support RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA
+ *     and RMAV_POLICY_F16_SHARED (the others return RMAV_ERR_INVALID).
+ * lo and hi finite with 0 < lo <= hi, anything else is RMAV_ERR_INVALID; quadrotor kinds only (RMAV_REINMAV: RMAV_ERR_INVALID).  A
+ * parameter the kind does not read is accepted as rmav_set_env_param accepts it.
+ * rmav_get_env_param_range: *enabled = 1 and the range, or 0 (and lo = hi = 0) when the parameter has none; any pointer may be NULL. */
+int rmav_set_env_param_range(rmav_handle h, int which, float lo, float hi);
+int rmav_get_env_param_range(rmav_handle h, int which, float *lo, float *hi, int32_t *enabled);
 /* Explicit, per-handle overrides of the launch rules (DESIGN.md section 4 states the automatic rules and what was measured).
  * -1 = automatic, the default of every key.  Results never depend on them: every variant writes the same bits
  * (tests/test_gpu_parity.py::test_kernel_selection_variants_give_the_same_bits, ::test_single_step_variants_give_the_same_bits). */

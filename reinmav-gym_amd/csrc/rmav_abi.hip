@@ -209,6 +209,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->range_mask) {   // a handle with a parameter range: k_rollout_dr, with or without a time limit (launch_rollout_km routes it here)
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_ranged_rollout(h, MODE, ST, a)) return rc;
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no ranged kernel for action mode %d", MODE);
+        }
     } else {
         if (h->time_limit > 0) {   // (one launch per chunk of a chunk-major call: launch_rollout_km)
             // (ACT_BUFFER_CTRL comes here only with n_steps > 1, which no entry point asks for: its single steps run k_step_tl)
@@ -282,7 +288,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     constexpr bool has_split = (MODE == ACT_RANDOM || MODE == ACT_CONTROLLER || MODE == ACT_BUFFER) && K != REINMAV;
     // A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
     // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
-    if (K != REINMAV && h->time_limit > 0) {
+    // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -357,7 +364,9 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->time_limit > 0) {   // every batch size: the eager record load, k_step's preloaded arguments (k_step_tl)
+    if (h->range_mask) {   // a handle with a parameter range: k_step_dr for every batch size (eager record load, default store policy)
+        if (int rc = rmav_launch_ranged_step(h, a, ctrl, bs, FinalArgs{})) return rc;
+    } else if (h->time_limit > 0) {   // every batch size: the eager record load, k_step's preloaded arguments (k_step_tl)
         const TimeLimitArgs tl = tl_args(h);
         if (ctrl) launch_step_hot(h, a, kp, bs, k_step_tl<K, true>, tl);
         else dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(st, [&](auto s) { launch_step_hot(h, a, kp, bs, k_step_tl<K, false, decltype(s)::value>, tl); });
@@ -386,7 +395,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(step_store(h), [&](auto s) {
+    if (h->range_mask) {
+        if (int rc = rmav_launch_ranged_step(h, a, false, bs, fa)) return rc;
+    } else dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(step_store(h), [&](auto s) {
         constexpr int ST = decltype(s)::value;
         if (h->time_limit > 0) launch_step_hot(h, a, kp, bs, k_step_final<K, true, ST>, tl, fa);
         else launch_step_hot(h, a, kp, bs, k_step_final<K, false, ST>, tl, fa);
@@ -446,8 +457,32 @@ int restart_episode_clocks(rmav_handle h) {
 
 // rmav_reset: k_reset keeps ep_start only when the handle tracks episodes; a time-limited handle that does not gets it restarted by
 // the record fill behind it (k_reset itself is unchanged)
+// The device copy of the handle's ranges (k_rollout_nrm_dr reads them through a pointer): rewritten, in stream order, whenever they change.
+int sync_range_dev(rmav_handle h) {
+    if (!h->range_dev && hipMalloc((void **)&h->range_dev, sizeof(RangeArgs)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->range_dev = nullptr;
+        return rmav_fail(RMAV_ERR_ALLOC, "device allocation failed");
+    }
+    const RangeArgs r = range_args(h);
+    HIP_TRY(hipMemcpyAsync(h->range_dev, &r, sizeof(r), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (r is on this stack frame)
+    return RMAV_OK;
+}
+
+// The constants of the running episodes of the parameters in `mask`, drawn from their ranges (k_range_draw).
+int launch_range_draw(rmav_handle h, uint32_t mask) {
+    hipLaunchKernelGGL(k_range_draw, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, range_args(h, mask), (const EnvRec *)h->rec,
+                       (int64_t)h->n, h->seed, h->env_base);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// ... and a handle with parameter ranges redraws its constants behind it, for the reset index k_reset has just used.
 int launch_reset_tl(rmav_handle h, float *obs_dev, int layout) {
     if (int rc = launch_reset(h, obs_dev, layout)) return rc;
+    if (h->range_mask)
+        if (int rc = launch_range_draw(h, h->range_mask)) return rc;
     if (h->time_limit > 0 && !(h->flags & RMAV_F_TRACK_EPISODES)) return restart_episode_clocks(h);
     return RMAV_OK;
 }
@@ -576,6 +611,9 @@ void free_all(rmav_handle h) {
     if (h->pinned) (void)hipHostFree(h->pinned);
     if (h->done_flag) (void)hipHostFree(h->done_flag);
     if (h->last_trunc) (void)hipFree(h->last_trunc);
+    if (h->range_dev) (void)hipFree(h->range_dev);
+    if (h->ident_norm) (void)hipFree(h->ident_norm);
+    if (h->boot_scratch) (void)hipFree(h->boot_scratch);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     h->magic = 0;
     delete h;
@@ -831,7 +869,11 @@ int rmav_set_env_param(rmav_handle h, int which, const float *values, int mem) {
     if (int rc = check_mem_layout(mem, RMAV_SOA)) return rc;
     if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
     if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "per-env constants are for the quadrotor kinds");
-    if (!values) {  // back to the shared value
+    if (!values) {  // back to the shared value (and no range any more)
+        if ((h->range_mask >> which) & 1u) {
+            h->range_mask &= ~(1u << which);
+            if (int rc = sync_range_dev(h)) return rc;
+        }
         if (h->pe[which]) {
             HIP_TRY(hipStreamSynchronize(h->stream));
             HIP_TRY(hipFree(h->pe[which]));
@@ -845,6 +887,53 @@ int rmav_set_env_param(rmav_handle h, int which, const float *values, int mem) {
         return rmav_fail(RMAV_ERR_ALLOC, "device allocation failed");
     }
     return copy_in(h, h->pe[which], values, (size_t)h->n, mem);
+}
+
+int rmav_set_env_param_range(rmav_handle h, int which, float lo, float hi) {
+    CHECK_HANDLE(h);
+    if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "per-env constants are for the quadrotor kinds");
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo > 0.0f) || !(lo <= hi))
+        return rmav_fail(RMAV_ERR_INVALID, "a parameter range needs finite 0 < lo <= hi, got [%g, %g]", (double)lo, (double)hi);
+    if (!h->pe[which] && hipMalloc((void **)&h->pe[which], (size_t)h->n * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->pe[which] = nullptr;
+        return rmav_fail(RMAV_ERR_ALLOC, "device allocation failed");
+    }
+    h->range_lo[which] = lo;
+    h->range_hi[which] = hi;
+    h->range_mask |= 1u << which;
+    if (int rc = sync_range_dev(h)) return rc;
+    return launch_range_draw(h, 1u << which);   // this parameter only: the others keep the values they have
+}
+
+int rmav_get_env_param_range(rmav_handle h, int which, float *lo, float *hi, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
+    const bool on = (h->range_mask >> which) & 1u;
+    if (lo) *lo = on ? h->range_lo[which] : 0.0f;
+    if (hi) *hi = on ? h->range_hi[which] : 0.0f;
+    if (enabled) *enabled = on ? 1 : 0;
+    return RMAV_OK;
+}
+
+int rmav_get_env_param(rmav_handle h, int which, float *out, int mem) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, RMAV_SOA)) return rc;
+    if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "per-env constants are for the quadrotor kinds");
+    if (!out) return rmav_fail(RMAV_ERR_INVALID, "output pointer is NULL");
+    if (h->pe[which]) return copy_out(h, (const float *)h->pe[which], out, (size_t)h->n, mem);
+    // no array: every env has the shared value, rounded to fp32 as an uploaded array would hold it
+    const float v = (float)(which == RMAV_PARAM_MASS ? h->params.mass : which == RMAV_PARAM_LOAD_MASS ? h->params.load_mass : h->params.tether_length);
+    if (mem == RMAV_DEVICE) {
+        uint32_t bits;
+        memcpy(&bits, &v, 4);
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)bits, (size_t)h->n, h->stream));
+    } else {
+        for (int64_t i = 0; i < h->n; ++i) out[i] = v;
+    }
+    return RMAV_OK;
 }
 
 int rmav_set_tuning(rmav_handle h, int key, int value) {
@@ -1173,6 +1262,51 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
                       : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
                                                            : (int)ACT_POLICY_F32M;
     h->xchg.allow = true;
+    // A handle with a parameter range runs ONE ranged kernel per actor, the normalised one: a call without
+    // statistics gets identity tables - z then has the bits of x (rmav_ppo.h) - and a call on a time-limited handle that asked for no
+    // bootstrap term a boot_out of the handle's own.
+    BootArgs bt_r{};
+    NormArgs nm_r{};
+    if (h->range_mask) {
+        if (!limit_capable(precision))
+            return rmav_fail(RMAV_ERR_INVALID, "a handle with a parameter range runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or "
+                                               "RMAV_POLICY_F16_SHARED (the fp32 vector-ALU and bf16 actors have no ranged kernel)");
+        if (!nm) {
+            if (!h->ident_norm) {
+                float tab[kNormWords] = {};
+                for (int c = 0; c < 16; ++c) tab[16 + c] = 1.0f;
+                tab[32] = INFINITY;
+                if (hipMalloc((void **)&h->ident_norm, sizeof(tab)) != hipSuccess) {
+                    (void)hipGetLastError();
+                    h->ident_norm = nullptr;
+                    return rmav_fail(RMAV_ERR_ALLOC, "device allocation of the identity tables failed");
+                }
+                HIP_TRY(hipMemcpyAsync(h->ident_norm, tab, sizeof(tab), hipMemcpyHostToDevice, h->stream));
+                HIP_TRY(hipStreamSynchronize(h->stream));   // (tab is on this stack frame)
+            }
+            nm_r.tab = h->ident_norm;
+            nm = &nm_r;
+        }
+        if (h->time_limit > 0 && !bt) {
+            const size_t need = (size_t)n_steps * (size_t)h->n * sizeof(float);
+            if (need > h->boot_scratch_bytes) {
+                if (h->boot_scratch) {
+                    HIP_TRY(hipStreamSynchronize(h->stream));
+                    HIP_TRY(hipFree(h->boot_scratch));
+                    h->boot_scratch = nullptr;
+                    h->boot_scratch_bytes = 0;
+                }
+                if (hipMalloc((void **)&h->boot_scratch, need) != hipSuccess) {
+                    (void)hipGetLastError();
+                    h->boot_scratch = nullptr;
+                    return rmav_fail(RMAV_ERR_ALLOC, "device allocation of %zu bytes for the unused bootstrap terms failed", need);
+                }
+                h->boot_scratch_bytes = need;
+            }
+            bt_r.boot_out = h->boot_scratch;
+            bt = &bt_r;
+        }
+    }
     if (int rc = rmav_launch_policy_rollout(h, kmode, a, bt, nm)) return rc;
     h->t += (uint64_t)n_steps;
     return RMAV_OK;

@@ -266,6 +266,18 @@ __global__ __launch_bounds__(256) void k_shift_ep_start(EnvRec *rec, uint32_t de
     if (i < n) rec[i].ep_start += delta;
 }
 
+// The constants of every env's RUNNING episode - reset index = resets drawn so far - 1 - for the parameters of dr.mask:
+// rmav_set_env_param_range's initial draw, and rmav_reset's redraw behind k_reset.
+__global__ __launch_bounds__(kBlock) void k_range_draw(const RangeArgs dr, const EnvRec *rec, int64_t n, uint64_t seed, uint64_t env_base) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float v[3] = {0.0f, 0.0f, 0.0f};
+    range_draw(dr, seed, env_base + (uint64_t)i, rec[i].reset_cnt - 1u, v);
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+        if ((dr.mask >> w) & 1u) dr.pe[w][i] = v[w];
+}
+
 // One 32-bit field of the per-env records <-> a dense array (rmav_get_sbd / rmav_set_sbd, the reset counters, last lengths: the
 // accessors of the C ABI; not on any hot path).  field = word index in EnvRec: 0 sbd, 1 reset_cnt, 2 ep_start, 3 last_len.
 __global__ __launch_bounds__(256) void k_rec_get(uint32_t *out, const EnvRec *rec, int field, int64_t n) {

@@ -84,8 +84,30 @@ struct rmav_env_s {
     // truncated flags of the last finished episodes, allocated (zero-filled) on first use
     int32_t time_limit;
     uint8_t *last_trunc;
+    // per-episode domain randomisation (rmav_set_env_param_range): bit `which` of range_mask = pe[which] is redrawn from
+    // [range_lo, range_hi] whenever its env's state is; != 0 routes every stepping launch to the *_dr kernels
+    uint32_t range_mask;
+    float range_lo[3], range_hi[3];
+    // what the ranged policy kernels (the *_nrm bodies) are fed when the caller passed none: identity tables (allocated on first use)
+    // and, on a time-limited handle, a boot_out nobody reads (grown on demand)
+    rmav::RangeArgs *range_dev;   // device copy of range_args(h) for the kernels that take it by pointer (k_rollout_nrm_dr); kept current by sync_range_dev
+    float *ident_norm;
+    float *boot_scratch;
+    size_t boot_scratch_bytes;
 };
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
+// what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
+inline rmav::RangeArgs range_args(const rmav_env_s *h, uint32_t mask) {
+    rmav::RangeArgs r{};
+    for (int w = 0; w < 3; ++w) {
+        r.pe[w] = h->pe[w];
+        r.lo[w] = h->range_lo[w];
+        r.span[w] = h->range_hi[w] - h->range_lo[w];
+    }
+    r.mask = mask;
+    return r;
+}
+inline rmav::RangeArgs range_args(const rmav_env_s *h) { return range_args(h, h->range_mask); }
 
 constexpr int kExchangeDepth = 8;   // buffer pairs of the overlapped statistics exchange
 // bounds of k_wait_arrivals, in ticks of the 100 MHz wall clock: 2 s once the armed launch has begun, 10 min overall
@@ -203,3 +225,10 @@ template <int K> RMAV_INTERNAL inline KindParams<K> kind_params(const rmav_env_s
 // required with it when the handle has a time limit and ignored otherwise.
 RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt = nullptr,
                                              const rmav::NormArgs *nm = nullptr);
+
+// rmav_range_abi.hip: the launches of a handle with a parameter range (rmav_set_env_param_range).  _rollout: ONE launch of
+// k_rollout_dr<K, mode, st, time limit?> over the envs a names (mode = ACT_BUFFER | ACT_RANDOM | ACT_CONTROLLER, st = a store policy;
+// ST_AOS_LDS runs the write-through kernel); _step: k_step_dr at bs threads per workgroup, ctrl = the launch ends with control(),
+// fa = what rmav_step_final wants (NULL pointers otherwise).  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_ranged_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_ranged_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);

@@ -266,6 +266,39 @@ template <int NS> __device__ __forceinline__ void norm_state16(const float *ntab
     for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? norm1(t, c, s[c], clip) : 0.0f;
 }
 
+// Per-episode domain randomisation (rmav_set_env_param_range; the *_dr kernels), trailing as well.
+//   pe     the handle's per-env arrays again, writable: a lane whose env resets stores its new constants there (RolloutArgs::pe is const)
+//   lo, span   value = fma(span, u, lo), span = hi - lo in fp32, u = word `which` of the env's tag-4 Philox block (include/rmav.h)
+//   mask   bit `which`: the parameter has a range; the others keep the value they have
+struct RangeArgs {
+    float *pe[3];
+    float lo[3], span[3];
+    uint32_t mask;
+};
+// the constants of the episode that starts with reset index rc: v[which] for the ranged parameters, v untouched for the others
+RMAV_HD void range_draw(const RangeArgs &dr, uint64_t seed, uint64_t env_id, uint32_t rc, float (&v)[3]) {
+    uint32_t r[4];
+    philox4x32_10((uint32_t)env_id, (uint32_t)(env_id >> 32), rc, 4u << 24, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+        if ((dr.mask >> w) & 1u) v[w] = rfma(dr.span[w], u01(r[w]), dr.lo[w]);
+}
+// ... stored, and re-derived for the lane in each of ps (the env's constants, the fp64 controller's).  A parameter without a range keeps
+// its value in force: its per-env element (which no kernel writes) or the shared constant, read again here - on the rare reset path -
+// rather than carried through the step loop.
+template <typename... Ps>
+__device__ __forceinline__ void range_apply(const RangeArgs &dr, const float *const (&pe)[3], const ParamsT<double> &pc_shared, uint32_t li, uint32_t off,
+                                            const float (&v)[3], Ps &...ps) {
+    const double m = (dr.mask & 1u) ? (double)v[0] : pe[0] ? (double)pe[0][li] : (double)pc_shared.mass;
+    const double ml = (dr.mask & 2u) ? (double)v[1] : pe[1] ? (double)pe[1][li] : (double)pc_shared.load_mass;
+    const double L = (dr.mask & 4u) ? (double)v[2] : pe[2] ? (double)pe[2][li] : (double)pc_shared.L;
+    (override_params(ps, m, ml, L), ...);
+#pragma unroll
+    for (int w = 0; w < 3; ++w)
+        if ((dr.mask >> w) & 1u)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[w]), __builtin_amdgcn_make_buffer_rsrc(dr.pe[w], 0, -1, 0x00020000), off, 0, 0);
+}
+
 __device__ __forceinline__ uint32_t ep_clock0(const RolloutArgs &a) { return (uint32_t)a.t0; }
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
@@ -392,7 +425,8 @@ __device__ __forceinline__ void wide_cols(const float *tile, rsrc_t r, uint32_t 
 template <int K, int MODE, int ST = ST_DEFAULT, bool FIXED = false>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                     const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, DR = false;
+    [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -404,7 +438,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false;
+    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false;
+    [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     static_assert(!is_split(MODE) && K != REINMAV, "time-limited launches run the one-wavefront kernels");
@@ -416,7 +451,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                          const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
-    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false;
+    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false;
+    [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const NormArgs nm{};
     static_assert(MODE == ACT_POLICY_F32M && K != REINMAV, "the one-wavefront actor of time-limited handles");
 #include "rmav_rollout_body.inc"
@@ -435,7 +471,37 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     // scalar registers) wherever the argument was placed (profiles/r09/obs_norm.md).
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false;
+    [[maybe_unused]] const RangeArgs dr{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#include "rmav_rollout_body.inc"
+}
+// The one-wavefront kernels of a handle with a parameter range (rmav_set_env_param_range): a lane whose env resets draws the new
+// episode's constants (with the spare reset state where there is one), re-derives what override_params derives, and stores them.
+// TL = the handle has a time limit too (tl is not read otherwise).  Symbols of their own: the kernels above keep their instruction streams.
+template <int K, int MODE, int ST, bool TL>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr) {
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true;
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "ranged launches run the one-wavefront kernels");
+#include "rmav_rollout_body.inc"
+}
+
+// The fp32 matrix-core actor of a handle with a parameter range: k_rollout_nrm with the redraw, for rmav_rollout_policy, _boot and _norm
+// alike - a call without statistics gets the handle's identity tables (z has the bits of x), a call on a time-limited handle that
+// wants no bootstrap term gets a scratch boot_out.
+template <int K, bool BOOT>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp) {
+    // (the range by pointer - the handle's device copy, read with scalar loads on the reset path: as 60 more bytes of kernel arguments
+    // it cost three of these kernels, which run out of scalar registers first, a stack frame)
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
 }
@@ -509,9 +575,10 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 };
 // TL: the launch has an episode time limit (tl; k_step_tl) - with the eager record load only: every lane needs ep_start every step.
 // FIN: the launch also reports what the auto-reset destroys (fa; k_step_final).
-template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false>
+// DR: the handle has a parameter range (dr; k_step_dr): a finishing lane draws and stores the constants of its new episode.
+template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
-                                          const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}) {
+                                          const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{}) {
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
     static_assert(!(TL && LAZY), "a time limit needs every lane's episode start");
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
@@ -694,6 +761,15 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     }
     if (auto_reset)   // wave-uniform; every lane takes part
         reset_state_wave<K>(a.seed, a.env_base + (uint64_t)(gi - (threadIdx.x & 63u)), rc, done && valid, s);
+    if constexpr (DR) {
+        // the new episode's constants: the tag-4 block of the reset index its state was drawn with.  The step above used the old
+        // ones; the control() below, on the fresh state, uses these.
+        if (auto_reset && done && valid) {
+            float v[3] = {0.0f, 0.0f, 0.0f};
+            range_draw(dr, a.seed, a.env_base + (uint64_t)gi, rc, v);
+            range_apply(dr, a.pe, pc_shared, li, off, v, pl, pcl);
+        }
+    }
     if (valid) store_state();
     if constexpr (CTRL) {   // control() of the state this launch leaves behind
         float a2[NA];
@@ -792,6 +868,23 @@ __global__ __launch_bounds__(kBlock) void k_step_final(float *state_pl, int64_t 
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, false, false, ST, TL, true>(a, block_pl, p_shared, pc_shared, tl, fa);
+}
+
+// The single-step kernel of a handle with a parameter range, for every batch size and all four single-step entry points: k_step_final's
+// argument list (fa's pointers are NULL when the call wants neither output, tl is read only with TL) and the range behind it.
+template <int K, bool CTRL, bool TL>
+__global__ __launch_bounds__(kBlock) void k_step_dr(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, CTRL, false, ST_DEFAULT, TL, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr);
 }
 
 // reset() of every env

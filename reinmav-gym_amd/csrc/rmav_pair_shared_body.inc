@@ -187,8 +187,14 @@
     if constexpr (K == REINMAV) tenv = a.env_time[li];
     float spare[NS];
     bool have_spare = false;
+#if RMAV_PAIR_DR   // the *_dr kernels: the constants of the episode the spare state starts (the ranged parameters' elements)
+    float spare_pe[3] = {0.0f, 0.0f, 0.0f};
+#endif
     if (K != REINMAV && auto_reset && T >= 8) {
         reset_state<K>(a.seed, env_id, rc, spare);
+#if RMAV_PAIR_DR
+        range_draw(dr, a.seed, env_id, rc, spare_pe);
+#endif
         have_spare = true;
     }
     float pol_std[4] = {0.f, 0.f, 0.f, 0.f};
@@ -320,12 +326,18 @@
             if (__ballot(done && !have_spare) != 0) {
                 if (!have_spare) {   // every lane that has used its spare up (see k_rollout)
                     reset_state<K>(a.seed, env_id, rc, spare);
+            #if RMAV_PAIR_DR
+        range_draw(dr, a.seed, env_id, rc, spare_pe);
+#endif
                     have_spare = true;
                 }
             }
             if (done) {
 #pragma unroll
                 for (int c = 0; c < NS; ++c) s[c] = spare[c];
+#if RMAV_PAIR_DR
+                range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl);   // the new episode's constants, re-derived and stored
+#endif
                 have_spare = false;
                 rc += 1;
             }

@@ -46,7 +46,11 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
         const TimeLimitArgs tl = variant_tl(h);
         const BootArgs b = variant_boot(h, bt);
         if (nm) a.act_in = nm->tab;   // (k_rollout_nrm takes the tables there: see the kernel)
-        if (v == V_TL) hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
+        // a handle with a parameter range: the ranged *_nrm kernels (rmav_abi.hip hands every such call statistics and, with a limit, a boot_out)
+        if (h->range_mask && v == V_NRM) hipLaunchKernelGGL((k_rollout_nrm_dr<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, (const RangeArgs *)h->range_dev);
+        else if (h->range_mask && v == V_NRM_BOOT) hipLaunchKernelGGL((k_rollout_nrm_dr<K, true>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, (const RangeArgs *)h->range_dev);
+        else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
+        else if (v == V_TL) hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
         else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_boot<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl, b);
         else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b);
         else if (v == V_NRM_BOOT) hipLaunchKernelGGL((k_rollout_nrm<K, true>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b);
@@ -81,7 +85,11 @@ template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutAr
         const TimeLimitArgs tl = variant_tl(h);
         const BootArgs b = variant_boot(h, bt);
         const size_t lds = pair_lds_bytes<K>(g), lds_boot = pair_boot_lds_bytes<K>(g);
-        if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
+        if (h->range_mask && v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_dr<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
+        else if (h->range_mask && v == V_NRM_BOOT)
+            hipLaunchKernelGGL((k_rollout_pair_dr<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
+        else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
+        else if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
         else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_pair_boot<K, FMT>), grid, block, lds_boot, h->stream, a, kp.p, kp.pc, tl, b);
         else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
         else if (v == V_NRM_BOOT)
@@ -106,7 +114,11 @@ template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs
         const TimeLimitArgs tl = variant_tl(h);
         const BootArgs b = variant_boot(h, bt);
         const size_t lds = shared_lds_bytes<K>(g), lds_boot = shared_boot_lds_bytes<K>(g);
-        if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
+        if (h->range_mask && v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_shared_dr<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
+        else if (h->range_mask && v == V_NRM_BOOT)
+            hipLaunchKernelGGL((k_rollout_pair_shared_dr<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
+        else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
+        else if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
         else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_pair_shared_boot<K>), grid, block, lds_boot, h->stream, a, kp.p, kp.pc, tl, b);
         else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
         else if (v == V_NRM_BOOT)
@@ -120,6 +132,8 @@ template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs
     // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
     if (nm && (K == REINMAV || (kmode != ACT_POLICY_F32M && kmode != ACT_POLICY_F16 && kmode != ACT_POLICY_F16_SHARED)))
         return rmav_fail(RMAV_ERR_INVALID, "no normalised kernel for policy mode %d", kmode);
+    if (h->range_mask && (K == REINMAV || (kmode != ACT_POLICY_F32M && kmode != ACT_POLICY_F16 && kmode != ACT_POLICY_F16_SHARED)))
+        return rmav_fail(RMAV_ERR_INVALID, "no ranged kernel for policy mode %d", kmode);
     switch (kmode) {
     case RMAV_ACT_POLICY: return launch_policy_1w<K, ACT_POLICY>(h, a, nullptr, nullptr);
     case RMAV_ACT_POLICY_BF16:

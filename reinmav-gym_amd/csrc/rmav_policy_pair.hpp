@@ -30,6 +30,11 @@
 
 #include "rmav_kernels.hpp"
 
+// RMAV_PAIR_DR: the pair bodies (rmav_pair_body.inc, rmav_pair_shared_body.inc) compile the redraw of a ranged handle's constants
+// (rmav_set_env_param_range) only where a *_dr wrapper sets it around its #include.  A preprocessor flag, not a constexpr one like TL /
+// BOOT / NORM: even a dead local declaration in the bodies changed the register allocation of the bf16 pair kernels.
+#define RMAV_PAIR_DR 0
+
 namespace rmav {
 
 enum : int { FMT_BF16 = 0, FMT_F16 = 1 };
@@ -269,6 +274,21 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_nrm(con
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_body.inc"
 }
+// The f16 pair of a handle with a parameter range (rmav_set_env_param_range; see k_rollout_nrm_dr): k_rollout_pair_nrm whose actor
+// wavefront - the one that integrates - redraws the constants of a lane that resets.  Serves rmav_rollout_policy, _boot and _norm.
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr) {
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
 
 // ---- one shared 2 x 64 trunk with a mean head and a value head (RMAV_POLICY_F16_SHARED) -------------------------------------------
 //
@@ -412,6 +432,19 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     constexpr bool TL = BOOT, NORM = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_shared_body.inc"
+}
+// ... and the shared-trunk pair of such a handle: k_rollout_pair_shared_nrm with the redraw.
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                                    const BootArgs bt, const NormArgs nm, const RangeArgs dr) {
+    constexpr bool TL = BOOT, NORM = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
 }
 
 

@@ -483,6 +483,9 @@
             lds_spare = lds_w + split_g * SplitTile<NS, NA, DRAWS>::WORDS +
                         (uint32_t)__builtin_amdgcn_readfirstlane(split_local >> 6) * SplitTile<NS, NA, DRAWS>::SPARE + (threadIdx.x & 63u);
         bool have_spare = false;
+        // k_rollout_dr: the constants of the episode the spare state starts (the ranged parameters' elements)
+        [[maybe_unused]] float spare_pe[3];
+        if constexpr (DR) spare_pe[0] = spare_pe[1] = spare_pe[2] = 0.0f;
         if (K != REINMAV && auto_reset && a.n_steps >= 8) {   // ReinmavEnv.reset() is a no-op (reinmav_env.py:348-351)
             if constexpr (SPARE_LDS) {
                 float sp[NS];
@@ -492,6 +495,7 @@
             } else {
                 reset_state<K>(a.seed, env_id, rc, spare);
             }
+            if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);   // the spare constants with the spare state
             have_spare = true;
         }
 
@@ -795,6 +799,7 @@
                                     if constexpr (SPARE_LDS) lds_spare[c * 64] = sp[c];
                                     else spare[c] = sp[c];
                                 }
+                                if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);
                                 have_spare = true;
                             }
                         }
@@ -804,6 +809,7 @@
                                 if constexpr (SPARE_LDS) s[c] = lds_spare[c * 64];
                                 else s[c] = spare[c];
                             }
+                            if constexpr (DR) range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl, pcl);   // the new episode's constants, re-derived and stored
                             have_spare = false;
                             rc += 1;
                         }
@@ -839,6 +845,7 @@
                                 if constexpr (SPARE_LDS) lds_spare[c * 64] = sp[c];
                                 else spare[c] = sp[c];
                             }
+                            if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);
                             have_spare = true;
                         }
                     }
@@ -848,6 +855,7 @@
                             if constexpr (SPARE_LDS) s[c] = lds_spare[c * 64];
                             else s[c] = spare[c];
                         }
+                        if constexpr (DR) range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl, pcl);   // the new episode's constants, re-derived and stored
                         have_spare = false;
                         rc += 1;
                     }

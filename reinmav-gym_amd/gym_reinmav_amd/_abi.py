@@ -82,6 +82,9 @@ PROTOTYPES = {
     "rmav_set_params": (C.c_int, [C.c_void_p, C.POINTER(Params)]),
     "rmav_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rmav_set_env_param": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
+    "rmav_set_env_param_range": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "rmav_get_env_param_range": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "rmav_get_env_param": (C.c_int, [C.c_void_p, C.c_int, _fp, C.c_int]),
     "rmav_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "rmav_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "rmav_num_envs": (C.c_int64, [C.c_void_p]),

@@ -41,9 +41,13 @@ class BatchedQuadrotor:
 
     def __init__(self, kind, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
-                 reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None):
+                 reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
+                 randomize: Optional[dict] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
-        rmav_set_time_limit); None or 0 = no limit."""
+        rmav_set_time_limit); None or 0 = no limit.
+
+        ``randomize``: per-episode domain randomisation, ``{"mass": (lo, hi), "load_mass": ..., "tether_length": ...}``: every env
+        draws the constant anew from ``[lo, hi)`` whenever its state is reset, inside the kernels (:meth:`set_env_param_range`)."""
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
@@ -66,6 +70,8 @@ class BatchedQuadrotor:
         self._h = h
         if max_episode_steps:
             self.max_episode_steps = max_episode_steps
+        for name, (lo, hi) in (randomize or {}).items():
+            self.set_env_param_range(name, lo, hi)
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -457,6 +463,32 @@ class BatchedQuadrotor:
             return
         v, mem = self._in(values, (self.num_envs,))
         A.check(self._lib.rmav_set_env_param(self._h, which, self._ptr(v), mem))
+
+    _PARAMS = {"mass": A.PARAM_MASS, "load_mass": A.PARAM_LOAD_MASS, "tether_length": A.PARAM_TETHER_LENGTH}
+
+    def set_env_param_range(self, name: str, lo: Optional[float], hi: Optional[float] = None):
+        """Per-episode domain randomisation of one constant (``rmav_set_env_param_range``): while the range is set, env ``i`` runs
+        each episode with ``fma(hi - lo, u, lo)``, ``u`` from the Philox block of (seed, global env id, the episode's reset index) -
+        redrawn at :meth:`reset` and at every auto-reset inside the kernels, and drawn for the running episodes by this call.
+        ``lo=None`` clears the range AND the per-env values (``set_env_param(name, None)``)."""
+        which = self._PARAMS[name]
+        if lo is None:
+            A.check(self._lib.rmav_set_env_param(self._h, which, None, A.HOST))
+            return
+        A.check(self._lib.rmav_set_env_param_range(self._h, which, float(lo), float(lo if hi is None else hi)))
+
+    def get_env_param_range(self, name: str):
+        """``(lo, hi)`` of the constant's range, None if it has none."""
+        lo, hi, on = C.c_float(), C.c_float(), C.c_int32()
+        A.check(self._lib.rmav_get_env_param_range(self._h, self._PARAMS[name], C.byref(lo), C.byref(hi), C.byref(on)))
+        return (lo.value, hi.value) if on.value else None
+
+    def get_env_param(self, name: str, device_out: bool = False):
+        """f32 [N]: the constant every env runs its current episode with (the shared ``params`` value where no per-env array is
+        set).  With the ranges, this is the checkpoint of a randomised handle."""
+        out = self._new((self.num_envs,), np.float32, device_out)
+        A.check(self._lib.rmav_get_env_param(self._h, self._PARAMS[name], self._ptr(out), A.DEVICE if device_out else A.HOST))
+        return out
 
     def get_time(self) -> np.ndarray:
         """'reinmav' envs only: each env's own clock t (float64)."""

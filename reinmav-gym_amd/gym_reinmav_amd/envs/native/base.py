@@ -40,7 +40,7 @@ class NativeQuadrotorEnv(_EnvBase):
     _action_box = None    # (low, high, dtype)
     _reading_2d = None
 
-    def __init__(self, device: int = 0, seed=None, max_episode_steps=None):
+    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None):
         kind = A.KIND_BY_NAME[self._kind]
         nS, nA = A.STATE_DIM[kind], A.ACTION_DIM[kind]
         lo, hi, dt = self._action_box
@@ -53,10 +53,11 @@ class NativeQuadrotorEnv(_EnvBase):
         # limit lives in the kernels, and the handle then tracks episodes so that lengths survive seed() / reset() exactly.
         # (No 'terminal_observation' here: this env never auto-resets, so the obs step() returns for a finished episode IS its
         # terminal observation - rmav_step_final / QuadrotorVecEnv(terminal_observation=True) are for the batched, auto-resetting path.)
+        # randomize ({"mass": (lo, hi), ...}): the constants are drawn anew by every reset() (this env never auto-resets).
         self._limited = bool(max_episode_steps)
         self._batch = BatchedQuadrotor(kind, 1, device=device, seed=self._seed_value, auto_reset=False,
                                        track_episodes=self._limited, reading_2d=self._reading_2d,
-                                       max_episode_steps=max_episode_steps)
+                                       max_episode_steps=max_episode_steps, randomize=randomize)
         self._dim = 2 if nS in (5, 9) else 3
         self._has_load = nS in (9, 16)
         # Lean per-call path: preallocated host arrays and cached ctypes pointers, so a step() is one ABI call

@@ -486,6 +486,10 @@ class FusedPolicyCollector:
         if getattr(env, "max_episode_steps", None) and (bf16_mfma or not (f32_mfma or f16_mfma)):
             raise ValueError("an env with max_episode_steps runs the fp32 matrix-core actor (the default), f16_mfma=True or a "
                              "shared-trunk policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no time-limited kernel")
+        if (bf16_mfma or not (f32_mfma or f16_mfma)) and hasattr(env, "get_env_param_range") and any(
+                env.get_env_param_range(nm) for nm in ("mass", "load_mass", "tether_length")):
+            raise ValueError("an env with randomize= / set_env_param_range runs the fp32 matrix-core actor (the default), f16_mfma=True or a "
+                             "shared-trunk policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no ranged kernel")
         norm = getattr(policy, "obs_norm", None)
         if norm is not None:
             if bf16_mfma or not (f32_mfma or f16_mfma):
