@@ -88,6 +88,39 @@ int ensure_scratch(rmav_handle h, size_t bytes) {
     return RMAV_OK;
 }
 
+// What launch_policy_call feeds a ranged handle's kernels when the caller passed none: identity tables (allocated once) ...
+int ensure_ident_norm(rmav_handle h) {
+    if (h->ident_norm) return RMAV_OK;
+    float tab[kNormWords] = {};
+    for (int c = 0; c < 16; ++c) tab[16 + c] = 1.0f;
+    tab[32] = INFINITY;
+    if (hipMalloc((void **)&h->ident_norm, sizeof(tab)) != hipSuccess) {
+        (void)hipGetLastError();
+        h->ident_norm = nullptr;
+        return rmav_fail(RMAV_ERR_ALLOC, "device allocation of the identity tables failed");
+    }
+    HIP_TRY(hipMemcpyAsync(h->ident_norm, tab, sizeof(tab), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (tab is on this stack frame)
+    return RMAV_OK;
+}
+// ... and, on a time-limited handle, a boot_out nobody reads (grown on demand, to exactly `bytes`)
+int ensure_boot_scratch(rmav_handle h, size_t bytes) {
+    if (bytes <= h->boot_scratch_bytes) return RMAV_OK;
+    if (h->boot_scratch) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipFree(h->boot_scratch));
+        h->boot_scratch = nullptr;
+        h->boot_scratch_bytes = 0;
+    }
+    if (hipMalloc((void **)&h->boot_scratch, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->boot_scratch = nullptr;
+        return rmav_fail(RMAV_ERR_ALLOC, "device allocation of %zu bytes for the unused bootstrap terms failed", bytes);
+    }
+    h->boot_scratch_bytes = bytes;
+    return RMAV_OK;
+}
+
 // Host-pointer calls that move at most this many bytes go through the pinned block (zero-copy); bigger ones
 // stage through device scratch with hipMemcpyAsync, which is the faster route for bulk data.
 constexpr size_t kPinnedMax = 256u << 10;
@@ -1231,9 +1264,12 @@ int rmav_pack_policy_f16(rmav_handle h, int n_params, const float *const *params
 }
 
 // ---- rmav_rollout_policy / _boot / _norm: the checks all three make, in the order they make them, and the launch ------------------
-// the actors with time-limited (and *_boot, *_nrm) kernels; the fp32 vector-ALU and bf16 actors have none
-static bool limit_capable(int precision) {
-    return precision == RMAV_POLICY_FP32_MFMA || precision == RMAV_POLICY_F16_MFMA || precision == RMAV_POLICY_F16_SHARED;
+// The refusal of an actor without variant kernels (policy_has_variants, rmav_handle.hpp): `who` = the entry point or the handle's feature,
+// `what` = the kind of kernel the fp32 vector-ALU and bf16 actors lack.  RMAV_OK for the three actors that have them.
+static int need_variants(int precision, const char *who, const char *what) {
+    if (policy_has_variants(policy_kmode(precision))) return RMAV_OK;
+    return rmav_fail(RMAV_ERR_INVALID, "%s runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
+                                       "(the fp32 vector-ALU and bf16 actors have no %s kernel), got precision %d", who, what, precision);
 }
 // boot_out: checked (and named) only when the entry point requires it
 static int check_policy_args(int32_t n_steps, const float *weights, const float *logp_out, const float *value_out, bool need_boot, const float *boot_out) {
@@ -1256,11 +1292,6 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
     a.policy_w = weights;
     a.logp_out = logp_out;
     a.val_out = value_out;
-    const int kmode = precision == RMAV_POLICY_FP32        ? (int)RMAV_ACT_POLICY
-                      : precision == RMAV_POLICY_BF16_MFMA ? (int)RMAV_ACT_POLICY_BF16
-                      : precision == RMAV_POLICY_F16_MFMA  ? (int)ACT_POLICY_F16
-                      : precision == RMAV_POLICY_F16_SHARED ? (int)ACT_POLICY_F16_SHARED
-                                                           : (int)ACT_POLICY_F32M;
     h->xchg.allow = true;
     // A handle with a parameter range runs ONE ranged kernel per actor, the normalised one: a call without
     // statistics gets identity tables - z then has the bits of x (rmav_ppo.h) - and a call on a time-limited handle that asked for no
@@ -1268,46 +1299,19 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
     BootArgs bt_r{};
     NormArgs nm_r{};
     if (h->range_mask) {
-        if (!limit_capable(precision))
-            return rmav_fail(RMAV_ERR_INVALID, "a handle with a parameter range runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or "
-                                               "RMAV_POLICY_F16_SHARED (the fp32 vector-ALU and bf16 actors have no ranged kernel)");
+        if (int rc = need_variants(precision, "a handle with a parameter range", "ranged")) return rc;
         if (!nm) {
-            if (!h->ident_norm) {
-                float tab[kNormWords] = {};
-                for (int c = 0; c < 16; ++c) tab[16 + c] = 1.0f;
-                tab[32] = INFINITY;
-                if (hipMalloc((void **)&h->ident_norm, sizeof(tab)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    h->ident_norm = nullptr;
-                    return rmav_fail(RMAV_ERR_ALLOC, "device allocation of the identity tables failed");
-                }
-                HIP_TRY(hipMemcpyAsync(h->ident_norm, tab, sizeof(tab), hipMemcpyHostToDevice, h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));   // (tab is on this stack frame)
-            }
+            if (int rc = ensure_ident_norm(h)) return rc;
             nm_r.tab = h->ident_norm;
             nm = &nm_r;
         }
         if (h->time_limit > 0 && !bt) {
-            const size_t need = (size_t)n_steps * (size_t)h->n * sizeof(float);
-            if (need > h->boot_scratch_bytes) {
-                if (h->boot_scratch) {
-                    HIP_TRY(hipStreamSynchronize(h->stream));
-                    HIP_TRY(hipFree(h->boot_scratch));
-                    h->boot_scratch = nullptr;
-                    h->boot_scratch_bytes = 0;
-                }
-                if (hipMalloc((void **)&h->boot_scratch, need) != hipSuccess) {
-                    (void)hipGetLastError();
-                    h->boot_scratch = nullptr;
-                    return rmav_fail(RMAV_ERR_ALLOC, "device allocation of %zu bytes for the unused bootstrap terms failed", need);
-                }
-                h->boot_scratch_bytes = need;
-            }
+            if (int rc = ensure_boot_scratch(h, (size_t)n_steps * (size_t)h->n * sizeof(float))) return rc;
             bt_r.boot_out = h->boot_scratch;
             bt = &bt_r;
         }
     }
-    if (int rc = rmav_launch_policy_rollout(h, kmode, a, bt, nm)) return rc;
+    if (int rc = rmav_launch_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
     h->t += (uint64_t)n_steps;
     return RMAV_OK;
 }
@@ -1319,9 +1323,8 @@ int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, fl
     if (precision < RMAV_POLICY_FP32 || precision > RMAV_POLICY_F16_SHARED)
         return rmav_fail(RMAV_ERR_INVALID, "precision must be one of RMAV_POLICY_FP32 ... RMAV_POLICY_F16_SHARED (rmav_policy_precision)");
     if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
-    if (h->time_limit > 0 && !limit_capable(precision))
-        return rmav_fail(RMAV_ERR_INVALID, "a time-limited handle runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
-                                           "(the fp32 vector-ALU and bf16 actors have no time-limited kernel)");
+    if (h->time_limit > 0)
+        if (int rc = need_variants(precision, "a time-limited handle", "time-limited")) return rc;
     return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, nullptr, nullptr);
 }
 
@@ -1349,9 +1352,7 @@ int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weight
         return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap");
     if (h->time_limit <= 0)
         return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot needs an episode time limit on the handle (rmav_set_time_limit)");
-    if (!limit_capable(precision))
-        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
-                                           "(the fp32 vector-ALU and bf16 actors have no time-limited kernel), got precision %d", precision);
+    if (int rc = need_variants(precision, "rmav_rollout_policy_boot", "time-limited")) return rc;
     if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, true, boot_out)) return rc;
     const BootArgs bt{boot_out, trunc_out};
     return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, nullptr);
@@ -1768,9 +1769,7 @@ int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weight
                              int precision) {
     CHECK_HANDLE(h);
     if (int rc = check_norm_handle(h, "rmav_rollout_policy_norm")) return rc;
-    if (!limit_capable(precision))
-        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_norm runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
-                                           "(the fp32 vector-ALU and bf16 actors have no normalised kernel), got precision %d", precision);
+    if (int rc = need_variants(precision, "rmav_rollout_policy_norm", "normalised")) return rc;
     if (int rc = check_stats(stats)) return rc;
     if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
     if (h->time_limit > 0 && !boot_out)

@@ -218,6 +218,23 @@ template <int K> RMAV_INTERNAL inline KindParams<K> kind_params(const rmav_env_s
     return {rmav::derive_env<K>(h->params), rmav::derive<double>(h->params, h->kind == RMAV_QUAD2D || h->kind == RMAV_QUAD2D_SL)};
 }
 
+// The policy actors.  policy_kmode: the kernel mode of an rmav_policy_precision, -1 for a value outside the enum.
+// policy_has_variants: THE capability rule - the fp32-MFMA actor, the f16 pair and the shared-trunk pair have *_tl / *_boot / *_nrm / *_dr
+// kernels (on a quadrotor kind); the fp32 vector-ALU and bf16 actors have the plain kernel only.
+constexpr int policy_kmode(int precision) {
+    switch (precision) {
+    case RMAV_POLICY_FP32: return RMAV_ACT_POLICY;
+    case RMAV_POLICY_BF16_MFMA: return RMAV_ACT_POLICY_BF16;
+    case RMAV_POLICY_FP32_MFMA: return rmav::ACT_POLICY_F32M;
+    case RMAV_POLICY_F16_MFMA: return rmav::ACT_POLICY_F16;
+    case RMAV_POLICY_F16_SHARED: return rmav::ACT_POLICY_F16_SHARED;
+    }
+    return -1;
+}
+constexpr bool policy_has_variants(int kmode) {
+    return kmode == rmav::ACT_POLICY_F32M || kmode == rmav::ACT_POLICY_F16 || kmode == rmav::ACT_POLICY_F16_SHARED;
+}
+
 // rmav_policy_abi.hip: launches the kernel of rmav_rollout_policy / _boot / _norm for kmode = RMAV_ACT_POLICY | RMAV_ACT_POLICY_BF16 |
 // ACT_POLICY_F32M | ACT_POLICY_F16 | ACT_POLICY_F16_SHARED on the handle's stream.
 // bt (rmav_rollout_policy_boot): the launch also leaves the bootstrap term of its truncated steps - the *_boot kernels; nullptr otherwise.

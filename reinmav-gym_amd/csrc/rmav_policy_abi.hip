@@ -30,34 +30,42 @@ inline TimeLimitArgs variant_tl(rmav_handle h) { return h->time_limit > 0 ? tl_a
 inline BootArgs variant_boot(rmav_handle h, const BootArgs *bt) { return (h->time_limit > 0 && bt) ? *bt : BootArgs{}; }
 constexpr size_t kNormBytes = sizeof(float) * kNormWords;   // the *_nrm kernels' tables, in LDS behind the weights
 
+// ---- the three actor families -------------------------------------------------------------------------------------------------------
+// A family names its kernels once - plain(), tl(), boot(), nrm<BOOT>, dr<BOOT>: the seven slots - and says what differs between the
+// families around them: envs behind one arrival word, the workgroup (pairs sharing one LDS copy of the weights, envs, threads), the LDS
+// bytes, and how the *_nrm / *_dr kernels take the tables and the range.  kVariants = false: the plain kernel is the only one.
+struct Workgroup {
+    int pairs;
+    int64_t envs;
+    unsigned threads;
+};
+struct VariantArgs {   // what the kernels take behind (a, p, pc); nm is set in the nrm / dr slots
+    rmav_handle h;
+    RolloutArgs &a;
+    TimeLimitArgs tl;
+    BootArgs b;
+    const NormArgs *nm;
+};
+
 // one wavefront per 64 envs (32 for the fp32-MFMA actor: both half-waves work on the same 32 envs)
 // (time-limited handles: k_rollout_tl, ACT_POLICY_F32M only - rmav_rollout_policy refuses the other one-wavefront actors)
-template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
-    RolloutArgs a = a_in;
-    take_armed_exchange(h, a, MODE == ACT_POLICY_F32M ? 32 : 64);
-    const KindParams<K> kp = kind_params<K>(h);
-    const size_t lds = sizeof(float) * (MODE == ACT_POLICY ? (size_t)PolicyLayout<Dims<K>::NS>::TOTAL
-                                        : MODE == ACT_POLICY_BF16 ? (size_t)MfmaLayout::TOTAL : (size_t)Mfma32Layout::TOTAL);
-    const int64_t per_wg = MODE == ACT_POLICY_F32M ? block_size(h) / 2 : block_size(h);
-    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(block_size(h));
-    PolicyVariant v = V_PLAIN;
-    if constexpr (K != REINMAV && MODE == ACT_POLICY_F32M) {
-        v = policy_variant(h, bt, nm);
-        const TimeLimitArgs tl = variant_tl(h);
-        const BootArgs b = variant_boot(h, bt);
-        if (nm) a.act_in = nm->tab;   // (k_rollout_nrm takes the tables there: see the kernel)
-        // a handle with a parameter range: the ranged *_nrm kernels (rmav_abi.hip hands every such call statistics and, with a limit, a boot_out)
-        if (h->range_mask && v == V_NRM) hipLaunchKernelGGL((k_rollout_nrm_dr<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, (const RangeArgs *)h->range_dev);
-        else if (h->range_mask && v == V_NRM_BOOT) hipLaunchKernelGGL((k_rollout_nrm_dr<K, true>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, (const RangeArgs *)h->range_dev);
-        else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
-        else if (v == V_TL) hipLaunchKernelGGL((k_rollout_tl<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
-        else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_boot<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl, b);
-        else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b);
-        else if (v == V_NRM_BOOT) hipLaunchKernelGGL((k_rollout_nrm<K, true>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b);
+template <int KIND, int MODE> struct OneWave {
+    static constexpr int K = KIND, kEnvsPerWord = MODE == ACT_POLICY_F32M ? 32 : 64;
+    static constexpr bool kVariants = K != REINMAV && MODE == ACT_POLICY_F32M;
+    static Workgroup workgroup(rmav_handle h) { return {1, MODE == ACT_POLICY_F32M ? block_size(h) / 2 : block_size(h), (unsigned)block_size(h)}; }
+    static size_t lds_bytes(int, bool, bool tables) {
+        return sizeof(float) * (MODE == ACT_POLICY ? (size_t)PolicyLayout<Dims<K>::NS>::TOTAL
+                                : MODE == ACT_POLICY_BF16 ? (size_t)MfmaLayout::TOTAL : (size_t)Mfma32Layout::TOTAL) + (tables ? kNormBytes : 0);
     }
-    if (v == V_PLAIN) hipLaunchKernelGGL((k_rollout<K, MODE, ST_DEFAULT>), grid, block, lds, h->stream, a, kp.p, kp.pc);
-    return check_rollout_launch(h, a);
-}
+    static auto plain() { return k_rollout<K, MODE, ST_DEFAULT>; }
+    static auto tl() { return k_rollout_tl<K, MODE, ST_DEFAULT>; }
+    static auto boot() { return k_rollout_boot<K, MODE, ST_DEFAULT>; }
+    // the tables travel in RolloutArgs::act_in and the range by device pointer (see the kernels)
+    template <bool BOOT, typename Go> static void nrm(Go go, const VariantArgs &v) { v.a.act_in = v.nm->tab, go(k_rollout_nrm<K, BOOT>, v.tl, v.b); }
+    template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) {
+        v.a.act_in = v.nm->tab, go(k_rollout_nrm_dr<K, BOOT>, v.tl, v.b, (const RangeArgs *)v.h->range_dev);
+    }
+};
 
 // The matrix-core actors as (actor, critic) wavefront pairs (rmav_policy_pair.hpp).  Pairs per workgroup: the pairs of a
 // workgroup share one LDS copy of the weights (30 KB) but also one s_barrier; RMAV_TUNE_PAIR_GROUP = 1 .. 4 overrides.
@@ -66,82 +74,81 @@ template <int K, int MODE> int launch_policy_1w(rmav_handle h, const RolloutArgs
 static_assert(pair_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + kNormBytes <= (160u << 10) &&
                   shared_boot_lds_bytes<QUAD3D_SL>(kPairGroupMax) + kNormBytes <= (160u << 10),
               "the hand-over tiles with their terminal-state areas must fit one workgroup's LDS");
-inline int pairs_per_workgroup(rmav_handle h, int measured) {
+inline Workgroup pairs_per_workgroup(rmav_handle h, int measured) {
     const int forced = h->tune[RMAV_TUNE_PAIR_GROUP];
-    return (forced >= 1 && forced <= kPairGroupMax) ? forced : measured;
+    const int g = (forced >= 1 && forced <= kPairGroupMax) ? forced : measured;
+    return {g, 64 * g, 128u * g};
 }
-template <int K, int FMT> int launch_rollout_pair(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
-    RolloutArgs a = a_in;
-    take_armed_exchange(h, a, 64);
-    const KindParams<K> kp = kind_params<K>(h);
+template <int KIND, int FMT> struct Pair {   // (time-limited handles: RMAV_POLICY_F16_MFMA only)
+    static constexpr int K = KIND, kEnvsPerWord = 64;
+    static constexpr bool kVariants = K != REINMAV && FMT == FMT_F16;
     // measured (profiles/r04/actor_bench.txt, quadrotor3d x 32 steps): 65 536 envs 4 pairs 15.0 G env-steps/s, 2 pairs 14.1, 1 pair 13.7
     // (one workgroup per CU, weights staged once per CU); 131 072 envs 2 pairs 15.8 - 16.7, 4 pairs 15.5 - 16.3, 1 pair 11.1
-    const int g = pairs_per_workgroup(h, h->n <= 98304 ? 4 : 2);
-    const int64_t per_wg = 64 * g;
-    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
-    PolicyVariant v = V_PLAIN;
-    if constexpr (K != REINMAV && FMT == FMT_F16) {   // (time-limited handles: RMAV_POLICY_F16_MFMA only)
-        v = policy_variant(h, bt, nm);
-        const TimeLimitArgs tl = variant_tl(h);
-        const BootArgs b = variant_boot(h, bt);
-        const size_t lds = pair_lds_bytes<K>(g), lds_boot = pair_boot_lds_bytes<K>(g);
-        if (h->range_mask && v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_dr<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
-        else if (h->range_mask && v == V_NRM_BOOT)
-            hipLaunchKernelGGL((k_rollout_pair_dr<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
-        else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
-        else if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_tl<K, FMT>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
-        else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_pair_boot<K, FMT>), grid, block, lds_boot, h->stream, a, kp.p, kp.pc, tl, b);
-        else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
-        else if (v == V_NRM_BOOT)
-            hipLaunchKernelGGL((k_rollout_pair_nrm<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
-    }
-    if (v == V_PLAIN) hipLaunchKernelGGL((k_rollout_pair<K, FMT>), grid, block, pair_lds_bytes<K>(g), h->stream, a, kp.p, kp.pc);
-    return check_rollout_launch(h, a);
-}
+    static Workgroup workgroup(rmav_handle h) { return pairs_per_workgroup(h, h->n <= 98304 ? 4 : 2); }
+    static size_t lds_bytes(int g, bool boot_tiles, bool tables) { return (boot_tiles ? pair_boot_lds_bytes<K>(g) : pair_lds_bytes<K>(g)) + (tables ? kNormBytes : 0); }
+    static auto plain() { return k_rollout_pair<K, FMT>; }
+    static auto tl() { return k_rollout_pair_tl<K, FMT>; }
+    static auto boot() { return k_rollout_pair_boot<K, FMT>; }
+    template <bool BOOT, typename Go> static void nrm(Go go, const VariantArgs &v) { go(k_rollout_pair_nrm<K, BOOT>, v.tl, v.b, *v.nm); }
+    template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) { go(k_rollout_pair_dr<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h)); }
+};
 
 // RMAV_POLICY_F16_SHARED: one trunk, both wavefronts of a pair evaluate it for one 32-env column tile each (k_rollout_pair_shared)
-template <int K> int launch_rollout_pair_shared(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
-    RolloutArgs a = a_in;
-    take_armed_exchange(h, a, 64);
-    const KindParams<K> kp = kind_params<K>(h);
+template <int KIND> struct SharedPair {
+    static constexpr int K = KIND, kEnvsPerWord = 64;
+    static constexpr bool kVariants = K != REINMAV;
     // measured (profiles/r04/actor_bench.txt): 65 536 envs 1 / 2 / 4 pairs per workgroup 20.8 / 21.5 / 20.4 G env-steps/s, 131 072: 19.9 / 25.9 / 26.1
-    const int g = pairs_per_workgroup(h, 2);
-    const int64_t per_wg = 64 * g;
-    const dim3 grid((unsigned)((h->n + per_wg - 1) / per_wg)), block(128 * g);
+    static Workgroup workgroup(rmav_handle h) { return pairs_per_workgroup(h, 2); }
+    static size_t lds_bytes(int g, bool boot_tiles, bool tables) { return (boot_tiles ? shared_boot_lds_bytes<K>(g) : shared_lds_bytes<K>(g)) + (tables ? kNormBytes : 0); }
+    static auto plain() { return k_rollout_pair_shared<K>; }
+    static auto tl() { return k_rollout_pair_shared_tl<K>; }
+    static auto boot() { return k_rollout_pair_shared_boot<K>; }
+    template <bool BOOT, typename Go> static void nrm(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_nrm<K, BOOT>, v.tl, v.b, *v.nm); }
+    template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_dr<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h)); }
+};
+
+// ---- the one ladder: which of family F's kernels this launch runs, with which LDS size and trailing arguments ---------------------------
+template <typename F> int launch_family(rmav_handle h, const RolloutArgs &a_in, const BootArgs *bt, const NormArgs *nm) {
+    RolloutArgs a = a_in;
+    take_armed_exchange(h, a, F::kEnvsPerWord);
+    const KindParams<F::K> kp = kind_params<F::K>(h);
+    const Workgroup wg = F::workgroup(h);
+    const dim3 grid((unsigned)((h->n + wg.envs - 1) / wg.envs)), block(wg.threads);
+    // go(boot tiles?)(kernel, trailing arguments...): a is read at the launch (OneWave::nrm / dr set its act_in first)
+    const auto go = [&](bool boot_tiles) {
+        return [&, lds = F::lds_bytes(wg.pairs, boot_tiles, nm != nullptr)](auto kernel, const auto &...tail) {
+            hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, a, kp.p, kp.pc, tail...);
+        };
+    };
     PolicyVariant v = V_PLAIN;
-    if constexpr (K != REINMAV) {
+    if constexpr (F::kVariants) {
         v = policy_variant(h, bt, nm);
-        const TimeLimitArgs tl = variant_tl(h);
-        const BootArgs b = variant_boot(h, bt);
-        const size_t lds = shared_lds_bytes<K>(g), lds_boot = shared_boot_lds_bytes<K>(g);
-        if (h->range_mask && v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_shared_dr<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
-        else if (h->range_mask && v == V_NRM_BOOT)
-            hipLaunchKernelGGL((k_rollout_pair_shared_dr<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm, range_args(h));
+        const VariantArgs va{h, a, variant_tl(h), variant_boot(h, bt), nm};
+        // a handle with a parameter range: the ranged *_nrm kernels (rmav_abi.hip hands every such call statistics and, with a limit, a boot_out)
+        if (h->range_mask && v == V_NRM) F::template dr<false>(go(false), va);
+        else if (h->range_mask && v == V_NRM_BOOT) F::template dr<true>(go(true), va);
         else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
-        else if (v == V_TL) hipLaunchKernelGGL((k_rollout_pair_shared_tl<K>), grid, block, lds, h->stream, a, kp.p, kp.pc, tl);
-        else if (v == V_BOOT) hipLaunchKernelGGL((k_rollout_pair_shared_boot<K>), grid, block, lds_boot, h->stream, a, kp.p, kp.pc, tl, b);
-        else if (v == V_NRM) hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, false>), grid, block, lds + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
-        else if (v == V_NRM_BOOT)
-            hipLaunchKernelGGL((k_rollout_pair_shared_nrm<K, true>), grid, block, lds_boot + kNormBytes, h->stream, a, kp.p, kp.pc, tl, b, *nm);
+        else if (v == V_TL) go(false)(F::tl(), va.tl);
+        else if (v == V_BOOT) go(true)(F::boot(), va.tl, va.b);
+        else if (v == V_NRM) F::template nrm<false>(go(false), va);
+        else if (v == V_NRM_BOOT) F::template nrm<true>(go(true), va);
     }
-    if (v == V_PLAIN) hipLaunchKernelGGL((k_rollout_pair_shared<K>), grid, block, shared_lds_bytes<K>(g), h->stream, a, kp.p, kp.pc);
+    if (v == V_PLAIN) go(false)(F::plain());
     return check_rollout_launch(h, a);
 }
 
 template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs *nm) {
     // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
-    if (nm && (K == REINMAV || (kmode != ACT_POLICY_F32M && kmode != ACT_POLICY_F16 && kmode != ACT_POLICY_F16_SHARED)))
-        return rmav_fail(RMAV_ERR_INVALID, "no normalised kernel for policy mode %d", kmode);
-    if (h->range_mask && (K == REINMAV || (kmode != ACT_POLICY_F32M && kmode != ACT_POLICY_F16 && kmode != ACT_POLICY_F16_SHARED)))
-        return rmav_fail(RMAV_ERR_INVALID, "no ranged kernel for policy mode %d", kmode);
+    if ((nm || h->range_mask) && (K == REINMAV || !policy_has_variants(kmode)))
+        return rmav_fail(RMAV_ERR_INVALID, "no %s kernel for policy mode %d", nm ? "normalised" : "ranged", kmode);
     switch (kmode) {
-    case RMAV_ACT_POLICY: return launch_policy_1w<K, ACT_POLICY>(h, a, nullptr, nullptr);
+    case RMAV_ACT_POLICY: return launch_family<OneWave<K, ACT_POLICY>>(h, a, nullptr, nullptr);
     case RMAV_ACT_POLICY_BF16:
-        return h->tune[RMAV_TUNE_POLICY_PAIR] == 0 ? launch_policy_1w<K, ACT_POLICY_BF16>(h, a, nullptr, nullptr)
-                                                   : launch_rollout_pair<K, FMT_BF16>(h, a, nullptr, nullptr);
-    case ACT_POLICY_F32M: return launch_policy_1w<K, ACT_POLICY_F32M>(h, a, bt, nm);
-    case ACT_POLICY_F16: return launch_rollout_pair<K, FMT_F16>(h, a, bt, nm);
-    case ACT_POLICY_F16_SHARED: return launch_rollout_pair_shared<K>(h, a, bt, nm);
+        return h->tune[RMAV_TUNE_POLICY_PAIR] == 0 ? launch_family<OneWave<K, ACT_POLICY_BF16>>(h, a, nullptr, nullptr)
+                                                   : launch_family<Pair<K, FMT_BF16>>(h, a, nullptr, nullptr);
+    case ACT_POLICY_F32M: return launch_family<OneWave<K, ACT_POLICY_F32M>>(h, a, bt, nm);
+    case ACT_POLICY_F16: return launch_family<Pair<K, FMT_F16>>(h, a, bt, nm);
+    case ACT_POLICY_F16_SHARED: return launch_family<SharedPair<K>>(h, a, bt, nm);
     }
     return rmav_fail(RMAV_ERR_INVALID, "unknown policy mode %d", kmode);
 }

@@ -232,6 +232,17 @@ def _rowmap(s: int, h: int, j: int) -> int:
     return 32 * (s >> 1) + (r & 3) + 8 * (r >> 2) + 4 * h
 
 
+# The in-kernel actors: name -> (rmav_policy_precision constant of _abi, the library's weight count, has *_tl / *_boot / *_nrm / *_dr
+# kernels).  FusedPolicyCollector resolves its keyword arguments and the policy's architecture to one of these names, once.
+_ACTORS = {
+    "fp32": ("POLICY_FP32", lambda L, kind: L.rmav_policy_weight_count(kind), False),          # fp32 FMAs on the vector ALU
+    "fp32_mfma": ("POLICY_FP32_MFMA", lambda L, kind: L.rmav_policy_weight_count_f32_mfma(), True),
+    "bf16": ("POLICY_BF16_MFMA", lambda L, kind: L.rmav_policy_weight_count_bf16(), False),
+    "f16": ("POLICY_F16_MFMA", lambda L, kind: L.rmav_policy_weight_count_bf16(), True),
+    "f16_shared": ("POLICY_F16_SHARED", lambda L, kind: L.rmav_policy_weight_count_shared(), True),   # one trunk, two heads
+}
+
+
 class _PolicyPacker:
     """Packs an ``MlpPolicy`` into the weight buffer ``rmav_rollout_policy`` reads (layouts in include/rmav.h).
 
@@ -241,18 +252,17 @@ class _PolicyPacker:
 
     K_TANH = 2.8853900817779268   # 2 log2(e): the f16 actor's layer-2 fragments carry -2 k W2, layer 3's -2 W3 (include/rmav.h)
 
-    def __init__(self, policy: MlpPolicy, n_obs: int, bf16_mfma: bool, f32_mfma: bool = False, f16_mfma: bool = False):
+    def __init__(self, policy: MlpPolicy, n_obs: int, actor: str):
+        """``actor``: a key of ``_ACTORS``."""
         import numpy as np
 
         H = policy.pi[0].out_features
         assert H == 64 and policy.pi[1].in_features == 64, "the in-kernel policy is the 2 x 64 baselines mlp"
         assert n_obs <= 16
-        # f16: the bf16 fragment layout with f16 pairs (and the tanh fold's weight scales)
-        self.f16 = bool(f16_mfma)
-        self.shared = bool(getattr(policy, "shared", False))
-        assert not self.shared or self.f16, "the shared-trunk policy runs on the f16 actor only (RMAV_POLICY_F16_SHARED)"
-        self.policy, self.bf16, self.f32m = policy, bool(bf16_mfma) or self.f16, bool(f32_mfma)
-        assert not (self.bf16 and self.f32m)
+        assert actor in _ACTORS, actor
+        assert bool(getattr(policy, "shared", False)) == (actor == "f16_shared"), "the shared-trunk policy runs on RMAV_POLICY_F16_SHARED, and only it"
+        # fragments: the MFMA fragment layout of bf16 pairs - or (f16) of f16 pairs with the tanh fold's weight scales
+        self.policy, self.shared, self.f16, self.fragments = policy, actor == "f16_shared", actor.startswith("f16"), actor in ("bf16", "f16", "f16_shared")
         if self.shared:
             self._init_shared(policy, n_obs)
             return
@@ -273,7 +283,7 @@ class _PolicyPacker:
             return int(offs[6 * net + 2 * layer + 1]) + r if r < p.numel() else ZERO
 
         logstd = [int(offs[12]) + c if c < n_act else ZERO for c in range(4)]
-        if self.f32m:   # A operands of v_mfma_f32_32x32x2_f32 (include/rmav.h, csrc/rmav_policy_mfma32.hpp)
+        if actor == "fp32_mfma":   # A operands of v_mfma_f32_32x32x2_f32 (include/rmav.h, csrc/rmav_policy_mfma32.hpp)
             def row(r, h):
                 return (r & 3) + 8 * (r >> 2) + 4 * h
 
@@ -293,7 +303,7 @@ class _PolicyPacker:
             idx += logstd
             self.idx_f32 = torch.tensor(idx, dtype=torch.int64, device=policy.logstd.device)
             self.n_out = len(idx)
-        elif not self.bf16:
+        elif not self.fragments:
             nsp = (n_obs + 3) // 4 * 4
             idx = []
             for net in range(2):
@@ -376,7 +386,7 @@ class _PolicyPacker:
                 fr, bi = self.idx_frag.to(torch.int32), self.idx_bias.to(torch.int32)
                 lo = torch.cat([fr[0::2], bi])
                 hi = torch.cat([fr[1::2], torch.full((bi.numel(),), -1, dtype=torch.int32, device=dev)])
-            elif self.f32m or not self.bf16:
+            elif not self.fragments:
                 lo = self.idx_f32.to(torch.int32)
                 hi = torch.full_like(lo, -1)
             else:
@@ -411,7 +421,7 @@ class _PolicyPacker:
             if self.shared:
                 fr = (flat[self.idx_frag] * self.frag_scale).to(torch.float16).view(torch.int16).view(torch.float32)
                 res = torch.cat([fr, flat[self.idx_bias]])
-            elif self.f32m or not self.bf16:
+            elif not self.fragments:
                 res = flat[self.idx_f32]
             else:
                 if self.f16:
@@ -429,25 +439,25 @@ class _PolicyPacker:
 
 def pack_policy_weights(policy: MlpPolicy, n_obs: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 layout: per net  W1 [64][NSP] | b1 | W2^T [64][64] | b2 | W3^T [64][4] | b3 [4],  then logstd [4]."""
-    return _PolicyPacker(policy, n_obs, False).pack(out)
+    return _PolicyPacker(policy, n_obs, "fp32").pack(out)
 
 
 def pack_policy_weights_f32_mfma(policy: MlpPolicy, n_obs: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 A operands of v_mfma_f32_32x32x2_f32: per net A1 [2][2][64][4] | A2 [2][2][4][64][4] | W3 [2][4][32] |
     b1 [64] | b2 [64] | b3 [4], then logstd [4] (include/rmav.h)."""
-    return _PolicyPacker(policy, n_obs, False, f32_mfma=True).pack(out)
+    return _PolicyPacker(policy, n_obs, "fp32_mfma").pack(out)
 
 
 def pack_policy_weights_bf16(policy: MlpPolicy, n_obs: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 MFMA fragments: per net A1 [2][64][8] | A2 [2][4][64][8] | A3 [4][64][8] (bf16) | b1 [64] | b2 [64] |
     b3 [32] (fp32), then logstd [4]."""
-    return _PolicyPacker(policy, n_obs, True).pack(out)
+    return _PolicyPacker(policy, n_obs, "bf16").pack(out)
 
 
 def pack_policy_weights_f16(policy: MlpPolicy, n_obs: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """f16 MFMA fragments in the bf16 layout, layers 2 / 3 pre-scaled by -2 * 2 log2(e) / -2 (tanh folded into the next
     layer: the kernel hands (1 - tanh z) / 2 on and derives the matching biases from these rounded weights)."""
-    return _PolicyPacker(policy, n_obs, False, f16_mfma=True).pack(out)
+    return _PolicyPacker(policy, n_obs, "f16_shared" if getattr(policy, "shared", False) else "f16").pack(out)
 
 
 class FusedPolicyCollector:
@@ -472,36 +482,39 @@ class FusedPolicyCollector:
         required there."""
         import ctypes as C
 
-        assert not (bf16_mfma and f16_mfma)
-        shared = bool(getattr(policy, "shared", False))
-        if shared:   # one trunk, two heads: RMAV_POLICY_F16_SHARED (the only actor of that architecture)
-            assert not bf16_mfma and not f32_mfma, "a shared-trunk policy runs on the f16 actor"
-            f16_mfma = True
-        if f32_mfma is None:
-            f32_mfma = not (bf16_mfma or f16_mfma)
-
         from . import _abi as A
 
+        assert not (bf16_mfma and f16_mfma) and not (f32_mfma and (bf16_mfma or f16_mfma))
+        if getattr(policy, "shared", False):   # one trunk, two heads: RMAV_POLICY_F16_SHARED (the only actor of that architecture)
+            assert not bf16_mfma and not f32_mfma, "a shared-trunk policy runs on the f16 actor"
+            actor = "f16_shared"
+        else:
+            actor = "f16" if f16_mfma else "bf16" if bf16_mfma else "fp32" if f32_mfma is not None and not f32_mfma else "fp32_mfma"
+        precision, weight_count, has_variants = _ACTORS[actor]
+
+        def refuse(feature, kernel):
+            raise ValueError(f"{feature} runs the fp32 matrix-core actor (the default), f16_mfma=True or a shared-trunk policy: "
+                             f"the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no {kernel} kernel")
+
         assert env.auto_reset, "rollouts need VecEnv semantics (auto-reset)"
-        if getattr(env, "max_episode_steps", None) and (bf16_mfma or not (f32_mfma or f16_mfma)):
-            raise ValueError("an env with max_episode_steps runs the fp32 matrix-core actor (the default), f16_mfma=True or a "
-                             "shared-trunk policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no time-limited kernel")
-        if (bf16_mfma or not (f32_mfma or f16_mfma)) and hasattr(env, "get_env_param_range") and any(
-                env.get_env_param_range(nm) for nm in ("mass", "load_mass", "tether_length")):
-            raise ValueError("an env with randomize= / set_env_param_range runs the fp32 matrix-core actor (the default), f16_mfma=True or a "
-                             "shared-trunk policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no ranged kernel")
+        limited = bool(getattr(env, "max_episode_steps", None))
         norm = getattr(policy, "obs_norm", None)
+        if not has_variants:
+            if limited:
+                refuse("an env with max_episode_steps", "time-limited")
+            if hasattr(env, "get_env_param_range") and any(env.get_env_param_range(nm) for nm in ("mass", "load_mass", "tether_length")):
+                refuse("an env with randomize= / set_env_param_range", "ranged")
+            if norm is not None:
+                refuse("a policy with obs_norm", "normalised")
         if norm is not None:
-            if bf16_mfma or not (f32_mfma or f16_mfma):
-                raise ValueError("a policy with obs_norm runs the fp32 matrix-core actor (the default), f16_mfma=True or a shared-trunk "
-                                 "policy: the fp32 vector-ALU (f32_mfma=False) and bf16 actors have no normalised kernel")
-            if getattr(env, "max_episode_steps", None) and not bootstrap_truncated:
+            if limited and not bootstrap_truncated:
                 raise ValueError("a policy with obs_norm on an env with max_episode_steps needs bootstrap_truncated=True "
                                  "(rmav_rollout_policy_norm always leaves the bootstrap term there)")
             if norm.buf.device != torch.device("cuda", env.device):
                 raise ValueError("policy.obs_norm must live on the env's device")
         self.env, self.policy, self.T = env, policy, int(nsteps)
-        self.bf16_mfma, self.f32_mfma, self.f16_mfma = bool(bf16_mfma), bool(f32_mfma), bool(f16_mfma)
+        self.actor = actor
+        self.bf16_mfma, self.f32_mfma, self.f16_mfma = actor == "bf16", actor == "fp32_mfma", actor in ("f16", "f16_shared")
         self._C, self._A = C, A
         dev = torch.device("cuda", env.device)
         N, nS, nA, T = env.num_envs, env.nS, env.nA, self.T
@@ -512,12 +525,10 @@ class FusedPolicyCollector:
         self.val = torch.empty((T + 1, N), **f32)
         self.rew = torch.empty((T, N), **f32)
         self.done = torch.empty((T, N), dtype=torch.uint8, device=dev)
-        n_w = (A.lib().rmav_policy_weight_count_shared() if shared else
-               A.lib().rmav_policy_weight_count_bf16() if (self.bf16_mfma or self.f16_mfma) else
-               A.lib().rmav_policy_weight_count_f32_mfma() if self.f32_mfma else A.lib().rmav_policy_weight_count(env.kind))
+        n_w = weight_count(A.lib(), env.kind)
         self.weights = torch.empty(n_w, **f32)
         assert self.weights.data_ptr() % 16 == 0
-        self._packer = _PolicyPacker(policy, env.nS, self.bf16_mfma, f32_mfma=self.f32_mfma, f16_mfma=self.f16_mfma)
+        self._packer = _PolicyPacker(policy, env.nS, actor)
         assert self._packer.n_out == n_w, (self._packer.n_out, n_w)
         self.obs[0].copy_(env.get_state(layout="soa", device_out=True))
         # The weight repack before every rollout: one gather launch behind the C ABI (rmav_pack_policy).  As ~8 dependent torch
@@ -532,13 +543,15 @@ class FusedPolicyCollector:
                 raise ValueError("bootstrap_truncated=True needs an env with max_episode_steps")
             self.boot = torch.empty((T, N), **f32)
             self.trunc = torch.empty((T, N), dtype=torch.uint8, device=dev)
-        self._call = (A.lib().rmav_rollout_policy_norm if norm is not None else
-                      A.lib().rmav_rollout_policy_boot if bootstrap_truncated else A.lib().rmav_rollout_policy,
-                      self.T, p(self.weights)) + ((C.c_void_p(norm.data_ptr()),) if norm is not None else ()) + (
-                      p(self.act), p(self.obs[1:]), p(self.rew), p(self.done), p(self.logp), p(self.val)) + (
-                      (p(self.boot), p(self.trunc)) if bootstrap_truncated else (None, None) if norm is not None else ()) + (
-                      A.POLICY_F16_SHARED if shared else A.POLICY_F16_MFMA if self.f16_mfma else A.POLICY_BF16_MFMA if self.bf16_mfma
-                      else A.POLICY_FP32_MFMA if self.f32_mfma else A.POLICY_FP32,)
+        if norm is not None:
+            fn, stats = A.lib().rmav_rollout_policy_norm, (C.c_void_p(norm.data_ptr()),)
+            boot = (p(self.boot), p(self.trunc)) if bootstrap_truncated else (None, None)
+        elif bootstrap_truncated:
+            fn, stats, boot = A.lib().rmav_rollout_policy_boot, (), (p(self.boot), p(self.trunc))
+        else:
+            fn, stats, boot = A.lib().rmav_rollout_policy, (), ()
+        outs = (p(self.act), p(self.obs[1:]), p(self.rew), p(self.done), p(self.logp), p(self.val))
+        self._call = (fn, self.T, p(self.weights)) + stats + outs + boot + (getattr(A, precision),)
 
     def _pack(self):
         if self.native_pack:

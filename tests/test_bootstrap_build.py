@@ -1,71 +1,35 @@
 """Terminal observations and the bootstrap term of truncated steps, what can be checked without a GPU: the three entry points are
 declared, exported and bound, and the new kernels exist for the four quadrotor kinds with the resource budgets of the time-limited
 kernels they stand beside (`make asm`, as test_time_limit_build.py)."""
-import ctypes as C
 import os
-import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "reinmav-gym_amd")
-NEW = ("rmav_step_final", "rmav_rollout_policy_boot", "rmav_gae_boot")
+import buildinfo as B
+
+NEW = {"rmav_step_final": ("int", 9), "rmav_rollout_policy_boot": ("int", 12), "rmav_gae_boot": ("int", 12)}
 
 
 def test_bootstrap_entry_points_are_declared_exported_and_bound(built):
-    from gym_reinmav_amd import _abi as A
-
-    inc = os.path.join(ROOT, "include")
-    txt = "".join(open(os.path.join(inc, f)).read() for f in sorted(os.listdir(inc)) if f.endswith(".h"))
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    L = C.CDLL(A.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", txt), name
-        assert hasattr(L, name), name
-        assert name in A.PROTOTYPES, name
-    assert len(A.PROTOTYPES["rmav_step_final"][1]) == 9
-    assert len(A.PROTOTYPES["rmav_rollout_policy_boot"][1]) == 12
-    assert len(A.PROTOTYPES["rmav_gae_boot"][1]) == 12
-
-
-@pytest.fixture(scope="module")
-def usage():
-    subprocess.run(["make", "-s", "-C", PKG, "asm"], check=True)
-    txt = open(os.path.join(PKG, "build", "resource_usage.txt")).read()
-    out = {}
-    for b in re.split(r"remark: Function Name: ", txt)[1:]:
-        name = b.split(" ")[0]
-        out[name] = {k: int(re.search(pat, b).group(1)) for k, pat in (
-            ("vgpr", r"VGPRs: (\d+)"), ("agpr", r"AGPRs: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"),
-            ("spill", r"VGPRs Spill: (\d+)"), ("occ", r"Occupancy \[waves/SIMD\]: (\d+)"))}
-    return out
-
-
-def _hits(usage, prefix):
-    return {n: v for n, v in usage.items() if n.startswith(prefix)}
-
-
-def _clean(u):
-    return u["scratch"] == 0 and u["spill"] == 0
+    B.assert_entry_points(NEW)
 
 
 @pytest.mark.parametrize("kind", [0, 1, 2, 3])
-def test_single_step_final_kernels(usage, kind):
+def test_single_step_final_kernels(kind):
     """k_step_final<K, TL, ST>: with and without a limit, the three store policies; no scratch, no spills, and no more than two
     registers above the k_step_tl kernel of the same kind and store policy (the finishing lanes' store address)."""
     for tl in (0, 1):
-        hits = _hits(usage, f"_ZN4rmav12k_step_finalILi{kind}ELb{tl}E")
+        hits = B.hits(f"_ZN4rmav12k_step_finalILi{kind}ELb{tl}E")
         assert len(hits) == 3, (kind, tl, sorted(hits))
         for n, u in hits.items():
-            assert _clean(u), (n, u)
+            assert B.clean(u), (n, u)
     for st in (0, 1, 2):
-        u = next(iter(_hits(usage, f"_ZN4rmav12k_step_finalILi{kind}ELb1ELi{st}E").values()))
-        ref = next(iter(_hits(usage, f"_ZN4rmav9k_step_tlILi{kind}ELb0ELi{st}E").values()))
+        u = next(iter(B.hits(f"_ZN4rmav12k_step_finalILi{kind}ELb1ELi{st}E").values()))
+        ref = next(iter(B.hits(f"_ZN4rmav9k_step_tlILi{kind}ELb0ELi{st}E").values()))
         assert u["vgpr"] <= ref["vgpr"] + 2 and u["occ"] >= ref["occ"], (kind, st, u, ref)
 
 
-def test_fused_boot_kernels(usage):
+def test_fused_boot_kernels():
     """k_rollout_boot<K, ACT_POLICY_F32M>, k_rollout_pair_boot<K, FMT_F16>, k_rollout_pair_shared_boot<K>, K = 0..3: no scratch, no
     spills, VGPR + AGPR <= 256, the pair kernels two wavefronts per SIMD - and none below the occupancy of its time-limited sibling."""
     fam = (("_ZN4rmav14k_rollout_bootILi{k}ELi8ELi0E", "_ZN4rmav12k_rollout_tlILi{k}ELi8ELi0E", 1),
@@ -73,36 +37,26 @@ def test_fused_boot_kernels(usage):
            ("_ZN4rmav26k_rollout_pair_shared_bootILi{k}E", "_ZN4rmav24k_rollout_pair_shared_tlILi{k}E", 2))
     for new, old, min_occ in fam:
         for k in range(4):
-            h, o = _hits(usage, new.format(k=k)), _hits(usage, old.format(k=k))
+            h, o = B.hits(new.format(k=k)), B.hits(old.format(k=k))
             assert len(h) == 1 and len(o) == 1, (new, k, sorted(h), sorted(o))
             (n, u), ref = next(iter(h.items())), next(iter(o.values()))
-            assert u["vgpr"] + u["agpr"] <= 256 and _clean(u) and u["occ"] >= min_occ and u["occ"] >= ref["occ"], (n, u, ref)
+            assert u["vgpr"] + u["agpr"] <= 256 and B.clean(u) and u["occ"] >= min_occ and u["occ"] >= ref["occ"], (n, u, ref)
     # the matrix-core kernels keep the LDS permutes and compiler-packed fp32 out (the rule test_pair_time_limit_kernels applies to their siblings)
-    txt = open(os.path.join(PKG, "build", "rmav_policy_abi.gfx950.s")).read()
-    bodies = re.split(r"^(_ZN4rmav\w+):[^\n]*\n", txt, flags=re.M)
-    seen = 0
-    for name, body in zip(bodies[1::2], bodies[2::2]):
-        if not re.match(r"_ZN4rmav(19k_rollout_pair_boot|26k_rollout_pair_shared_boot|14k_rollout_bootILi\dELi8E)", name):
-            continue
-        seen += 1
-        body = body.split(".Lfunc_end")[0]
-        for bad in ("ds_bpermute", "ds_permute", "v_pk_mul_f32", "v_pk_mov_b32"):
-            assert bad not in body, (name, bad)
-    assert seen == 12, seen
+    B.assert_matrix_core_clean(r"_ZN4rmav(19k_rollout_pair_boot|26k_rollout_pair_shared_boot|14k_rollout_bootILi\dELi8E)", 12)
 
 
-def test_gae_boot_kernel(usage):
+def test_gae_boot_kernel():
     """k_gae_boot: k_gae with one more load stream - no scratch, no spills; k_gae itself is still there"""
-    new, old = _hits(usage, "_ZN4rmav10k_gae_bootE"), _hits(usage, "_ZN4rmav5k_gaeE")
+    new, old = B.hits("_ZN4rmav10k_gae_bootE"), B.hits("_ZN4rmav5k_gaeE")
     assert len(new) == 1 and len(old) == 1
     u = next(iter(new.values()))
-    assert _clean(u) and u["occ"] >= 2, u
+    assert B.clean(u) and u["occ"] >= 2, u
 
 
 def test_the_larger_tiles_fit_the_lds_budget():
     """LDS bytes of a 4-pair workgroup (the largest RMAV_TUNE_PAIR_GROUP) of the *_boot pair kernels for the 16-state kind, from the
     tile definitions of csrc/rmav_policy_pair.hpp: weights + 4 x (noise tile + 2 output rows + 2 terminal-state areas) <= 160 KiB."""
-    src = open(os.path.join(PKG, "csrc", "rmav_policy_pair.hpp")).read()
+    src = open(os.path.join(B.PKG, "csrc", "rmav_policy_pair.hpp")).read()
     assert "struct PairBootTile" in src and "struct SharedBootTile" in src
     ns, na, g = 16, 4, 4
     z_words = 2 * 4 * 64

@@ -219,15 +219,15 @@ def test_native_weight_pack_equals_the_torch_pack(G, kind):
     with torch.no_grad():
         for prm in pol.parameters():
             prm.add_(torch.randn_like(prm) * 0.3)
-    for bf16, f32m, f16 in ((False, False, False), (False, True, False), (True, False, False), (False, False, True)):
-        pk = _PolicyPacker(pol, env.nS, bf16, f32_mfma=f32m, f16_mfma=f16)
+    for actor in ("fp32", "fp32_mfma", "bf16", "f16"):
+        pk = _PolicyPacker(pol, env.nS, actor)
         for rnd in range(2):
             ref = pk.pack()
             out = torch.full_like(ref, float("nan"))
             pk.pack_native(env, out)
             env.sync()
             torch.cuda.synchronize()
-            assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), (bf16, f32m, f16, rnd)
+            assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), (actor, rnd)
             with torch.no_grad():                       # an optimiser step updates in place: the next pack must see it
                 for prm in pol.parameters():
                     prm.mul_(1.01).add_(0.003)
@@ -235,7 +235,7 @@ def test_native_weight_pack_equals_the_torch_pack(G, kind):
     with torch.no_grad():
         for prm in spol.parameters():
             prm.add_(torch.randn_like(prm) * 0.3)
-    pk = _PolicyPacker(spol, env.nS, False, f16_mfma=True)
+    pk = _PolicyPacker(spol, env.nS, "f16_shared")
     ref = pk.pack()
     out = torch.full_like(ref, float("nan"))
     pk.pack_native(env, out)
@@ -390,6 +390,56 @@ def test_matrix_core_actors_are_deterministic(G, actor, n, tune):
             bad = (x != y)
             assert not bool(bad.any()), (rep, int(bad.sum()), sorted(set((bad.nonzero()[:, -1] % 64).tolist()))[:4])
         assert tot == tot0
+
+
+@pytest.mark.parametrize("variant", ["tl", "boot", "nrm", "nrm_boot", "dr", "dr_boot"])
+@pytest.mark.parametrize("actor", ["f16", "f16_shared"])
+def test_pair_group_never_changes_a_variant_rollout(G, actor, variant):
+    """RMAV_TUNE_PAIR_GROUP sizes the workgroup and its LDS (weights once, one tile per pair - the larger *_boot tiles, the *_nrm tables
+    behind them) and must never change a result: for every variant kernel of the two pair families, 1 and 4 pairs per workgroup give
+    the bits of the automatic choice.  quadrotor3d-slungload (16 states: the largest tiles), 160 envs = two full wavefronts and a ragged
+    one, 8 steps under a 3-step limit (every env is truncated at least twice) where the variant has one; nrm: statistics after one
+    update; dr: a mass range."""
+    import torch
+    from gym_reinmav_amd.obs_norm import RunningObsNorm
+    from gym_reinmav_amd.ppo import FusedPolicyCollector
+
+    kind, N, T, seed = "quad3d_sl", 160, 8, 21
+    limit = None if variant in ("nrm", "dr") else 3
+    want_boot = variant.endswith("boot")
+    ranges = {"mass": (0.8, 1.25)} if variant.startswith("dr") else None
+    torch.manual_seed(6)
+    probe = G.BatchedQuadrotor(kind, N, seed=seed + 1)
+    norm = None
+    if variant.startswith("nrm"):
+        norm = RunningObsNorm(probe.nS, torch.device("cuda", probe.device))
+        norm.update(probe.rollout(T, mode="random", layout="soa", want=("obs",), device_out=True)["obs"], layout="soa", env=probe)
+    pol = _policy_for(actor, probe.nS, probe.nA, init_logstd=0.5, obs_norm=norm).cuda()
+    torch.cuda.synchronize()
+    probe.close()
+    names = ("act", "obs", "rew", "done", "logp", "val") + (("boot", "trunc") if want_boot else ())
+    outs = {}
+    for group in (-1, 1, 4):
+        env = G.BatchedQuadrotor(kind, N, seed=seed, max_episode_steps=limit, randomize=ranges)
+        env.set_tuning(pair_group=group)
+        ro = FusedPolicyCollector(env, pol, T, f16_mfma=True, bootstrap_truncated=want_boot)
+        ro.collect()
+        torch.cuda.synchronize()
+        outs[group] = {k: getattr(ro, k).clone() for k in names}
+        outs[group]["state"] = env.get_state(layout="soa", device_out=True).clone()
+        outs[group]["mass"] = torch.from_numpy(env.get_env_param("mass"))
+        env.close()
+    ref = outs[-1]
+    if limit:
+        assert int(ref["done"].sum()) >= 2 * N
+    if want_boot:
+        assert int(ref["trunc"].sum()) > 0 and bool((ref["boot"] != 0).any())
+    if ranges:
+        assert float(ref["mass"].std()) > 0.05
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t  # noqa: E731
+    for group in (1, 4):
+        for k, x in outs[group].items():
+            assert torch.equal(bits(x), bits(ref[k])), (actor, variant, group, k)
 
 
 @pytest.mark.parametrize("kind,n,mode", [("quad3d", 65536, "random"), ("quad3d", 262144, "random"), ("quad3d", 131072, "controller"),

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Compare the instruction streams of the kernels of two `make asm` outputs (build/rmav_abi.gfx950.s, build/rmav_policy_abi.gfx950.s).
+"""Compare the instruction streams of the kernels of two `make asm` outputs: the listings of the three translation units,
+build/rmav_abi.gfx950.s, build/rmav_policy_abi.gfx950.s and build/rmav_range_abi.gfx950.s.
 
     python tools/isa_compare.py OLD_DIR NEW_DIR
 
@@ -18,7 +19,7 @@ import os
 import re
 import sys
 
-UNITS = ("rmav_abi.gfx950.s", "rmav_policy_abi.gfx950.s")
+UNITS = ("rmav_abi.gfx950.s", "rmav_policy_abi.gfx950.s", "rmav_range_abi.gfx950.s")
 _LABEL = re.compile(r"\.L[A-Za-z_]*\d+(?:_\d+)*")
 _KERNEL_ID = re.compile(r"^s_mov_b32 s15, \d+$")
 
