@@ -1,5 +1,6 @@
 // rmav_abi.hip - the C ABI of include/rmav.h: handle management, launches, host/device staging.
 // There is deliberately no CPU implementation in this library: without a GPU rmav_create fails.
+// The entry points of include/rmav_ppo.h are in rmav_ppo_abi.hip, those of include/rmav_comm.h in rmav_comm_abi.hip.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -9,12 +10,8 @@
 #include <ctime>
 #include <new>
 
-#include <dlfcn.h>
-
 #include "rmav_handle.hpp"
-#include "rmav_gae.hpp"
-#include "rmav_obs_norm.hpp"
-#include "rmav_ret_norm.hpp"
+#include "rmav_core_kernels.hpp"
 
 using namespace rmav;
 
@@ -32,45 +29,7 @@ int rmav_fail(int code, const char *fmt, ...) {
     return code;
 }
 
-namespace {
-
-bool valid(rmav_handle h) { return h && h->magic == kMagic; }
-
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-#define CHECK_HANDLE(h)                                                                            \
-    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");                           \
-    DeviceGuard guard_(h->device);                                                                 \
-    if (!guard_.ok) return rmav_fail(RMAV_ERR_HIP, "hipSetDevice(%d) failed", h->device)
-
-int check_params(const rmav_params &q) {
-    if (q.integrator != RMAV_INT_EULER && q.integrator != RMAV_INT_RK4)
-        return rmav_fail(RMAV_ERR_INVALID, "rmav_params.integrator must be RMAV_INT_EULER or RMAV_INT_RK4");
-    if (!(q.mass > 0) || !(q.dt > 0) || !(q.tau != 0) || !(q.mass + q.load_mass > 0))
-        return rmav_fail(RMAV_ERR_INVALID, "rmav_params: mass, dt must be > 0 and tau != 0");
-    for (int i = 0; i < 3; ++i)
-        if (!(q.g_vec[i] == q.g_vec[i]) || q.g_vec[i] - q.g_vec[i] != 0.0)
-            return rmav_fail(RMAV_ERR_INVALID, "rmav_params.g_vec must be finite");
-    return RMAV_OK;
-}
-
-// slots of the per-wavefront episode totals: one per 32 envs (the fp32-MFMA policy mode runs 32 envs per wavefront)
-// + 4: k_step reads its wavefront's slot in EVERY wavefront of the launch grid, also in those of the last 256-thread workgroup that lie
-// wholly past N (they add nothing and write nothing); the padding keeps those reads inside the array
-inline size_t n_total_slots(int64_t n) { return (size_t)((n + 31) / 32) + 4; }
-
-
+// ---- what rmav_ppo_abi.hip shares with this unit (declared in rmav_handle.hpp) ------------------------------------------------
 int ensure_scratch(rmav_handle h, size_t bytes) {
     if (bytes <= h->scratch_bytes) return RMAV_OK;
     if (h->scratch) {
@@ -120,6 +79,46 @@ int ensure_boot_scratch(rmav_handle h, size_t bytes) {
     h->boot_scratch_bytes = bytes;
     return RMAV_OK;
 }
+
+RolloutArgs base_args(rmav_handle h) {
+    RolloutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.state = h->state;
+    a.n = h->n;
+    a.pitch = h->n;
+    a.rec = h->rec;
+    a.ep_ret = h->ep_ret;
+    a.last_ret = h->last_ret;
+    a.totals = h->totals;
+    a.env_time = h->env_time;
+    for (int i = 0; i < 3; ++i) a.pe[i] = h->pe[i];
+    a.seed = h->seed;
+    a.env_base = h->env_base;
+    a.t0 = h->t;
+    a.n_steps = 1;
+    a.flags = h->flags & (F_AUTO_RESET | F_TRACK);
+    a.act_lo = (float)h->params.act_lo;
+    a.act_hi = (float)h->params.act_hi;
+    return a;
+}
+
+namespace {
+
+int check_params(const rmav_params &q) {
+    if (q.integrator != RMAV_INT_EULER && q.integrator != RMAV_INT_RK4)
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_params.integrator must be RMAV_INT_EULER or RMAV_INT_RK4");
+    if (!(q.mass > 0) || !(q.dt > 0) || !(q.tau != 0) || !(q.mass + q.load_mass > 0))
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_params: mass, dt must be > 0 and tau != 0");
+    for (int i = 0; i < 3; ++i)
+        if (!(q.g_vec[i] == q.g_vec[i]) || q.g_vec[i] - q.g_vec[i] != 0.0)
+            return rmav_fail(RMAV_ERR_INVALID, "rmav_params.g_vec must be finite");
+    return RMAV_OK;
+}
+
+// slots of the per-wavefront episode totals: one per 32 envs (the fp32-MFMA policy mode runs 32 envs per wavefront)
+// + 4: k_step reads its wavefront's slot in EVERY wavefront of the launch grid, also in those of the last 256-thread workgroup that lie
+// wholly past N (they add nothing and write nothing); the padding keeps those reads inside the array
+inline size_t n_total_slots(int64_t n) { return (size_t)((n + 31) / 32) + 4; }
 
 // Host-pointer calls that move at most this many bytes go through the pinned block (zero-copy); bigger ones
 // stage through device scratch with hipMemcpyAsync, which is the faster route for bulk data.
@@ -446,28 +445,6 @@ int launch_rollout(rmav_handle h, int mode, const RolloutArgs &a) {
     if (a.n_steps == 1 && (mode == RMAV_ACT_BUFFER || mode == ACT_BUFFER_CTRL) && h->kind != RMAV_REINMAV)
         return dispatch_kind<QUAD_KINDS>(h->kind, [&](auto k) { return launch_step_k<decltype(k)::value>(h, a, mode == ACT_BUFFER_CTRL); });
     return dispatch_kind<ALL_KINDS>(h->kind, [&](auto k) { return launch_rollout_k<decltype(k)::value>(h, mode, a); });
-}
-
-RolloutArgs base_args(rmav_handle h) {
-    RolloutArgs a;
-    memset(&a, 0, sizeof(a));
-    a.state = h->state;
-    a.n = h->n;
-    a.pitch = h->n;
-    a.rec = h->rec;
-    a.ep_ret = h->ep_ret;
-    a.last_ret = h->last_ret;
-    a.totals = h->totals;
-    a.env_time = h->env_time;
-    for (int i = 0; i < 3; ++i) a.pe[i] = h->pe[i];
-    a.seed = h->seed;
-    a.env_base = h->env_base;
-    a.t0 = h->t;
-    a.n_steps = 1;
-    a.flags = h->flags & (F_AUTO_RESET | F_TRACK);
-    a.act_lo = (float)h->params.act_lo;
-    a.act_hi = (float)h->params.act_hi;
-    return a;
 }
 
 int launch_reset(rmav_handle h, float *obs_dev, int layout) {
@@ -922,6 +899,25 @@ int rmav_set_env_param(rmav_handle h, int which, const float *values, int mem) {
     return copy_in(h, h->pe[which], values, (size_t)h->n, mem);
 }
 
+int rmav_get_env_param(rmav_handle h, int which, float *out, int mem) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, RMAV_SOA)) return rc;
+    if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "per-env constants are for the quadrotor kinds");
+    if (!out) return rmav_fail(RMAV_ERR_INVALID, "output pointer is NULL");
+    if (h->pe[which]) return copy_out(h, (const float *)h->pe[which], out, (size_t)h->n, mem);
+    // no array: every env has the shared value, rounded to fp32 as an uploaded array would hold it
+    const float v = (float)(which == RMAV_PARAM_MASS ? h->params.mass : which == RMAV_PARAM_LOAD_MASS ? h->params.load_mass : h->params.tether_length);
+    if (mem == RMAV_DEVICE) {
+        uint32_t bits;
+        memcpy(&bits, &v, 4);
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)bits, (size_t)h->n, h->stream));
+    } else {
+        for (int64_t i = 0; i < h->n; ++i) out[i] = v;
+    }
+    return RMAV_OK;
+}
+
 int rmav_set_env_param_range(rmav_handle h, int which, float lo, float hi) {
     CHECK_HANDLE(h);
     if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
@@ -947,25 +943,6 @@ int rmav_get_env_param_range(rmav_handle h, int which, float *lo, float *hi, int
     if (lo) *lo = on ? h->range_lo[which] : 0.0f;
     if (hi) *hi = on ? h->range_hi[which] : 0.0f;
     if (enabled) *enabled = on ? 1 : 0;
-    return RMAV_OK;
-}
-
-int rmav_get_env_param(rmav_handle h, int which, float *out, int mem) {
-    CHECK_HANDLE(h);
-    if (int rc = check_mem_layout(mem, RMAV_SOA)) return rc;
-    if (which < 0 || which > 2) return rmav_fail(RMAV_ERR_INVALID, "unknown env param %d", which);
-    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "per-env constants are for the quadrotor kinds");
-    if (!out) return rmav_fail(RMAV_ERR_INVALID, "output pointer is NULL");
-    if (h->pe[which]) return copy_out(h, (const float *)h->pe[which], out, (size_t)h->n, mem);
-    // no array: every env has the shared value, rounded to fp32 as an uploaded array would hold it
-    const float v = (float)(which == RMAV_PARAM_MASS ? h->params.mass : which == RMAV_PARAM_LOAD_MASS ? h->params.load_mass : h->params.tether_length);
-    if (mem == RMAV_DEVICE) {
-        uint32_t bits;
-        memcpy(&bits, &v, 4);
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)out, (int)bits, (size_t)h->n, h->stream));
-    } else {
-        for (int64_t i = 0; i < h->n; ++i) out[i] = v;
-    }
     return RMAV_OK;
 }
 
@@ -1153,6 +1130,35 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     return RMAV_OK;
 }
 
+int rmav_step(rmav_handle h, const float *actions, float *obs_out, float *rew_out,
+              uint8_t *done_out, int mem, int layout) {
+    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
+    return rmav_rollout(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, mem,
+                        layout, 1);
+}
+
+int rmav_control(rmav_handle h, float *actions_out, int mem, int layout) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, layout)) return rc;
+    if (!actions_out) return rmav_fail(RMAV_ERR_INVALID, "actions_out is NULL");
+    return write_via_host(h, actions_out, (size_t)h->n * kActionDim[h->kind] * sizeof(float), mem,
+                          [&](void *dst) { return launch_control(h, (float *)dst, layout); });
+}
+
+int rmav_control_step(rmav_handle h, float *actions_out, float *obs_out, float *rew_out, uint8_t *done_out, int mem,
+                      int layout) {
+    return rollout_impl(h, 1, RMAV_ACT_CONTROLLER, nullptr, actions_out, obs_out, rew_out, done_out, nullptr, mem,
+                        layout, 1);
+}
+
+int rmav_step_control(rmav_handle h, const float *actions, float *obs_out, float *rew_out, uint8_t *done_out,
+                      float *next_actions_out, int mem, int layout) {
+    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
+    if (!next_actions_out) return rmav_fail(RMAV_ERR_INVALID, "next_actions_out is NULL");
+    return rollout_impl(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, next_actions_out, mem,
+                        layout, 1);
+}
+
 int rmav_rollout(rmav_handle h, int32_t n_steps, int action_mode, const float *actions_in,
                  float *actions_out, float *obs_out, float *rew_out, uint8_t *done_out, int mem,
                  int layout, int fused) {
@@ -1199,171 +1205,6 @@ int rmav_rollout_chunked(rmav_handle h, int32_t n_steps, int action_mode, const 
     const int rc = rollout_impl(h, n_steps, action_mode, actions_in, actions_out, obs_out, rew_out, done_out, nullptr, RMAV_DEVICE, RMAV_SOA, 1);
     h->chunk = 0;
     return rc;
-}
-
-int rmav_step_control(rmav_handle h, const float *actions, float *obs_out, float *rew_out, uint8_t *done_out,
-                      float *next_actions_out, int mem, int layout) {
-    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
-    if (!next_actions_out) return rmav_fail(RMAV_ERR_INVALID, "next_actions_out is NULL");
-    return rollout_impl(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, next_actions_out, mem,
-                        layout, 1);
-}
-
-int rmav_control_step(rmav_handle h, float *actions_out, float *obs_out, float *rew_out, uint8_t *done_out, int mem,
-                      int layout) {
-    return rollout_impl(h, 1, RMAV_ACT_CONTROLLER, nullptr, actions_out, obs_out, rew_out, done_out, nullptr, mem,
-                        layout, 1);
-}
-
-int64_t rmav_policy_weight_count(int kind) {
-    return dispatch_kind<ALL_KINDS>(kind, [](auto k) { return (int64_t)PolicyLayout<Dims<decltype(k)::value>::NS>::TOTAL; });
-}
-
-int64_t rmav_policy_weight_count_bf16(void) { return MfmaLayout::TOTAL; }
-int64_t rmav_policy_weight_count_f32_mfma(void) { return Mfma32Layout::TOTAL; }
-int64_t rmav_policy_weight_count_shared(void) { return MfmaLayout::NET + 4; }
-
-static int pack_policy_impl(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
-                            const int32_t *idx_hi, int64_t n_out, float *weights_out, bool f16) {
-    CHECK_HANDLE(h);
-    if (n_params <= 0 || n_params > kPackMaxParams) return rmav_fail(RMAV_ERR_INVALID, "n_params must be in [1, %d]", kPackMaxParams);
-    if (!params || !sizes || !idx_lo || !idx_hi || !weights_out || n_out <= 0)
-        return rmav_fail(RMAV_ERR_INVALID, "params, sizes, idx_lo, idx_hi, weights_out are required and n_out > 0");
-    PackSrc src;
-    memset(&src, 0, sizeof(src));
-    int64_t end = 0;
-    for (int k = 0; k < n_params; ++k) {
-        if (!params[k] || sizes[k] < 0) return rmav_fail(RMAV_ERR_INVALID, "parameter %d is NULL or has a negative size", k);
-        end += sizes[k];
-        if (end > 0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many parameter elements");
-        src.p[k] = params[k];
-        src.end[k] = (int32_t)end;
-    }
-    src.n = n_params;
-    const dim3 grid((unsigned)((n_out + 255) / 256));
-    if (f16) {
-        if (n_out != MfmaLayout::TOTAL && n_out != MfmaLayout::NET + 4)
-            return rmav_fail(RMAV_ERR_INVALID, "n_out must be rmav_policy_weight_count_bf16() = %d or rmav_policy_weight_count_shared() = %d",
-                             (int)MfmaLayout::TOTAL, (int)MfmaLayout::NET + 4);
-        hipLaunchKernelGGL(k_pack_policy<true>, grid, dim3(256), 0, h->stream, src, idx_lo, idx_hi, n_out, weights_out, (int32_t)MfmaLayout::NET,
-                           (int32_t)MfmaLayout::A2, (int32_t)MfmaLayout::A3, (int32_t)MfmaLayout::B1, -2.0f * kTanhScale, -2.0f);
-    } else {
-        hipLaunchKernelGGL(k_pack_policy<false>, grid, dim3(256), 0, h->stream, src, idx_lo, idx_hi, n_out, weights_out, 1, 0, 0, 0, 1.0f, 1.0f);
-    }
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_pack_policy(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
-                     const int32_t *idx_hi, int64_t n_out, float *weights_out) {
-    return pack_policy_impl(h, n_params, params, sizes, idx_lo, idx_hi, n_out, weights_out, false);
-}
-int rmav_pack_policy_f16(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
-                         const int32_t *idx_hi, int64_t n_out, float *weights_out) {
-    return pack_policy_impl(h, n_params, params, sizes, idx_lo, idx_hi, n_out, weights_out, true);
-}
-
-// ---- rmav_rollout_policy / _boot / _norm: the checks all three make, in the order they make them, and the launch ------------------
-// The refusal of an actor without variant kernels (policy_has_variants, rmav_handle.hpp): `who` = the entry point or the handle's feature,
-// `what` = the kind of kernel the fp32 vector-ALU and bf16 actors lack.  RMAV_OK for the three actors that have them.
-static int need_variants(int precision, const char *who, const char *what) {
-    if (policy_has_variants(policy_kmode(precision))) return RMAV_OK;
-    return rmav_fail(RMAV_ERR_INVALID, "%s runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
-                                       "(the fp32 vector-ALU and bf16 actors have no %s kernel), got precision %d", who, what, precision);
-}
-// boot_out: checked (and named) only when the entry point requires it
-static int check_policy_args(int32_t n_steps, const float *weights, const float *logp_out, const float *value_out, bool need_boot, const float *boot_out) {
-    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!weights || !logp_out || !value_out || (need_boot && !boot_out))
-        return rmav_fail(RMAV_ERR_INVALID, need_boot ? "weights, logp_out, value_out and boot_out are required (device pointers)"
-                                                     : "weights, logp_out and value_out are required (device pointers)");
-    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
-    return RMAV_OK;
-}
-// one fused launch over all envs (it may carry an armed exchange's snapshot), then the step counter
-static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out, float *rew_out,
-                              uint8_t *done_out, float *logp_out, float *value_out, int precision, const BootArgs *bt, const NormArgs *nm) {
-    RolloutArgs a = base_args(h);
-    a.n_steps = n_steps;
-    a.act_out = actions_out;
-    a.obs_out = obs_out;
-    a.rew_out = rew_out;
-    a.done_out = done_out;
-    a.policy_w = weights;
-    a.logp_out = logp_out;
-    a.val_out = value_out;
-    h->xchg.allow = true;
-    // A handle with a parameter range runs ONE ranged kernel per actor, the normalised one: a call without
-    // statistics gets identity tables - z then has the bits of x (rmav_ppo.h) - and a call on a time-limited handle that asked for no
-    // bootstrap term a boot_out of the handle's own.
-    BootArgs bt_r{};
-    NormArgs nm_r{};
-    if (h->range_mask) {
-        if (int rc = need_variants(precision, "a handle with a parameter range", "ranged")) return rc;
-        if (!nm) {
-            if (int rc = ensure_ident_norm(h)) return rc;
-            nm_r.tab = h->ident_norm;
-            nm = &nm_r;
-        }
-        if (h->time_limit > 0 && !bt) {
-            if (int rc = ensure_boot_scratch(h, (size_t)n_steps * (size_t)h->n * sizeof(float))) return rc;
-            bt_r.boot_out = h->boot_scratch;
-            bt = &bt_r;
-        }
-    }
-    if (int rc = rmav_launch_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
-    h->t += (uint64_t)n_steps;
-    return RMAV_OK;
-}
-
-int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out,
-                        float *obs_out, float *rew_out, uint8_t *done_out, float *logp_out,
-                        float *value_out, int precision) {
-    CHECK_HANDLE(h);
-    if (precision < RMAV_POLICY_FP32 || precision > RMAV_POLICY_F16_SHARED)
-        return rmav_fail(RMAV_ERR_INVALID, "precision must be one of RMAV_POLICY_FP32 ... RMAV_POLICY_F16_SHARED (rmav_policy_precision)");
-    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
-    if (h->time_limit > 0)
-        if (int rc = need_variants(precision, "a time-limited handle", "time-limited")) return rc;
-    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, nullptr, nullptr);
-}
-
-int rmav_step(rmav_handle h, const float *actions, float *obs_out, float *rew_out,
-              uint8_t *done_out, int mem, int layout) {
-    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
-    return rmav_rollout(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, mem,
-                        layout, 1);
-}
-
-int rmav_step_final(rmav_handle h, const float *actions, float *obs_out, float *rew_out, uint8_t *done_out, float *final_obs_out,
-                    uint8_t *trunc_out, int mem, int layout) {
-    CHECK_HANDLE(h);
-    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
-    if (h->kind == RMAV_REINMAV)
-        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit and never resets: rmav_step's obs is its terminal observation");
-    return rollout_impl(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, nullptr, mem, layout, 1, 0, true, final_obs_out,
-                        trunc_out);
-}
-
-int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out, float *rew_out,
-                             uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out, int precision) {
-    CHECK_HANDLE(h);
-    if (h->kind == RMAV_REINMAV)
-        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap");
-    if (h->time_limit <= 0)
-        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot needs an episode time limit on the handle (rmav_set_time_limit)");
-    if (int rc = need_variants(precision, "rmav_rollout_policy_boot", "time-limited")) return rc;
-    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, true, boot_out)) return rc;
-    const BootArgs bt{boot_out, trunc_out};
-    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, nullptr);
-}
-
-int rmav_control(rmav_handle h, float *actions_out, int mem, int layout) {
-    CHECK_HANDLE(h);
-    if (int rc = check_mem_layout(mem, layout)) return rc;
-    if (!actions_out) return rmav_fail(RMAV_ERR_INVALID, "actions_out is NULL");
-    return write_via_host(h, actions_out, (size_t)h->n * kActionDim[h->kind] * sizeof(float), mem,
-                          [&](void *dst) { return launch_control(h, (float *)dst, layout); });
 }
 
 int rmav_get_state(rmav_handle h, float *out, int mem, int layout) {
@@ -1535,678 +1376,14 @@ int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem) {
     return copy_out(h, (const uint8_t *)h->last_trunc, out, (size_t)h->n, mem);
 }
 
-// ---- learner-side helpers on the trajectory ----------------------------------------------------
-// The one launcher of the GAE family.  with_boot (rmav_gae_boot): k_gae_boot, which adds the bootstrap term `boot` of the truncated steps;
-// stats (rmav_gae_norm): k_gae_norm<with_boot>, which normalises every reward as it is loaded (csrc/rmav_ret_norm.hpp)
-static int gae_impl(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, bool with_boot, const float *boot,
-                    const RetNormStats *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
-    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (!rew || !done || !values || (with_boot && !boot) || !adv_out || !ret_out)
-        return rmav_fail(RMAV_ERR_INVALID, with_boot ? "rew, done, values, boot, adv_out and ret_out are required (device pointers)"
-                                                     : "rew, done, values, adv_out and ret_out are required (device pointers)");
-    const unsigned nblk = (unsigned)((h->n + 255) / 256);
-    double *partial = nullptr;
-    if (sums_out) {
-        if (int rc = ensure_scratch(h, (size_t)nblk * 2 * sizeof(double))) return rc;
-        partial = (double *)h->scratch;
-    }
-    if (stats && with_boot)
-        hipLaunchKernelGGL(k_gae_norm<true>, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, stats, adv_out, ret_out, h->n, n_steps,
-                           gamma, lam, reward_scale, partial);
-    else if (stats)
-        hipLaunchKernelGGL(k_gae_norm<false>, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, stats, adv_out, ret_out, h->n, n_steps,
-                           gamma, lam, reward_scale, partial);
-    else if (with_boot)
-        hipLaunchKernelGGL(k_gae_boot, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, adv_out, ret_out, h->n, n_steps, gamma, lam,
-                           reward_scale, partial);
-    else
-        hipLaunchKernelGGL(k_gae, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, adv_out, ret_out, h->n, n_steps, gamma, lam, reward_scale,
-                           partial);
-    HIP_TRY(hipGetLastError());
-    if (sums_out) {
-        hipLaunchKernelGGL(k_gae_fold, dim3(1), dim3(256), 0, h->stream, (const double *)partial, (int)nblk, sums_out);
-        HIP_TRY(hipGetLastError());
-    }
-    return RMAV_OK;
-}
-
-int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values,
-             float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+int rmav_step_final(rmav_handle h, const float *actions, float *obs_out, float *rew_out, uint8_t *done_out, float *final_obs_out,
+                    uint8_t *trunc_out, int mem, int layout) {
     CHECK_HANDLE(h);
-    return gae_impl(h, n_steps, rew, done, values, false, nullptr, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
-}
-
-int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
-                  float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
-    CHECK_HANDLE(h);
+    if (!actions) return rmav_fail(RMAV_ERR_INVALID, "actions is NULL");
     if (h->kind == RMAV_REINMAV)
-        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (use rmav_gae)");
-    return gae_impl(h, n_steps, rew, done, values, true, boot, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
-}
-
-int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rstd) {
-    CHECK_HANDLE(h);
-    if (!x || count < 0) return rmav_fail(RMAV_ERR_INVALID, "x is NULL or count < 0");
-    if ((reinterpret_cast<uintptr_t>(x) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "x must be 16-byte aligned");
-    if (count == 0) return RMAV_OK;
-    int64_t blocks = (count / 4 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 4096) blocks = 4096;   // grid-stride: 16 blocks per CU keep the memory system full
-    hipLaunchKernelGGL(k_affine, dim3((unsigned)blocks), dim3(256), 0, h->stream, x, count, mean, rstd);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-// ---- observation normalisation (VecNormalize): running statistics on the device, csrc/rmav_obs_norm.hpp ------------------
-namespace {
-int check_norm_handle(rmav_handle h, const char *what) {
-    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "%s runs the four quadrotor kinds, not RMAV_REINMAV", what);
-    return RMAV_OK;
-}
-int check_stats(const void *stats) {
-    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_obs_norm_bytes() bytes)");
-    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
-    return RMAV_OK;
-}
-// the addressing of an observation array (ObsShape); n_rows >= 1 checked by the caller
-int obs_shape(rmav_handle h, int layout, int32_t n_rows, int64_t pitch, ObsShape &sh) {
-    const int ns = kStateDim[h->kind];
-    if (layout != RMAV_SOA && layout != RMAV_AOS) return rmav_fail(RMAV_ERR_INVALID, "layout must be RMAV_SOA or RMAV_AOS");
-    if (layout == RMAV_SOA) {
-        if (pitch == 0) pitch = h->n;
-        if (pitch < h->n || pitch > (int64_t)0x3fffffff) return rmav_fail(RMAV_ERR_INVALID, "pitch must be 0 (= N) or in [N, 2^30)");
-        sh = ObsShape{h->n, (int64_t)ns * pitch, pitch, 1, n_rows, ns};
-    } else {
-        if (pitch != 0) return rmav_fail(RMAV_ERR_INVALID, "pitch must be 0 with RMAV_AOS");
-        sh = ObsShape{h->n, h->n * ns, 1, ns, n_rows, ns};
-    }
-    return RMAV_OK;
-}
-}  // namespace
-
-int64_t rmav_obs_norm_bytes(void) { return (int64_t)sizeof(ObsNormStats); }
-
-int rmav_obs_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
-    CHECK_HANDLE(h);
-    if (int rc = check_norm_handle(h, "rmav_obs_norm_init")) return rc;
-    if (int rc = check_stats(stats)) return rc;
-    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
-        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
-    hipLaunchKernelGGL(k_obs_norm_init, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, (int32_t)kStateDim[h->kind], clip, eps, count0);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_obs_moments(rmav_handle h, const float *obs, int layout, int32_t n_rows, int64_t pitch, double *batch_out) {
-    CHECK_HANDLE(h);
-    if (int rc = check_norm_handle(h, "rmav_obs_moments")) return rc;
-    if (!obs || !batch_out) return rmav_fail(RMAV_ERR_INVALID, "obs and batch_out are required (device pointers)");
-    if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
-    ObsShape sh;
-    if (int rc = obs_shape(h, layout, n_rows > 0 ? n_rows : 1, pitch, sh)) return rc;
-    sh.n_rows = n_rows;   // 0 rows: an empty record (count 0), which rmav_obs_norm_merge skips
-    const bool vec = layout == RMAV_SOA && (reinterpret_cast<uintptr_t>(obs) & 15u) == 0 && (sh.feat & 3) == 0;
-    const int64_t cols = vec ? (sh.n + 3) / 4 : sh.n;
-    const int64_t xenv = (cols + 255) / 256;
-    // enough blocks for 256 CUs (8 per CU) when the rows allow it; a thread then walks every rgroups-th row
-    int64_t rgroups = (2048 + xenv * sh.ns - 1) / (xenv * sh.ns);
-    if (rgroups > n_rows) rgroups = n_rows;
-    if (rgroups < 1) rgroups = 1;
-    const int64_t nblk = xenv * rgroups;
-    if (int rc = ensure_scratch(h, (size_t)nblk * sh.ns * sizeof(Moment))) return rc;
-    const dim3 grid((unsigned)nblk, (unsigned)sh.ns);
-    if (vec) hipLaunchKernelGGL(k_obs_moments<true>, grid, dim3(256), 0, h->stream, obs, sh, (int32_t)xenv, (int32_t)rgroups, (Moment *)h->scratch);
-    else hipLaunchKernelGGL(k_obs_moments<false>, grid, dim3(256), 0, h->stream, obs, sh, (int32_t)xenv, (int32_t)rgroups, (Moment *)h->scratch);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_obs_moments_fold, dim3(kNormFeat), dim3(256), 0, h->stream, (const Moment *)h->scratch, (int32_t)nblk, (int32_t)sh.ns, batch_out);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_obs_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
-    CHECK_HANDLE(h);
-    if (int rc = check_norm_handle(h, "rmav_obs_norm_merge")) return rc;
-    if (int rc = check_stats(stats)) return rc;
-    if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
-    if (n_batches == 0) return RMAV_OK;
-    if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 33 doubles on the device)");
-    hipLaunchKernelGGL(k_obs_norm_merge, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, batch, n_batches, (int32_t)kStateDim[h->kind]);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_obs_normalize(rmav_handle h, const void *stats, const float *in, float *out, int layout, int32_t n_rows, int64_t pitch) {
-    CHECK_HANDLE(h);
-    if (int rc = check_norm_handle(h, "rmav_obs_normalize")) return rc;
-    if (int rc = check_stats(stats)) return rc;
-    if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
-    if (n_rows == 0) return RMAV_OK;
-    if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
-    ObsShape sh;
-    if (int rc = obs_shape(h, layout, n_rows, pitch, sh)) return rc;
-    const int64_t total = sh.n * sh.ns * (int64_t)n_rows;
-    if ((total + 255) / 256 > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many elements for one launch");
-    hipLaunchKernelGGL(k_obs_normalize, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const ObsNormStats *)stats, in, out, sh);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-// ---- return normalisation (the reward half of VecNormalize): one scalar RunningMeanStd on the device, csrc/rmav_ret_norm.hpp -----------
-namespace {
-int check_ret_stats(const void *stats) {
-    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_ret_norm_bytes() bytes)");
-    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
-    return RMAV_OK;
-}
-}  // namespace
-
-int64_t rmav_ret_norm_bytes(void) { return (int64_t)sizeof(RetNormStats); }
-
-int rmav_ret_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
-    CHECK_HANDLE(h);
-    if (int rc = check_ret_stats(stats)) return rc;
-    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
-        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
-    hipLaunchKernelGGL(k_ret_norm_init, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, clip, eps, count0);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_ret_moments(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, float reward_scale, float gamma, float *carry,
-                     double *batch_out) {
-    CHECK_HANDLE(h);
-    if (n_steps < 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be >= 0");
-    if (!batch_out) return rmav_fail(RMAV_ERR_INVALID, "batch_out is required (3 doubles on the device)");
-    if (n_steps > 0 && (!rew || !done || !carry)) return rmav_fail(RMAV_ERR_INVALID, "rew, done and carry are required (device pointers)");
-    const unsigned nblk = n_steps > 0 ? (unsigned)((h->n + 255) / 256) : 0u;   // 0 steps: an empty record, carry untouched
-    if (nblk) {
-        if (int rc = ensure_scratch(h, (size_t)nblk * sizeof(Moment))) return rc;
-        hipLaunchKernelGGL(k_ret_moments, dim3(nblk), dim3(256), 0, h->stream, rew, done, carry, h->n, n_steps, reward_scale, gamma,
-                           (Moment *)h->scratch);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_ret_moments_fold, dim3(1), dim3(256), 0, h->stream, (const Moment *)h->scratch, (int32_t)nblk, batch_out);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_ret_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
-    CHECK_HANDLE(h);
-    if (int rc = check_ret_stats(stats)) return rc;
-    if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
-    if (n_batches == 0) return RMAV_OK;
-    if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 3 doubles on the device)");
-    hipLaunchKernelGGL(k_ret_norm_merge, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, batch, n_batches);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_ret_normalize(rmav_handle h, const void *stats, const float *in, float *out, int64_t count, float reward_scale) {
-    CHECK_HANDLE(h);
-    if (int rc = check_ret_stats(stats)) return rc;
-    if (count < 0) return rmav_fail(RMAV_ERR_INVALID, "count must be >= 0");
-    if (count == 0) return RMAV_OK;
-    if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
-    if ((count + 255) / 256 > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many elements for one launch");
-    hipLaunchKernelGGL(k_ret_normalize, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (const RetNormStats *)stats, in, out, count,
-                       reward_scale);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
-                  const void *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
-    CHECK_HANDLE(h);
-    if (boot && h->kind == RMAV_REINMAV)
-        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (pass boot = NULL)");
-    if (int rc = check_ret_stats(stats)) return rc;
-    return gae_impl(h, n_steps, rew, done, values, boot != nullptr, boot, (const RetNormStats *)stats, gamma, lam, reward_scale, adv_out, ret_out,
-                    sums_out);
-}
-
-int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weights, const void *stats, float *actions_out, float *obs_out,
-                             float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out,
-                             int precision) {
-    CHECK_HANDLE(h);
-    if (int rc = check_norm_handle(h, "rmav_rollout_policy_norm")) return rc;
-    if (int rc = need_variants(precision, "rmav_rollout_policy_norm", "normalised")) return rc;
-    if (int rc = check_stats(stats)) return rc;
-    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
-    if (h->time_limit > 0 && !boot_out)
-        return rmav_fail(RMAV_ERR_INVALID, "boot_out is required on a handle with an episode time limit (as rmav_rollout_policy_boot)");
-    if (h->time_limit <= 0 && (boot_out || trunc_out))
-        return rmav_fail(RMAV_ERR_INVALID, "boot_out / trunc_out need an episode time limit on the handle (rmav_set_time_limit); pass NULL");
-    const BootArgs bt{boot_out, trunc_out};
-    const NormArgs nm{((const ObsNormStats *)stats)->mean_f};
-    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, &nm);
-}
-
-// ---- the path's one collective, behind the C ABI: RCCL all-gather of per-env episode statistics ---------------
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int *) = nullptr;      // optional (rmav_comm_info)
-    ncclResult_t (*CommUserRank)(const ncclComm_t, int *) = nullptr;   // optional
-};
-// resolved on first use: librmav.so has no link-time dependency on RCCL, and a process that already loaded
-// librccl.so.1 (torch does) shares that copy
-char g_rccl_path[1024] = "";   // rmav_comm_use_library
-bool g_rccl_tried = false;
-RcclApi *rccl() {
-    static RcclApi api;
-    if (!g_rccl_tried) {
-        g_rccl_tried = true;
-        if (g_rccl_path[0]) {
-            api.lib = dlopen(g_rccl_path, RTLD_NOW | RTLD_LOCAL);
-        } else {
-            for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-                api.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-                if (api.lib) break;
-            }
-        }
-        if (api.lib) {
-            api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.lib, "ncclGetUniqueId");
-            api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.lib, "ncclCommInitRank");
-            api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.lib, "ncclCommDestroy");
-            api.AllGather = (decltype(api.AllGather))dlsym(api.lib, "ncclAllGather");
-            api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.lib, "ncclGetErrorString");
-            api.CommCount = (decltype(api.CommCount))dlsym(api.lib, "ncclCommCount");
-            api.CommUserRank = (decltype(api.CommUserRank))dlsym(api.lib, "ncclCommUserRank");
-            if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllGather) api.lib = nullptr;
-        }
-    }
-    return api.lib ? &api : nullptr;
-}
-constexpr uint32_t kCommMagic = 0x524d4143u;  // 'RMAC'
-#define RCCL_TRY(expr)                                                                             \
-    do {                                                                                           \
-        ncclResult_t r_ = (expr);                                                                  \
-        if (r_ != ncclSuccess)                                                                     \
-            return rmav_fail(RMAV_ERR_HIP, "%s failed: %s", #expr, R->GetErrorString ? R->GetErrorString(r_) : "RCCL error"); \
-    } while (0)
-}  // namespace
-
-int rmav_comm_use_library(const char *path) {
-    if (g_rccl_tried) return rmav_fail(RMAV_ERR_INVALID, "the collective library has already been loaded: call this before any other rmav_comm_* function");
-    if (!path || !path[0] || strlen(path) >= sizeof(g_rccl_path)) return rmav_fail(RMAV_ERR_INVALID, "path is NULL, empty or too long");
-    snprintf(g_rccl_path, sizeof(g_rccl_path), "%s", path);
-    return RMAV_OK;
-}
-
-int rmav_comm_unique_id(void *id_out) {
-    if (!id_out) return rmav_fail(RMAV_ERR_INVALID, "id_out is NULL");
-    RcclApi *R = rccl();
-    if (!R) return rmav_fail(RMAV_ERR_NO_DEVICE, "librccl.so.1 could not be loaded");
-    ncclUniqueId id;
-    RCCL_TRY(R->GetUniqueId(&id));
-    static_assert(sizeof(id) == RMAV_COMM_ID_BYTES, "RCCL unique id size");
-    memcpy(id_out, &id, sizeof(id));
-    return RMAV_OK;
-}
-
-int rmav_comm_info(rmav_comm c, int *rank_out, int *world_out, int *lib_rank_out, int *lib_world_out) {
-    if (!c || c->magic != kCommMagic) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_comm");
-    if (rank_out) *rank_out = c->rank;
-    if (world_out) *world_out = c->world;
-    RcclApi *R = rccl();
-    int lr = -1, lw = -1;
-    if (R && R->CommUserRank && R->CommUserRank(c->comm, &lr) != ncclSuccess) lr = -1;
-    if (R && R->CommCount && R->CommCount(c->comm, &lw) != ncclSuccess) lw = -1;
-    if (lib_rank_out) *lib_rank_out = lr;
-    if (lib_world_out) *lib_world_out = lw;
-    return RMAV_OK;
-}
-
-int rmav_comm_create(rmav_comm *out, const void *id, int rank, int world, int device) {
-    if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!id || world <= 0 || rank < 0 || rank >= world) return rmav_fail(RMAV_ERR_INVALID, "need id and 0 <= rank < world");
-    const int ndev = rmav_device_count();
-    if (ndev <= 0) return rmav_fail(RMAV_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return rmav_fail(RMAV_ERR_INVALID, "device %d out of range [0,%d)", device, ndev);
-    RcclApi *R = rccl();
-    if (!R) return rmav_fail(RMAV_ERR_NO_DEVICE, "librccl.so.1 could not be loaded");
-    DeviceGuard guard(device);
-    if (!guard.ok) return rmav_fail(RMAV_ERR_HIP, "hipSetDevice(%d) failed", device);
-    ncclUniqueId uid;
-    memcpy(&uid, id, sizeof(uid));
-    rmav_comm c = new (std::nothrow) rmav_comm_s();
-    if (!c) return rmav_fail(RMAV_ERR_ALLOC, "host allocation failed");
-    memset(c, 0, sizeof(*c));
-    c->magic = kCommMagic;
-    c->rank = rank;
-    c->world = world;
-    c->device = device;
-    ncclResult_t r = R->CommInitRank(&c->comm, world, uid, rank);
-    if (r != ncclSuccess) {
-        delete c;
-        return rmav_fail(RMAV_ERR_HIP, "ncclCommInitRank failed: %s", R->GetErrorString ? R->GetErrorString(r) : "RCCL error");
-    }
-    // A high-priority stream: HIP multiplexes all streams of one priority onto a few hardware queues (GPU_MAX_HW_QUEUES,
-    // 4 by default) round-robin, and a process that also runs torch has dozens - when the communicator's stream lands on
-    // the compute stream's hardware queue their packets serialise (measured: a 131 072-env rollout 85 -> 108 us with the
-    // default mapping, 189 us with GPU_MAX_HW_QUEUES=8, 93 us with 2).  Priority levels have queues of their own.
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    hipError_t e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi);
-    c->depth = kExchangeDepth;
-    for (int k = 0; k < kExchangeDepth && e == hipSuccess; ++k) {
-        // device-scope release: these events only order streams of this GPU
-        const unsigned evf = hipEventDisableTiming | hipEventReleaseToDevice;
-        e = hipEventCreateWithFlags(&c->ready[k], evf);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done[k], evf);
-    }
-    // the words k_wait_arrivals writes when it gives up on an armed launch (pinned host memory: the host reads them for free)
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->timeout_seq, kExchangeDepth * sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        memset(c->timeout_seq, 0, kExchangeDepth * sizeof(uint32_t));
-        e = hipHostGetDevicePointer((void **)&c->timeout_seq_dev, c->timeout_seq, 0);
-    }
-    if (e == hipSuccess) e = hipMalloc((void **)&c->started, sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->started, 0, sizeof(uint32_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)rmav_comm_destroy(c);
-        return rmav_fail(RMAV_ERR_HIP, "stream / event creation for the communicator failed: %s", hipGetErrorString(e));
-    }
-    // Hand-over from the compute stream to the communicator's stream without an event: hipEventRecord puts a barrier
-    // packet into the COMPUTE stream (~8 us in front of the next rollout launch, measured); a one-thread kernel that
-    // publishes the post number in a signal word, and hipStreamWaitValue32 on the communicator's stream, cost the
-    // compute stream one tiny launch (hipStreamWriteValue32 in its place: +3 us per post, measured).  Falls back to the event when the device cannot wait on memory.
-    int can_wait = 0;
-    (void)hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, device);
-    if (can_wait) {
-        if (hipExtMallocWithFlags((void **)&c->flag, 8, hipMallocSignalMemory) != hipSuccess) {
-            (void)hipGetLastError();
-            c->flag = nullptr;
-        } else {
-            (void)hipMemset(c->flag, 0, 8);
-        }
-    }
-    *out = c;
-    return RMAV_OK;
-}
-
-int rmav_comm_destroy(rmav_comm c) {
-    if (!c || c->magic != kCommMagic) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_comm");
-    DeviceGuard guard(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    RcclApi *R = rccl();
-    if (R && c->comm) (void)R->CommDestroy(c->comm);
-    for (int k = 0; k < kExchangeDepth; ++k) {
-        if (c->ready[k]) (void)hipEventDestroy(c->ready[k]);
-        if (c->done[k]) (void)hipEventDestroy(c->done[k]);
-        if (c->send[k]) (void)hipFree(c->send[k]);
-        if (c->recv[k]) (void)hipFree(c->recv[k]);
-    }
-    if (c->flag) (void)hipFree(c->flag);
-    if (c->arrive) (void)hipFree(c->arrive);
-    if (c->timeout_seq) (void)hipHostFree(c->timeout_seq);
-    if (c->started) (void)hipFree(c->started);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->armed_by && c->armed_by->magic == kMagic && c->armed_by->xchg.comm == c) {
-        // a handle still points at this communicator: disarm it, or its next rollout would dereference freed memory
-        c->armed_by->xchg.armed = c->armed_by->xchg.fired = false;
-        c->armed_by->xchg.comm = nullptr;
-    }
-    c->magic = 0;
-    delete c;
-    return RMAV_OK;
-}
-
-int rmav_comm_warmup(rmav_comm c, double timeout_s) {
-    if (!c || c->magic != kCommMagic) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_comm");
-    RcclApi *R = rccl();
-    if (!R) return rmav_fail(RMAV_ERR_NO_DEVICE, "librccl.so.1 could not be loaded");
-    DeviceGuard guard(c->device);
-    int32_t *buf = nullptr;   // [1 + world]: this rank's word, then the gathered words
-    HIP_TRY(hipMalloc((void **)&buf, sizeof(int32_t) * (size_t)(1 + c->world)));
-    hipEvent_t ev = nullptr;
-    hipError_t e = hipMemsetAsync(buf, 0, sizeof(int32_t) * (size_t)(1 + c->world), c->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    int rc = RMAV_OK;
-    if (e != hipSuccess) {
-        rc = rmav_fail(RMAV_ERR_HIP, "rmav_comm_warmup: %s", hipGetErrorString(e));
-    } else {
-        // RCCL connects its transports inside the first collective's enqueue (a host-side exchange with the peers): this is the
-        // call that may block when a peer is gone, and it touches no handle's stream
-        const ncclResult_t r = R->AllGather(buf, buf + 1, 1, ncclInt32, c->comm, c->stream);
-        if (r != ncclSuccess) rc = rmav_fail(RMAV_ERR_HIP, "ncclAllGather failed: %s", R->GetErrorString ? R->GetErrorString(r) : "RCCL error");
-    }
-    if (rc == RMAV_OK && hipEventRecord(ev, c->stream) != hipSuccess) rc = rmav_fail(RMAV_ERR_HIP, "hipEventRecord failed");
-    if (rc == RMAV_OK) {
-        timespec t0;
-        clock_gettime(CLOCK_MONOTONIC, &t0);
-        for (;;) {
-            const hipError_t q = hipEventQuery(ev);
-            if (q == hipSuccess) break;
-            (void)hipGetLastError();
-            if (q != hipErrorNotReady) { rc = rmav_fail(RMAV_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(q)); break; }
-            timespec t1;
-            clock_gettime(CLOCK_MONOTONIC, &t1);
-            if (timeout_s >= 0 && (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec) > timeout_s) {
-                rc = rmav_fail(RMAV_ERR_TIMEOUT, "the warm-up collective did not complete within %.3f s", timeout_s);
-                break;
-            }
-            timespec nap = {0, 50000};
-            nanosleep(&nap, nullptr);
-        }
-    }
-    // (on a time-out the collective may still be in flight: the buffer and the event are left to the process, not freed under it)
-    if (rc != RMAV_ERR_TIMEOUT) {
-        if (ev) (void)hipEventDestroy(ev);
-        (void)hipFree(buf);
-    }
-    return rc;
-}
-
-int rmav_pack_stats(rmav_handle h, int64_t cmax, int32_t *send_out) {
-    CHECK_HANDLE(h);
-    if (!(h->flags & RMAV_F_TRACK_EPISODES))
-        return rmav_fail(RMAV_ERR_INVALID, "handle was created without RMAV_F_TRACK_EPISODES");
-    if (!send_out || cmax < h->n) return rmav_fail(RMAV_ERR_INVALID, "send_out is NULL or cmax < num_envs");
-    hipLaunchKernelGGL(k_pack_stats, dim3((unsigned)((cmax + 255) / 256)), dim3(256), 0, h->stream,
-                       (const float *)h->last_ret, (const EnvRec *)h->rec, h->n, cmax, send_out);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-namespace {
-// shard of rank c->rank out of n_total, checked against the handle
-int check_shard(rmav_handle h, rmav_comm c, int64_t n_total, int64_t *cmax_out) {
-    if (!c || c->magic != kCommMagic) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_comm");
-    if (!(h->flags & RMAV_F_TRACK_EPISODES))
-        return rmav_fail(RMAV_ERR_INVALID, "handle was created without RMAV_F_TRACK_EPISODES");
-    if (c->device != h->device) return rmav_fail(RMAV_ERR_INVALID, "communicator and handle live on different devices");
-    const int64_t W = c->world, base = n_total / W, rem = n_total % W;
-    if (n_total <= 0 || base == 0) return rmav_fail(RMAV_ERR_INVALID, "n_total must be >= the number of ranks");
-    const int64_t count = base + (c->rank < rem ? 1 : 0), start = c->rank * base + (c->rank < rem ? c->rank : rem);
-    if (h->n != count || (int64_t)h->env_base != start)
-        return rmav_fail(RMAV_ERR_INVALID, "rank %d of %d must own envs [%lld, %lld) of %lld; the handle owns [%llu, %llu)", c->rank,
-                    c->world, (long long)start, (long long)(start + count), (long long)n_total,
-                    (unsigned long long)h->env_base, (unsigned long long)(h->env_base + (uint64_t)h->n));
-    *cmax_out = base + (rem ? 1 : 0);
-    return RMAV_OK;
-}
-}  // namespace
-
-namespace {
-// Common front of _arm and _post: shard check, buffers, and the buffer pair of the next post (host-side back pressure).
-int exchange_slot(rmav_handle h, rmav_comm c, int64_t n_total, int64_t *cmax_out, int *slot_out) {
-    int64_t cmax = 0;
-    if (int rc = check_shard(h, c, n_total, &cmax)) return rc;
-    RcclApi *R = rccl();
-    if (!R) return rmav_fail(RMAV_ERR_NO_DEVICE, "librccl.so.1 could not be loaded");
-    if (cmax > c->cmax) {   // (re)allocate the buffer pairs
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-        for (int k = 0; k < c->depth; ++k) {
-            if (c->send[k]) (void)hipFree(c->send[k]);
-            if (c->recv[k]) (void)hipFree(c->recv[k]);
-            c->send[k] = c->recv[k] = nullptr;
-            c->used[k] = false;
-            if (hipMalloc((void **)&c->send[k], (size_t)(2 * cmax) * sizeof(int32_t)) != hipSuccess ||
-                hipMalloc((void **)&c->recv[k], (size_t)(2 * cmax) * sizeof(int32_t) * (size_t)c->world) != hipSuccess) {
-                (void)hipGetLastError();
-                c->cmax = 0;
-                return rmav_fail(RMAV_ERR_ALLOC, "device allocation for the exchange buffers failed");
-            }
-            // an armed launch writes only this rank's envs: the padding up to cmax stays zero from here on
-            HIP_TRY(hipMemsetAsync(c->send[k], 0, (size_t)(2 * cmax) * sizeof(int32_t), c->stream));
-        }
-        if (c->arrive) (void)hipFree(c->arrive);
-        c->arrive = nullptr;
-        const size_t words = (size_t)((cmax + 31) / 32);
-        if (hipMalloc((void **)&c->arrive, words * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->cmax = 0;
-            return rmav_fail(RMAV_ERR_ALLOC, "device allocation for the exchange buffers failed");
-        }
-        HIP_TRY(hipMemsetAsync(c->arrive, 0, words * sizeof(uint32_t), c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->cmax = cmax;
-    }
-    const int k = c->posts % c->depth;
-    // The gather that last used this buffer pair (`depth` posts ago) must have finished before the pack overwrites its
-    // send half.  In a GPU-bound loop the host runs far ahead of the device, so with two pairs that gather has usually not
-    // even started when the host gets here, and a device-side wait (hipStreamWaitEvent = a barrier packet in the COMPUTE
-    // stream) was inserted in front of nearly every pack: +8 us per rollout, measured.  So the HOST waits instead - back
-    // pressure that bounds its lead to `depth` rollouts (>= 0.5 ms of queued GPU work at depth 8) and puts nothing into
-    // the compute stream.
-    if (c->used[k] && hipEventQuery(c->done[k]) != hipSuccess) {
-        (void)hipGetLastError();
-        HIP_TRY(hipEventSynchronize(c->done[k]));
-    }
-    *cmax_out = cmax;
-    *slot_out = k;
-    return RMAV_OK;
-}
-}  // namespace
-
-int rmav_allgather_stats_arm(rmav_handle h, rmav_comm c, int64_t n_total) {
-    CHECK_HANDLE(h);
-    if (h->xchg.armed) return rmav_fail(RMAV_ERR_INVALID, "an exchange is already armed on this handle: post it first");
-    if (c && c->magic == kCommMagic && c->armed_by && c->armed_by != h)
-        return rmav_fail(RMAV_ERR_INVALID, "this communicator is armed by another handle: post that exchange first");
-    int64_t cmax = 0;
-    int k = 0;
-    if (int rc = exchange_slot(h, c, n_total, &cmax, &k)) return rc;
-    h->xchg.armed = true;
-    h->xchg.fired = false;
-    h->xchg.stale = false;
-    h->xchg.comm = c;
-    c->armed_by = h;
-    h->xchg.slot = k;
-    h->xchg.cmax = cmax;
-    h->xchg.seq = (uint32_t)(c->posts + 1);
-    h->xchg.expected = 0;
-    return RMAV_OK;
-}
-
-int rmav_allgather_stats_post(rmav_handle h, rmav_comm c, int64_t n_total) {
-    CHECK_HANDLE(h);
-    int64_t cmax = 0;
-    int k = 0;
-    RcclApi *R = rccl();
-    const bool armed = h->xchg.armed;
-    if (armed && h->xchg.comm != c) return rmav_fail(RMAV_ERR_INVALID, "the handle's armed exchange belongs to another communicator");
-    if (armed) {   // allocated and back-pressured when it was armed
-        if (!R) return rmav_fail(RMAV_ERR_NO_DEVICE, "librccl.so.1 could not be loaded");
-        if (int rc = check_shard(h, c, n_total, &cmax)) return rc;
-        if (cmax != h->xchg.cmax) return rmav_fail(RMAV_ERR_INVALID, "n_total differs from the armed exchange's");
-        cmax = h->xchg.cmax;
-        k = h->xchg.slot;
-        h->xchg.armed = false;
-        h->xchg.comm = nullptr;
-        c->armed_by = nullptr;
-    } else if (int rc = exchange_slot(h, c, n_total, &cmax, &k)) {
-        return rc;
-    }
-    // (the gather that last used this buffer pair has finished - exchange_slot waited for it - so its time-out word is history)
-    c->timeout_seq[k] = 0;
-    c->slot_seq[k] = (uint32_t)(c->posts + 1);
-    c->armed_slot[k] = armed && h->xchg.fired && !h->xchg.stale;
-    if (c->armed_slot[k]) {
-        // the rollout launch itself wrote the snapshot and its wavefronts' arrival words: nothing enters the compute stream.
-        // The wait is bounded (k_wait_arrivals: 2 s from the moment the armed launch begins): past that the waiter poisons this
-        // rank's payload, notes the post number in the pair's time-out word and lets the gather go ahead - the peers get their
-        // collective either way, and only THIS post reports RMAV_ERR_TIMEOUT.
-        hipLaunchKernelGGL(k_wait_arrivals, dim3(1), dim3(256), 0, c->stream, (const uint32_t *)c->arrive, h->xchg.expected,
-                           h->xchg.seq, h->xchg.no_start ? (const uint32_t *)nullptr : (const uint32_t *)c->started, kArrivalWaitTicks,
-                           kArrivalTotalTicks, c->timeout_seq_dev + k, c->send[k], cmax);
-        HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(k_pack_stats, dim3((unsigned)((cmax + 255) / 256)), dim3(256), 0, h->stream,
-                           (const float *)h->last_ret, (const EnvRec *)h->rec, h->n, cmax, c->send[k]);
-        HIP_TRY(hipGetLastError());
-        if (c->flag) {
-            const uint32_t seq = (uint32_t)(c->posts + 1);
-            hipLaunchKernelGGL(k_signal, dim3(1), dim3(1), 0, h->stream, c->flag, seq);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamWaitValue32(c->stream, c->flag, seq, hipStreamWaitValueGte, 0xFFFFFFFFu));
-        } else {
-            HIP_TRY(hipEventRecord(c->ready[k], h->stream));
-            HIP_TRY(hipStreamWaitEvent(c->stream, c->ready[k], 0));
-        }
-    }
-    RCCL_TRY(R->AllGather(c->send[k], c->recv[k], (size_t)(2 * cmax), ncclInt32, c->comm, c->stream));
-    HIP_TRY(hipEventRecord(c->done[k], c->stream));
-    c->used[k] = true;
-    c->posts += 1;
-    return RMAV_OK;
-}
-
-int rmav_allgather_stats_result(rmav_handle h, rmav_comm c, int64_t n_total, float *returns_out, int32_t *lengths_out) {
-    CHECK_HANDLE(h);
-    int64_t cmax = 0;
-    if (int rc = check_shard(h, c, n_total, &cmax)) return rc;
-    if (!returns_out || !lengths_out) return rmav_fail(RMAV_ERR_INVALID, "returns_out / lengths_out are required (device pointers)");
-    if (c->posts == 0 || cmax != c->cmax) return rmav_fail(RMAV_ERR_INVALID, "no exchange of this size has been posted");
-    const int k = (c->posts - 1) % c->depth;
-    // (known only if the waiter has already run; rmav_allgather_stats_wait knows for certain.  Either way the payload of a
-    // timed-out post is poisoned - return NaN, length -1 for this rank's envs - on every rank.)
-    if (c->armed_slot[k] && c->timeout_seq[k] == c->slot_seq[k])
-        return rmav_fail(RMAV_ERR_TIMEOUT, "the armed rollout launch of this exchange did not complete within 2 s of starting");
-    HIP_TRY(hipStreamWaitEvent(h->stream, c->done[k], 0));
-    hipLaunchKernelGGL(k_unpack_stats, dim3((unsigned)((n_total + 255) / 256)), dim3(256), 0, h->stream,
-                       (const int32_t *)c->recv[k], n_total, (int32_t)c->world, cmax, returns_out, lengths_out);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-int rmav_allgather_stats_wait(rmav_comm c, double timeout_s) {
-    if (!c || c->magic != kCommMagic) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_comm");
-    if (c->posts == 0) return RMAV_OK;
-    DeviceGuard guard(c->device);
-    const int k = (c->posts - 1) % c->depth;
-    timespec t0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (;;) {
-        const hipError_t e = hipEventQuery(c->done[k]);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) return rmav_fail(RMAV_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
-        (void)hipGetLastError();
-        timespec t1;
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        if (timeout_s >= 0 && (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec) > timeout_s)
-            return rmav_fail(RMAV_ERR_TIMEOUT, "the posted exchange did not complete within %.3f s", timeout_s);
-        timespec nap = {0, 50000};
-        nanosleep(&nap, nullptr);
-    }
-    if (c->armed_slot[k] && c->timeout_seq[k] == c->slot_seq[k])
-        return rmav_fail(RMAV_ERR_TIMEOUT, "the armed rollout launch of this exchange did not complete within 2 s of starting");
-    return RMAV_OK;
-}
-
-int rmav_allgather_stats(rmav_handle h, rmav_comm c, int64_t n_total, float *returns_out, int32_t *lengths_out) {
-    if (!returns_out || !lengths_out) return rmav_fail(RMAV_ERR_INVALID, "returns_out / lengths_out are required (device pointers)");
-    if (int rc = rmav_allgather_stats_post(h, c, n_total)) return rc;
-    return rmav_allgather_stats_result(h, c, n_total, returns_out, lengths_out);
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit and never resets: rmav_step's obs is its terminal observation");
+    return rollout_impl(h, 1, RMAV_ACT_BUFFER, actions, nullptr, obs_out, rew_out, done_out, nullptr, mem, layout, 1, 0, true, final_obs_out,
+                        trunc_out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// rmav_handle.hpp - what the translation units behind the C ABI share: the handle / communicator structs, the error helper, and
-// the one entry point of the second translation unit.  librmav.so is built from two of them because the policy-in-kernel
-// rollouts must be compiled WITHOUT the SLP vectoriser (rmav_policy_abi.hip explains why); everything else keeps it.
+// rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
+// helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus two that only launch kernels (rmav_policy_abi.hip,
+// rmav_range_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -108,6 +109,34 @@ inline rmav::RangeArgs range_args(const rmav_env_s *h, uint32_t mask) {
     return r;
 }
 inline rmav::RangeArgs range_args(const rmav_env_s *h) { return range_args(h, h->range_mask); }
+
+RMAV_INTERNAL inline bool valid(rmav_handle h) { return h && h->magic == kMagic; }
+
+// makes the handle's device current for the duration of an entry point
+struct RMAV_INTERNAL DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+#define CHECK_HANDLE(h)                                                                            \
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");                           \
+    DeviceGuard guard_(h->device);                                                                 \
+    if (!guard_.ok) return rmav_fail(RMAV_ERR_HIP, "hipSetDevice(%d) failed", h->device)
+
+// rmav_abi.hip, for rmav_ppo_abi.hip as well: the argument block every stepping launch starts from; the handle's scratch grown to
+// `bytes`; and what a ranged handle's policy kernels are fed when the caller passed none (identity tables, an unread boot_out)
+RMAV_INTERNAL rmav::RolloutArgs base_args(rmav_handle h);
+RMAV_INTERNAL int ensure_scratch(rmav_handle h, size_t bytes);
+RMAV_INTERNAL int ensure_ident_norm(rmav_handle h);
+RMAV_INTERNAL int ensure_boot_scratch(rmav_handle h, size_t bytes);
 
 constexpr int kExchangeDepth = 8;   // buffer pairs of the overlapped statistics exchange
 // bounds of k_wait_arrivals, in ticks of the 100 MHz wall clock: 2 s once the armed launch has begun, 10 min overall

@@ -948,37 +948,4 @@ __global__ __launch_bounds__(kBlock) void k_control(const float *state, int64_t 
     }
 }
 
-// ReinmavEnv: the built-in controller's command (F, Mx, My, Mz) at the env's current (state, t)
-[[maybe_unused]] static __global__ __launch_bounds__(kBlock) void k_control_reinmav(const float *state, const double *env_time, int64_t n,
-                                                            float *act_out, uint32_t flags, const ReinmavP p) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s[13], fm[4];
-#pragma unroll
-    for (int c = 0; c < 13; ++c) s[c] = state[(int64_t)c * n + i];
-    double R[3][3];
-    {
-        const double q[4] = {s[6], s[7], s[8], s[9]};
-        reinmav_quat2mat(q, R);
-    }
-    reinmav_controller(p, s, R, env_time[i], fm);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (flags & F_AOS) act_out[i * 4 + c] = (float)fm[c];
-        else act_out[(int64_t)c * n + i] = (float)fm[c];
-    }
-}
-
-// [dim][n] <-> [n][dim]
-[[maybe_unused]] static __global__ __launch_bounds__(kBlock) void k_soa_to_aos(const float *src, float *dst, int64_t n, int dim) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int c = 0; c < dim; ++c) dst[i * dim + c] = src[(int64_t)c * n + i];
-}
-[[maybe_unused]] static __global__ __launch_bounds__(kBlock) void k_aos_to_soa(const float *src, float *dst, int64_t n, int dim) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int c = 0; c < dim; ++c) dst[(int64_t)c * n + i] = src[i * dim + c];
-}
-
 }  // namespace rmav

@@ -1,0 +1,388 @@
+// rmav_ppo_abi.hip - the C ABI of include/rmav_ppo.h: policy weights, the policy-in-kernel rollouts (their kernels are launched from
+// rmav_policy_abi.hip), GAE, and the observation / return normalisers.
+#include <cstdint>
+#include <cstring>
+
+#include "rmav_handle.hpp"
+#include "rmav_pack_policy.hpp"
+#include "rmav_obs_norm.hpp"
+#include "rmav_ret_norm.hpp"   // (brings rmav_gae.hpp)
+
+using namespace rmav;
+
+// =================================================================================================
+extern "C" {
+
+int64_t rmav_policy_weight_count(int kind) {
+    return dispatch_kind<ALL_KINDS>(kind, [](auto k) { return (int64_t)PolicyLayout<Dims<decltype(k)::value>::NS>::TOTAL; });
+}
+
+int64_t rmav_policy_weight_count_bf16(void) { return MfmaLayout::TOTAL; }
+int64_t rmav_policy_weight_count_f32_mfma(void) { return Mfma32Layout::TOTAL; }
+int64_t rmav_policy_weight_count_shared(void) { return MfmaLayout::NET + 4; }
+
+static int pack_policy_impl(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
+                            const int32_t *idx_hi, int64_t n_out, float *weights_out, bool f16) {
+    CHECK_HANDLE(h);
+    if (n_params <= 0 || n_params > kPackMaxParams) return rmav_fail(RMAV_ERR_INVALID, "n_params must be in [1, %d]", kPackMaxParams);
+    if (!params || !sizes || !idx_lo || !idx_hi || !weights_out || n_out <= 0)
+        return rmav_fail(RMAV_ERR_INVALID, "params, sizes, idx_lo, idx_hi, weights_out are required and n_out > 0");
+    PackSrc src;
+    memset(&src, 0, sizeof(src));
+    int64_t end = 0;
+    for (int k = 0; k < n_params; ++k) {
+        if (!params[k] || sizes[k] < 0) return rmav_fail(RMAV_ERR_INVALID, "parameter %d is NULL or has a negative size", k);
+        end += sizes[k];
+        if (end > 0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many parameter elements");
+        src.p[k] = params[k];
+        src.end[k] = (int32_t)end;
+    }
+    src.n = n_params;
+    const dim3 grid((unsigned)((n_out + 255) / 256));
+    if (f16) {
+        if (n_out != MfmaLayout::TOTAL && n_out != MfmaLayout::NET + 4)
+            return rmav_fail(RMAV_ERR_INVALID, "n_out must be rmav_policy_weight_count_bf16() = %d or rmav_policy_weight_count_shared() = %d",
+                             (int)MfmaLayout::TOTAL, (int)MfmaLayout::NET + 4);
+        hipLaunchKernelGGL(k_pack_policy<true>, grid, dim3(256), 0, h->stream, src, idx_lo, idx_hi, n_out, weights_out, (int32_t)MfmaLayout::NET,
+                           (int32_t)MfmaLayout::A2, (int32_t)MfmaLayout::A3, (int32_t)MfmaLayout::B1, -2.0f * kTanhScale, -2.0f);
+    } else {
+        hipLaunchKernelGGL(k_pack_policy<false>, grid, dim3(256), 0, h->stream, src, idx_lo, idx_hi, n_out, weights_out, 1, 0, 0, 0, 1.0f, 1.0f);
+    }
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_pack_policy(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
+                     const int32_t *idx_hi, int64_t n_out, float *weights_out) {
+    return pack_policy_impl(h, n_params, params, sizes, idx_lo, idx_hi, n_out, weights_out, false);
+}
+int rmav_pack_policy_f16(rmav_handle h, int n_params, const float *const *params, const int64_t *sizes, const int32_t *idx_lo,
+                         const int32_t *idx_hi, int64_t n_out, float *weights_out) {
+    return pack_policy_impl(h, n_params, params, sizes, idx_lo, idx_hi, n_out, weights_out, true);
+}
+
+// ---- rmav_rollout_policy / _boot / _norm: the checks all three make, in the order they make them, and the launch ------------------
+// The refusal of an actor without variant kernels (policy_has_variants, rmav_handle.hpp): `who` = the entry point or the handle's feature,
+// `what` = the kind of kernel the fp32 vector-ALU and bf16 actors lack.  RMAV_OK for the three actors that have them.
+static int need_variants(int precision, const char *who, const char *what) {
+    if (policy_has_variants(policy_kmode(precision))) return RMAV_OK;
+    return rmav_fail(RMAV_ERR_INVALID, "%s runs RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA or RMAV_POLICY_F16_SHARED "
+                                       "(the fp32 vector-ALU and bf16 actors have no %s kernel), got precision %d", who, what, precision);
+}
+// boot_out: checked (and named) only when the entry point requires it
+static int check_policy_args(int32_t n_steps, const float *weights, const float *logp_out, const float *value_out, bool need_boot, const float *boot_out) {
+    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
+    if (!weights || !logp_out || !value_out || (need_boot && !boot_out))
+        return rmav_fail(RMAV_ERR_INVALID, need_boot ? "weights, logp_out, value_out and boot_out are required (device pointers)"
+                                                     : "weights, logp_out and value_out are required (device pointers)");
+    if ((reinterpret_cast<uintptr_t>(weights) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "weights must be 16-byte aligned");
+    return RMAV_OK;
+}
+// one fused launch over all envs (it may carry an armed exchange's snapshot), then the step counter
+static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out, float *rew_out,
+                              uint8_t *done_out, float *logp_out, float *value_out, int precision, const BootArgs *bt, const NormArgs *nm) {
+    RolloutArgs a = base_args(h);
+    a.n_steps = n_steps;
+    a.act_out = actions_out;
+    a.obs_out = obs_out;
+    a.rew_out = rew_out;
+    a.done_out = done_out;
+    a.policy_w = weights;
+    a.logp_out = logp_out;
+    a.val_out = value_out;
+    h->xchg.allow = true;
+    // A handle with a parameter range runs ONE ranged kernel per actor, the normalised one: a call without
+    // statistics gets identity tables - z then has the bits of x (rmav_ppo.h) - and a call on a time-limited handle that asked for no
+    // bootstrap term a boot_out of the handle's own.
+    BootArgs bt_r{};
+    NormArgs nm_r{};
+    if (h->range_mask) {
+        if (int rc = need_variants(precision, "a handle with a parameter range", "ranged")) return rc;
+        if (!nm) {
+            if (int rc = ensure_ident_norm(h)) return rc;
+            nm_r.tab = h->ident_norm;
+            nm = &nm_r;
+        }
+        if (h->time_limit > 0 && !bt) {
+            if (int rc = ensure_boot_scratch(h, (size_t)n_steps * (size_t)h->n * sizeof(float))) return rc;
+            bt_r.boot_out = h->boot_scratch;
+            bt = &bt_r;
+        }
+    }
+    if (int rc = rmav_launch_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
+    h->t += (uint64_t)n_steps;
+    return RMAV_OK;
+}
+
+int rmav_rollout_policy(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out,
+                        float *obs_out, float *rew_out, uint8_t *done_out, float *logp_out,
+                        float *value_out, int precision) {
+    CHECK_HANDLE(h);
+    if (precision < RMAV_POLICY_FP32 || precision > RMAV_POLICY_F16_SHARED)
+        return rmav_fail(RMAV_ERR_INVALID, "precision must be one of RMAV_POLICY_FP32 ... RMAV_POLICY_F16_SHARED (rmav_policy_precision)");
+    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
+    if (h->time_limit > 0)
+        if (int rc = need_variants(precision, "a time-limited handle", "time-limited")) return rc;
+    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, nullptr, nullptr);
+}
+
+int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weights, float *actions_out, float *obs_out, float *rew_out,
+                             uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out, int precision) {
+    CHECK_HANDLE(h);
+    if (h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap");
+    if (h->time_limit <= 0)
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_rollout_policy_boot needs an episode time limit on the handle (rmav_set_time_limit)");
+    if (int rc = need_variants(precision, "rmav_rollout_policy_boot", "time-limited")) return rc;
+    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, true, boot_out)) return rc;
+    const BootArgs bt{boot_out, trunc_out};
+    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, nullptr);
+}
+
+// ---- learner-side helpers on the trajectory ----------------------------------------------------
+// The one launcher of the GAE family.  with_boot (rmav_gae_boot): k_gae_boot, which adds the bootstrap term `boot` of the truncated steps;
+// stats (rmav_gae_norm): k_gae_norm<with_boot>, which normalises every reward as it is loaded (csrc/rmav_ret_norm.hpp)
+static int gae_impl(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, bool with_boot, const float *boot,
+                    const RetNormStats *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
+    if (!rew || !done || !values || (with_boot && !boot) || !adv_out || !ret_out)
+        return rmav_fail(RMAV_ERR_INVALID, with_boot ? "rew, done, values, boot, adv_out and ret_out are required (device pointers)"
+                                                     : "rew, done, values, adv_out and ret_out are required (device pointers)");
+    const unsigned nblk = (unsigned)((h->n + 255) / 256);
+    double *partial = nullptr;
+    if (sums_out) {
+        if (int rc = ensure_scratch(h, (size_t)nblk * 2 * sizeof(double))) return rc;
+        partial = (double *)h->scratch;
+    }
+    if (stats && with_boot)
+        hipLaunchKernelGGL(k_gae_norm<true>, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, stats, adv_out, ret_out, h->n, n_steps,
+                           gamma, lam, reward_scale, partial);
+    else if (stats)
+        hipLaunchKernelGGL(k_gae_norm<false>, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, stats, adv_out, ret_out, h->n, n_steps,
+                           gamma, lam, reward_scale, partial);
+    else if (with_boot)
+        hipLaunchKernelGGL(k_gae_boot, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, boot, adv_out, ret_out, h->n, n_steps, gamma, lam,
+                           reward_scale, partial);
+    else
+        hipLaunchKernelGGL(k_gae, dim3(nblk), dim3(256), 0, h->stream, rew, done, values, adv_out, ret_out, h->n, n_steps, gamma, lam, reward_scale,
+                           partial);
+    HIP_TRY(hipGetLastError());
+    if (sums_out) {
+        hipLaunchKernelGGL(k_gae_fold, dim3(1), dim3(256), 0, h->stream, (const double *)partial, (int)nblk, sums_out);
+        HIP_TRY(hipGetLastError());
+    }
+    return RMAV_OK;
+}
+
+int rmav_gae(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values,
+             float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    CHECK_HANDLE(h);
+    return gae_impl(h, n_steps, rew, done, values, false, nullptr, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
+}
+
+int rmav_gae_boot(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
+                  float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    CHECK_HANDLE(h);
+    if (h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (use rmav_gae)");
+    return gae_impl(h, n_steps, rew, done, values, true, boot, nullptr, gamma, lam, reward_scale, adv_out, ret_out, sums_out);
+}
+
+int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rstd) {
+    CHECK_HANDLE(h);
+    if (!x || count < 0) return rmav_fail(RMAV_ERR_INVALID, "x is NULL or count < 0");
+    if ((reinterpret_cast<uintptr_t>(x) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "x must be 16-byte aligned");
+    if (count == 0) return RMAV_OK;
+    int64_t blocks = (count / 4 + 255) / 256;
+    if (blocks < 1) blocks = 1;
+    if (blocks > 4096) blocks = 4096;   // grid-stride: 16 blocks per CU keep the memory system full
+    hipLaunchKernelGGL(k_affine, dim3((unsigned)blocks), dim3(256), 0, h->stream, x, count, mean, rstd);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// ---- observation normalisation (VecNormalize): running statistics on the device, csrc/rmav_obs_norm.hpp ------------------
+namespace {
+int check_norm_handle(rmav_handle h, const char *what) {
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "%s runs the four quadrotor kinds, not RMAV_REINMAV", what);
+    return RMAV_OK;
+}
+int check_stats(const void *stats) {
+    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_obs_norm_bytes() bytes)");
+    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
+    return RMAV_OK;
+}
+// the addressing of an observation array (ObsShape); n_rows >= 1 checked by the caller
+int obs_shape(rmav_handle h, int layout, int32_t n_rows, int64_t pitch, ObsShape &sh) {
+    const int ns = kStateDim[h->kind];
+    if (layout != RMAV_SOA && layout != RMAV_AOS) return rmav_fail(RMAV_ERR_INVALID, "layout must be RMAV_SOA or RMAV_AOS");
+    if (layout == RMAV_SOA) {
+        if (pitch == 0) pitch = h->n;
+        if (pitch < h->n || pitch > (int64_t)0x3fffffff) return rmav_fail(RMAV_ERR_INVALID, "pitch must be 0 (= N) or in [N, 2^30)");
+        sh = ObsShape{h->n, (int64_t)ns * pitch, pitch, 1, n_rows, ns};
+    } else {
+        if (pitch != 0) return rmav_fail(RMAV_ERR_INVALID, "pitch must be 0 with RMAV_AOS");
+        sh = ObsShape{h->n, h->n * ns, 1, ns, n_rows, ns};
+    }
+    return RMAV_OK;
+}
+}  // namespace
+
+int64_t rmav_obs_norm_bytes(void) { return (int64_t)sizeof(ObsNormStats); }
+
+int rmav_obs_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_norm_init")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
+        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    hipLaunchKernelGGL(k_obs_norm_init, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, (int32_t)kStateDim[h->kind], clip, eps, count0);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_obs_moments(rmav_handle h, const float *obs, int layout, int32_t n_rows, int64_t pitch, double *batch_out) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_moments")) return rc;
+    if (!obs || !batch_out) return rmav_fail(RMAV_ERR_INVALID, "obs and batch_out are required (device pointers)");
+    if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
+    ObsShape sh;
+    if (int rc = obs_shape(h, layout, n_rows > 0 ? n_rows : 1, pitch, sh)) return rc;
+    sh.n_rows = n_rows;   // 0 rows: an empty record (count 0), which rmav_obs_norm_merge skips
+    const bool vec = layout == RMAV_SOA && (reinterpret_cast<uintptr_t>(obs) & 15u) == 0 && (sh.feat & 3) == 0;
+    const int64_t cols = vec ? (sh.n + 3) / 4 : sh.n;
+    const int64_t xenv = (cols + 255) / 256;
+    // enough blocks for 256 CUs (8 per CU) when the rows allow it; a thread then walks every rgroups-th row
+    int64_t rgroups = (2048 + xenv * sh.ns - 1) / (xenv * sh.ns);
+    if (rgroups > n_rows) rgroups = n_rows;
+    if (rgroups < 1) rgroups = 1;
+    const int64_t nblk = xenv * rgroups;
+    if (int rc = ensure_scratch(h, (size_t)nblk * sh.ns * sizeof(Moment))) return rc;
+    const dim3 grid((unsigned)nblk, (unsigned)sh.ns);
+    if (vec) hipLaunchKernelGGL(k_obs_moments<true>, grid, dim3(256), 0, h->stream, obs, sh, (int32_t)xenv, (int32_t)rgroups, (Moment *)h->scratch);
+    else hipLaunchKernelGGL(k_obs_moments<false>, grid, dim3(256), 0, h->stream, obs, sh, (int32_t)xenv, (int32_t)rgroups, (Moment *)h->scratch);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_obs_moments_fold, dim3(kNormFeat), dim3(256), 0, h->stream, (const Moment *)h->scratch, (int32_t)nblk, (int32_t)sh.ns, batch_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_obs_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_norm_merge")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
+    if (n_batches == 0) return RMAV_OK;
+    if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 33 doubles on the device)");
+    hipLaunchKernelGGL(k_obs_norm_merge, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, batch, n_batches, (int32_t)kStateDim[h->kind]);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_obs_normalize(rmav_handle h, const void *stats, const float *in, float *out, int layout, int32_t n_rows, int64_t pitch) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_obs_normalize")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
+    if (n_rows == 0) return RMAV_OK;
+    if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
+    ObsShape sh;
+    if (int rc = obs_shape(h, layout, n_rows, pitch, sh)) return rc;
+    const int64_t total = sh.n * sh.ns * (int64_t)n_rows;
+    if ((total + 255) / 256 > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many elements for one launch");
+    hipLaunchKernelGGL(k_obs_normalize, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, (const ObsNormStats *)stats, in, out, sh);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weights, const void *stats, float *actions_out, float *obs_out,
+                             float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out,
+                             int precision) {
+    CHECK_HANDLE(h);
+    if (int rc = check_norm_handle(h, "rmav_rollout_policy_norm")) return rc;
+    if (int rc = need_variants(precision, "rmav_rollout_policy_norm", "normalised")) return rc;
+    if (int rc = check_stats(stats)) return rc;
+    if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
+    if (h->time_limit > 0 && !boot_out)
+        return rmav_fail(RMAV_ERR_INVALID, "boot_out is required on a handle with an episode time limit (as rmav_rollout_policy_boot)");
+    if (h->time_limit <= 0 && (boot_out || trunc_out))
+        return rmav_fail(RMAV_ERR_INVALID, "boot_out / trunc_out need an episode time limit on the handle (rmav_set_time_limit); pass NULL");
+    const BootArgs bt{boot_out, trunc_out};
+    const NormArgs nm{((const ObsNormStats *)stats)->mean_f};
+    return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, &nm);
+}
+
+// ---- return normalisation (the reward half of VecNormalize): one scalar RunningMeanStd on the device, csrc/rmav_ret_norm.hpp -----------
+namespace {
+int check_ret_stats(const void *stats) {
+    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_ret_norm_bytes() bytes)");
+    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
+    return RMAV_OK;
+}
+}  // namespace
+
+int64_t rmav_ret_norm_bytes(void) { return (int64_t)sizeof(RetNormStats); }
+
+int rmav_ret_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
+    CHECK_HANDLE(h);
+    if (int rc = check_ret_stats(stats)) return rc;
+    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
+        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    hipLaunchKernelGGL(k_ret_norm_init, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, clip, eps, count0);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ret_moments(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, float reward_scale, float gamma, float *carry,
+                     double *batch_out) {
+    CHECK_HANDLE(h);
+    if (n_steps < 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be >= 0");
+    if (!batch_out) return rmav_fail(RMAV_ERR_INVALID, "batch_out is required (3 doubles on the device)");
+    if (n_steps > 0 && (!rew || !done || !carry)) return rmav_fail(RMAV_ERR_INVALID, "rew, done and carry are required (device pointers)");
+    const unsigned nblk = n_steps > 0 ? (unsigned)((h->n + 255) / 256) : 0u;   // 0 steps: an empty record, carry untouched
+    if (nblk) {
+        if (int rc = ensure_scratch(h, (size_t)nblk * sizeof(Moment))) return rc;
+        hipLaunchKernelGGL(k_ret_moments, dim3(nblk), dim3(256), 0, h->stream, rew, done, carry, h->n, n_steps, reward_scale, gamma,
+                           (Moment *)h->scratch);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_ret_moments_fold, dim3(1), dim3(256), 0, h->stream, (const Moment *)h->scratch, (int32_t)nblk, batch_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ret_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
+    CHECK_HANDLE(h);
+    if (int rc = check_ret_stats(stats)) return rc;
+    if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
+    if (n_batches == 0) return RMAV_OK;
+    if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 3 doubles on the device)");
+    hipLaunchKernelGGL(k_ret_norm_merge, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, batch, n_batches);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ret_normalize(rmav_handle h, const void *stats, const float *in, float *out, int64_t count, float reward_scale) {
+    CHECK_HANDLE(h);
+    if (int rc = check_ret_stats(stats)) return rc;
+    if (count < 0) return rmav_fail(RMAV_ERR_INVALID, "count must be >= 0");
+    if (count == 0) return RMAV_OK;
+    if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
+    if ((count + 255) / 256 > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "too many elements for one launch");
+    hipLaunchKernelGGL(k_ret_normalize, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, h->stream, (const RetNormStats *)stats, in, out, count,
+                       reward_scale);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
+                  const void *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out) {
+    CHECK_HANDLE(h);
+    if (boot && h->kind == RMAV_REINMAV)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (pass boot = NULL)");
+    if (int rc = check_ret_stats(stats)) return rc;
+    return gae_impl(h, n_steps, rew, done, values, boot != nullptr, boot, (const RetNormStats *)stats, gamma, lam, reward_scale, adv_out, ret_out,
+                    sums_out);
+}
+
+}  // extern "C"

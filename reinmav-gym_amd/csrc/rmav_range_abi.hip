@@ -1,6 +1,6 @@
 // rmav_range_abi.hip - the launches of a handle with a parameter range (rmav_set_env_param_range; include/rmav.h): the single-step
 // kernels k_step_dr and the one-wavefront fused rollouts k_rollout_dr.  A translation unit of its own so that these kernels compile
-// beside the two others instead of lengthening the longest of them; rmav_abi.hip decides what a call launches (action mode, store
+// beside the others instead of lengthening the longest of them; rmav_abi.hip decides what a call launches (action mode, store
 // policy, slices) and comes here only for the launch itself.  The ranged policy rollouts are in rmav_policy_abi.hip.
 #include "rmav_handle.hpp"
 

@@ -1,6 +1,6 @@
 """What the *_build tests and test_resource_usage.py read off a build without a GPU: the assembly listings and hipcc's
 -Rpass-analysis=kernel-resource-usage remarks of `make asm`, the census of the kernel families, and the declared / exported / bound
-check of the C entry points.  `make asm` recompiles all three translation units, so it runs once per process."""
+check of the C entry points.  `make asm` recompiles every translation unit, so it runs once per process."""
 import ctypes as C
 import os
 import re
@@ -8,7 +8,7 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "reinmav-gym_amd")
-UNITS = ("rmav_abi", "rmav_policy_abi", "rmav_range_abi")
+UNITS = ("rmav_abi", "rmav_ppo_abi", "rmav_comm_abi", "rmav_policy_abi", "rmav_range_abi")   # = UNITS of the Makefile
 
 # Every kernel family (prefix of the mangled name) and how many members the library has.  A new family is a new line here.
 RANGED = {"_ZN4rmav9k_step_drILi": 16, "_ZN4rmav12k_rollout_drILi": 72, "_ZN4rmav16k_rollout_nrm_drILi": 8,   # (handles with a parameter range)

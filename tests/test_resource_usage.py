@@ -80,11 +80,11 @@ def test_pair_actors_fit_two_wavefronts_per_simd():
 def test_matrix_core_kernels_have_no_lds_permutes_and_no_compiler_packed_fp32():
     """gfx950 hazard, root-caused in round 5 (profiles/r05/packed_f32_hazard.md, tools/micro/pk_hazard.hip): a packed-fp32 instruction whose
     op_sel selects the HIGH half of src1 for the low result reads zero in lanes 48..63 while a v_mfma_f32_32x32x16_{f16,bf16} executes on
-    the SIMD.  Only the SLP vectoriser emits that form, so NO kernel of the library may contain it (both translation units are built with
+    the SIMD.  Only the SLP vectoriser emits that form, so NO kernel of the library may contain it (every translation unit is built with
     -fno-slp-vectorize, and the Makefile's check_isa step refuses an object that has it).  The matrix-core kernels additionally stay free
     of v_pk_mul_f32 / v_pk_mov_b32 (compiler-only forms) and of LDS permutes (lanes are exchanged with v_permlane32_swap)."""
     bad_form = re.compile(r"v_pk_(fma|mul|add)_f32 .*op_sel:\[[01],1")
-    for unit in ("rmav_abi", "rmav_policy_abi"):
+    for unit in B.UNITS:
         hits = bad_form.findall(B.listing(unit))
         assert not hits, (unit, len(hits))
     txt = B.listing("rmav_policy_abi")

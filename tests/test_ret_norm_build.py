@@ -30,7 +30,7 @@ def test_ret_norm_kernels():
 
 
 def test_gae_norm_clamp_is_one_instruction():
-    bodies = B.bodies("rmav_abi")
+    bodies = B.bodies("rmav_ppo_abi")
     seen = 0
     for name, body in bodies.items():
         if not name.startswith("_ZN4rmav10k_gae_normILb"):
@@ -40,5 +40,5 @@ def test_gae_norm_clamp_is_one_instruction():
         for bad in ("scratch_", "v_pk_mul_f32", "v_pk_fma_f32"):   # (the block reduction's shuffles are the only cross-lane traffic)
             assert bad not in body, (name, bad)
     assert seen == 2
-    txt = B.listing("rmav_abi")
+    txt = B.listing("rmav_ppo_abi")
     assert "_ZN4rmav5k_gaeE" in txt and "_ZN4rmav10k_gae_bootE" in txt

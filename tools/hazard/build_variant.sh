@@ -11,7 +11,9 @@ HERE=$(cd $(dirname $0) && pwd); PKG=$HERE/../../reinmav-gym_amd; OUT=$HERE/_bui
 LLVM=/opt/rocm/lib/llvm/bin
 BASE="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC -Wno-unused-command-line-argument"
 cd $PKG
-[ -f build/rmav_abi.o ] || make build/rmav_abi.o
+# every other translation unit as the product build compiles it (the objects are intermediate files: name them to get them)
+OTHERS=$(for f in csrc/*.hip; do echo build/$(basename $f .hip).o; done | grep -v rmav_policy_abi)
+make -s $OTHERS
 /opt/rocm/bin/hipcc $BASE $EXTRA -S --cuda-device-only -o $OUT/dev.s csrc/rmav_policy_abi.hip
 
 if [ $# -gt 0 ]; then python3 $HERE/patch_asm.py $OUT/dev.s "$@" > $OUT/patch.log; fi
@@ -20,6 +22,6 @@ $LLVM/lld -flavor gnu -m elf64_amdgpu --no-undefined -shared -o $OUT/dev.out $OU
 $LLVM/clang-offload-bundler -type=o -bundle-align=4096 -targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950 \
     -input=/dev/null -input=$OUT/dev.out -output=$OUT/dev.hipfb
 /opt/rocm/bin/hipcc $BASE $EXTRA --cuda-host-only -Xclang -fcuda-include-gpubinary -Xclang $OUT/dev.hipfb -c -o $OUT/host.o csrc/rmav_policy_abi.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/librmav.so build/rmav_abi.o $OUT/host.o -ldl -Wl,-rpath,/opt/rocm/lib
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $OUT/librmav.so $OTHERS $OUT/host.o -ldl -Wl,-rpath,/opt/rocm/lib
 rm -f $OUT/dev.o $OUT/dev.out $OUT/dev.hipfb $OUT/host.o
 echo "$NAME: $(ls -la $OUT/librmav.so | awk '{print $5}') bytes; $(cat $OUT/patch.log 2>/dev/null | tail -1)"

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Compare the instruction streams of the kernels of two `make asm` outputs: the listings of the three translation units,
-build/rmav_abi.gfx950.s, build/rmav_policy_abi.gfx950.s and build/rmav_range_abi.gfx950.s.
+"""Compare the instruction streams of the kernels of two `make asm` outputs: every listing build/<unit>.gfx950.s of each directory,
+by symbol over their union - a kernel that moved to another translation unit is neither missing nor added.  A symbol that two listings
+of one directory define is an error (the internal-linkage `_ZN4rmavL...` helpers excepted: every unit that includes their header has a
+copy, which is compared with the copy of the unit of the same name; a copy less is reported, not counted as missing).
 
     python tools/isa_compare.py OLD_DIR NEW_DIR
 
@@ -15,11 +17,11 @@ device function that reads LDS (the index of the calling kernel in the module's 
 added to the module; a function whose only differences are such immediates is listed as "kernel id only" and does not count as
 changed."""
 import argparse
+import glob
 import os
 import re
 import sys
 
-UNITS = ("rmav_abi.gfx950.s", "rmav_policy_abi.gfx950.s", "rmav_range_abi.gfx950.s")
 _LABEL = re.compile(r"\.L[A-Za-z_]*\d+(?:_\d+)*")
 _KERNEL_ID = re.compile(r"^s_mov_b32 s15, \d+$")
 
@@ -48,25 +50,52 @@ def kernels(path):
     return out
 
 
+def _local(symbol):
+    return symbol.startswith("_ZN4rmavL")   # internal linkage: every unit that includes its header has a copy of its own
+
+
+def directory(path):
+    """{symbol: (unit, body)} over every listing of a build directory; an internal-linkage helper is keyed by (unit, symbol)"""
+    out = {}
+    for f in sorted(glob.glob(os.path.join(path, "*.gfx950.s"))):
+        unit = os.path.basename(f)[:-len(".gfx950.s")]
+        for k, body in kernels(f).items():
+            if not _local(k) and k in out:
+                sys.exit(f"ERROR {path}: {k} is defined in {out[k][0]} and in {unit}")
+            out[(unit, k) if _local(k) else k] = (unit, body)
+    if not out:
+        sys.exit(f"ERROR {path}: no *.gfx950.s listing with a function in it")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
     ap.add_argument("new")
     args = ap.parse_args()
-    changed, missing, same, added, kid = [], [], 0, [], []
-    for unit in UNITS:
-        old, new = kernels(os.path.join(args.old, unit)), kernels(os.path.join(args.new, unit))
-        for k, body in sorted(old.items()):
-            if k not in new:
-                missing.append((unit, k))
-            elif new[k] == body:
-                same += 1
-            elif len(new[k]) == len(body) and all(a == b or (_KERNEL_ID.match(a) and _KERNEL_ID.match(b)) for a, b in zip(body, new[k])):
-                kid.append((unit, k))
+    changed, missing, same, kid, moved, dropped = [], [], 0, [], 0, 0
+    old, new = directory(args.old), directory(args.new)
+    name = lambda key: key[1] if isinstance(key, tuple) else key
+    new_names = {name(key) for key in new}
+    for key, (unit, body) in sorted(old.items(), key=str):
+        if key not in new:
+            # a unit's copy of an internal-linkage helper that another unit still defines is a copy less, not a kernel less
+            if isinstance(key, tuple) and name(key) in new_names:
+                dropped += 1
             else:
-                diff = sum(1 for a, b in zip(body, new[k]) if a != b) + abs(len(body) - len(new[k]))
-                changed.append((unit, k, len(body), len(new[k]), diff))
-        added += [(unit, k) for k in sorted(set(new) - set(old))]
+                missing.append((unit, name(key)))
+            continue
+        unit1, body1 = new[key]
+        moved += unit1 != unit
+        if body1 == body:
+            same += 1
+        elif len(body1) == len(body) and all(a == b or (_KERNEL_ID.match(a) and _KERNEL_ID.match(b)) for a, b in zip(body, body1)):
+            kid.append((unit1, name(key)))
+        else:
+            diff = sum(1 for a, b in zip(body, body1) if a != b) + abs(len(body) - len(body1))
+            changed.append((unit1, name(key), len(body), len(body1), diff))
+    old_names = {name(key) for key in old}
+    added = sorted((new[key][0], name(key)) for key in new if name(key) not in old_names)
     for unit, k, n0, n1, d in changed:
         print(f"CHANGED {unit} {k}: {n0} -> {n1} lines, {d} differ")
     for unit, k in missing:
@@ -74,7 +103,7 @@ def main():
     for unit, k in kid:
         print(f"KERNEL-ID-ONLY {unit} {k}")
     print(f"{same} pre-existing functions identical, {len(kid)} identical but for the LDS kernel id, {len(changed)} changed, "
-          f"{len(missing)} missing; {len(added)} added")
+          f"{len(missing)} missing; {len(added)} added; {moved} in another translation unit, {dropped} copies of internal-linkage helpers dropped")
     for unit, k in added:
         print(f"  added {unit} {k}")
     return 1 if changed or missing else 0
