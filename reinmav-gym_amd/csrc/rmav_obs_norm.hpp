@@ -2,6 +2,10 @@
 // on the device: batch moments of a stored observation array, their merge into the running state, and the elementwise
 // normalisation.  The fused rollouts read only the fp32 tables at the end of the buffer (NormArgs, rmav_kernels.hpp).
 //
+// Each rule is written once and rmav_ret_norm.hpp uses the same ones: chan() combines two moments (threads, wavefronts, blocks AND
+// the merge of a batch record into the running state), shifted_moment() turns a thread's sums into a moment, fold_partials() is the
+// second stage of both moments launches, rstd_entry() the scale both tables hold.
+//
 // Moments are (n, mean, M2 = sum (x - mean)^2) triples in fp64 from the first per-thread value on: a thread accumulates
 // sum (x - K) and sum (x - K)^2 with K = the first value it sees (x - K is exact in fp64 for fp32 data, and |x - K| is of the
 // order of the spread, so the conversion to (mean, M2) does not cancel), and everything above a thread - lanes of a wavefront,
@@ -68,6 +72,19 @@ __device__ __forceinline__ Moment block_chan(Moment m) {
     if (threadIdx.x == 0) m = chan(chan(sh[0], sh[1]), chan(sh[2], sh[3]));
     return m;
 }
+// a thread's moment from its count and its sums of (x - K), (x - K)^2; no sample: the empty moment
+__device__ __forceinline__ Moment shifted_moment(double cnt, double k0, double s1, double s2) {
+    if (!(cnt > 0.0)) return Moment{0.0, 0.0, 0.0};
+    return Moment{cnt, k0 + s1 / cnt, s2 - s1 * s1 / cnt};
+}
+// nblk partials -> one moment in thread 0 (one block of 256 threads)
+__device__ __forceinline__ Moment fold_partials(const Moment *__restrict__ partial, int32_t nblk) {
+    Moment m{0.0, 0.0, 0.0};
+    for (int32_t b = threadIdx.x; b < nblk; b += 256) m = chan(m, partial[b]);
+    return block_chan(m);
+}
+// THE table entry both normalisers scale by: 1 / sqrt(var + eps) of the running state, rounded to fp32 once
+__device__ __forceinline__ float rstd_entry(double count, double m2, double eps) { return (float)(1.0 / sqrt(m2 / count + eps)); }
 
 // Element (row r, feature c, env i) of an observation array sits at r * row + c * feat + i * elem floats:
 //   SoA [n_rows][nS][pitch]: row = nS * pitch, feat = pitch, elem = 1;   AoS [n_rows * N][nS]: row = N * nS, feat = 1, elem = nS
@@ -107,19 +124,15 @@ __global__ __launch_bounds__(256) void k_obs_moments(const float *__restrict__ o
             }
         }
     }
-    Moment m{0.0, 0.0, 0.0};
-    if (cnt > 0.0) m = Moment{cnt, k0 + s1 / cnt, s2 - s1 * s1 / cnt};
-    m = block_chan(m);
+    const Moment m = block_chan(shifted_moment(cnt, k0, s1, s2));
     if (threadIdx.x == 0) partial[(int64_t)c * gridDim.x + blockIdx.x] = m;
 }
 
 // Stage 2.  Block c folds feature c's partials into batch_out = (count, mean[16], m2[16]); blocks c >= nS write zeros.
 __global__ __launch_bounds__(256) void k_obs_moments_fold(const Moment *__restrict__ partial, int32_t nblk, int32_t ns, double *__restrict__ batch_out) {
     const int32_t c = blockIdx.x;
-    Moment m{0.0, 0.0, 0.0};
-    if (c < ns)
-        for (int32_t b = threadIdx.x; b < nblk; b += 256) m = chan(m, partial[(int64_t)c * nblk + b]);
-    m = block_chan(m);
+    const bool used = c < ns;
+    const Moment m = fold_partials(partial + (used ? (int64_t)c * nblk : 0), used ? nblk : 0);
     if (threadIdx.x == 0) {
         if (c == 0) batch_out[0] = m.n;
         batch_out[1 + c] = m.mean;
@@ -130,7 +143,7 @@ __global__ __launch_bounds__(256) void k_obs_moments_fold(const Moment *__restri
 // the fp32 tables from the running state (thread c < 16); features >= ns stay at mean 0, scale 1
 __device__ __forceinline__ void obs_norm_tables(ObsNormStats *st, int c, int ns, double count, double mean, double m2, double eps, float clip) {
     st->mean_f[c] = c < ns ? (float)mean : 0.0f;
-    st->rstd_f[c] = c < ns ? (float)(1.0 / sqrt(m2 / count + eps)) : 1.0f;
+    st->rstd_f[c] = c < ns ? rstd_entry(count, m2, eps) : 1.0f;
     if (c == 0) st->clip_f = clip;
 }
 
@@ -149,32 +162,32 @@ __global__ __launch_bounds__(64) void k_obs_norm_init(ObsNormStats *st, int32_t 
     obs_norm_tables(st, c, ns, count0, 0.0, count0, eps, clip);
 }
 
-// running state <- running state merged with n_batches records, in order (the update rule of RunningMeanStd in terms of M2 = var * count)
+// running state <- running state merged with n_batches records, in order: the update rule of RunningMeanStd in terms of
+// M2 = var * count is chan(); empty (or NaN-count) records are skipped, features >= ns keep var = 1.  chan() takes a running count
+// of exactly 0 as "no sample yet" and returns the record as it is; _init refuses count0 <= 0, so only a buffer written by the caller
+// can hold one.
 __global__ __launch_bounds__(64) void k_obs_norm_merge(ObsNormStats *st, const double *__restrict__ batch, int32_t n_batches, int32_t ns) {
     const int c = threadIdx.x;
     if (c >= kNormFeat) return;
-    double count = st->count, mean = st->mean[c], m2 = st->m2[c];
+    Moment run{st->count, st->mean[c], st->m2[c]};
     const double eps = st->eps;
     const float clip = st->clip;
     for (int32_t b = 0; b < n_batches; ++b) {
         const double *rec = batch + (int64_t)b * kMomentWords;
         const double bc = rec[0];
         if (!(bc > 0.0)) continue;
-        const double tot = count + bc;
         if (c < ns) {
-            const double d = rec[1 + c] - mean;
-            mean += d * bc / tot;
-            m2 = m2 + rec[1 + kNormFeat + c] + d * d * count * bc / tot;
+            run = chan(run, Moment{bc, rec[1 + c], rec[1 + kNormFeat + c]});
         } else {
-            m2 = tot;   // var = 1
+            run.n += bc;
+            run.m2 = run.n;   // var = 1
         }
-        count = tot;
     }
     __syncthreads();   // every thread has read the old count
-    if (c == 0) st->count = count;
-    st->mean[c] = mean;
-    st->m2[c] = m2;
-    obs_norm_tables(st, c, ns, count, mean, m2, eps, clip);
+    if (c == 0) st->count = run.n;
+    st->mean[c] = run.mean;
+    st->m2[c] = run.m2;
+    obs_norm_tables(st, c, ns, run.n, run.mean, run.m2, eps, clip);
 }
 
 // THE arithmetic of observation normalisation, fp32, uncontracted, in this order (include/rmav_ppo.h): subtract, multiply, clamp

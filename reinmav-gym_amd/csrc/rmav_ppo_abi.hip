@@ -202,13 +202,20 @@ int rmav_normalize(rmav_handle h, float *x, int64_t count, float mean, float rst
 }
 
 // ---- observation normalisation (VecNormalize): running statistics on the device, csrc/rmav_obs_norm.hpp ------------------
+// the settings both _init entry points take (observation and return statistics)
+static int check_norm_settings(float clip, double eps, double count0) {
+    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
+        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    return RMAV_OK;
+}
 namespace {
 int check_norm_handle(rmav_handle h, const char *what) {
     if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "%s runs the four quadrotor kinds, not RMAV_REINMAV", what);
     return RMAV_OK;
 }
-int check_stats(const void *stats) {
-    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_obs_norm_bytes() bytes)");
+// a statistics buffer of either normaliser; bytes_fn = the function that gives its size
+int check_stats(const void *stats, const char *bytes_fn) {
+    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of %s() bytes)", bytes_fn);
     if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
     return RMAV_OK;
 }
@@ -233,9 +240,8 @@ int64_t rmav_obs_norm_bytes(void) { return (int64_t)sizeof(ObsNormStats); }
 int rmav_obs_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
     CHECK_HANDLE(h);
     if (int rc = check_norm_handle(h, "rmav_obs_norm_init")) return rc;
-    if (int rc = check_stats(stats)) return rc;
-    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
-        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    if (int rc = check_stats(stats, "rmav_obs_norm_bytes")) return rc;
+    if (int rc = check_norm_settings(clip, eps, count0)) return rc;
     hipLaunchKernelGGL(k_obs_norm_init, dim3(1), dim3(64), 0, h->stream, (ObsNormStats *)stats, (int32_t)kStateDim[h->kind], clip, eps, count0);
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
@@ -270,7 +276,7 @@ int rmav_obs_moments(rmav_handle h, const float *obs, int layout, int32_t n_rows
 int rmav_obs_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
     CHECK_HANDLE(h);
     if (int rc = check_norm_handle(h, "rmav_obs_norm_merge")) return rc;
-    if (int rc = check_stats(stats)) return rc;
+    if (int rc = check_stats(stats, "rmav_obs_norm_bytes")) return rc;
     if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
     if (n_batches == 0) return RMAV_OK;
     if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 33 doubles on the device)");
@@ -282,7 +288,7 @@ int rmav_obs_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t
 int rmav_obs_normalize(rmav_handle h, const void *stats, const float *in, float *out, int layout, int32_t n_rows, int64_t pitch) {
     CHECK_HANDLE(h);
     if (int rc = check_norm_handle(h, "rmav_obs_normalize")) return rc;
-    if (int rc = check_stats(stats)) return rc;
+    if (int rc = check_stats(stats, "rmav_obs_norm_bytes")) return rc;
     if (n_rows < 0) return rmav_fail(RMAV_ERR_INVALID, "n_rows must be >= 0");
     if (n_rows == 0) return RMAV_OK;
     if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
@@ -301,7 +307,7 @@ int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weight
     CHECK_HANDLE(h);
     if (int rc = check_norm_handle(h, "rmav_rollout_policy_norm")) return rc;
     if (int rc = need_variants(precision, "rmav_rollout_policy_norm", "normalised")) return rc;
-    if (int rc = check_stats(stats)) return rc;
+    if (int rc = check_stats(stats, "rmav_obs_norm_bytes")) return rc;
     if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, false, nullptr)) return rc;
     if (h->time_limit > 0 && !boot_out)
         return rmav_fail(RMAV_ERR_INVALID, "boot_out is required on a handle with an episode time limit (as rmav_rollout_policy_boot)");
@@ -313,21 +319,12 @@ int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weight
 }
 
 // ---- return normalisation (the reward half of VecNormalize): one scalar RunningMeanStd on the device, csrc/rmav_ret_norm.hpp -----------
-namespace {
-int check_ret_stats(const void *stats) {
-    if (!stats) return rmav_fail(RMAV_ERR_INVALID, "stats is NULL (a device buffer of rmav_ret_norm_bytes() bytes)");
-    if ((reinterpret_cast<uintptr_t>(stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "stats must be 16-byte aligned");
-    return RMAV_OK;
-}
-}  // namespace
-
 int64_t rmav_ret_norm_bytes(void) { return (int64_t)sizeof(RetNormStats); }
 
 int rmav_ret_norm_init(rmav_handle h, void *stats, float clip, double eps, double count0) {
     CHECK_HANDLE(h);
-    if (int rc = check_ret_stats(stats)) return rc;
-    if (!(clip > 0.0f) || !(eps >= 0.0) || !(count0 > 0.0) || eps - eps != 0.0 || count0 - count0 != 0.0)
-        return rmav_fail(RMAV_ERR_INVALID, "clip must be > 0 (+inf = no clip), eps finite and >= 0, count0 finite and > 0");
+    if (int rc = check_stats(stats, "rmav_ret_norm_bytes")) return rc;
+    if (int rc = check_norm_settings(clip, eps, count0)) return rc;
     hipLaunchKernelGGL(k_ret_norm_init, dim3(1), dim3(64), 0, h->stream, (RetNormStats *)stats, clip, eps, count0);
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
@@ -353,7 +350,7 @@ int rmav_ret_moments(rmav_handle h, int32_t n_steps, const float *rew, const uin
 
 int rmav_ret_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t n_batches) {
     CHECK_HANDLE(h);
-    if (int rc = check_ret_stats(stats)) return rc;
+    if (int rc = check_stats(stats, "rmav_ret_norm_bytes")) return rc;
     if (n_batches < 0) return rmav_fail(RMAV_ERR_INVALID, "n_batches must be >= 0");
     if (n_batches == 0) return RMAV_OK;
     if (!batch) return rmav_fail(RMAV_ERR_INVALID, "batch is NULL (n_batches records of 3 doubles on the device)");
@@ -364,7 +361,7 @@ int rmav_ret_norm_merge(rmav_handle h, void *stats, const double *batch, int32_t
 
 int rmav_ret_normalize(rmav_handle h, const void *stats, const float *in, float *out, int64_t count, float reward_scale) {
     CHECK_HANDLE(h);
-    if (int rc = check_ret_stats(stats)) return rc;
+    if (int rc = check_stats(stats, "rmav_ret_norm_bytes")) return rc;
     if (count < 0) return rmav_fail(RMAV_ERR_INVALID, "count must be >= 0");
     if (count == 0) return RMAV_OK;
     if (!in || !out) return rmav_fail(RMAV_ERR_INVALID, "in and out are required (device pointers; out == in is allowed)");
@@ -380,7 +377,7 @@ int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_
     CHECK_HANDLE(h);
     if (boot && h->kind == RMAV_REINMAV)
         return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no time limit: there is no truncated step to bootstrap (pass boot = NULL)");
-    if (int rc = check_ret_stats(stats)) return rc;
+    if (int rc = check_stats(stats, "rmav_ret_norm_bytes")) return rc;
     return gae_impl(h, n_steps, rew, done, values, boot != nullptr, boot, (const RetNormStats *)stats, gamma, lam, reward_scale, adv_out, ret_out,
                     sums_out);
 }

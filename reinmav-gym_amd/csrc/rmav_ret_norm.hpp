@@ -3,8 +3,10 @@
 // R_t = gamma R_{t-1} + s r_t, their merge into ONE scalar RunningMeanStd, the elementwise scaling, and GAE with that scaling
 // applied to every reward as it is loaded (k_gae_norm: k_gae / k_gae_boot of rmav_gae.hpp with one multiply and one clamp in front).
 //
-// The moments reuse the machinery of rmav_obs_norm.hpp: per lane sum (R - K) and sum (R - K)^2 in fp64 with K = the lane's first
-// return, Chan's pairwise combination above that in a fixed order, no floating-point atomics - the same input gives the same bits.
+// The moments reuse the machinery of rmav_obs_norm.hpp (shifted_moment, chan, fold_partials, rstd_entry): per lane sum (R - K) and
+// sum (R - K)^2 in fp64 with K = the lane's first return, Chan's pairwise combination above that in a fixed order - the merge into
+// the running state included - no floating-point atomics: the same input gives the same bits.  k_gae_norm is a wrapper of
+// gae_body (rmav_gae.hpp) that hands it ret_norm_apply.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -83,20 +85,13 @@ __global__ __launch_bounds__(256) void k_ret_moments(const float *__restrict__ r
         }
         carry[i] = R;
     }
-    Moment m{0.0, 0.0, 0.0};
-    if (i < n) {
-        const double cnt = (double)T;
-        m = Moment{cnt, k0 + s1 / cnt, s2 - s1 * s1 / cnt};
-    }
-    m = block_chan(m);
+    const Moment m = block_chan(shifted_moment(i < n ? (double)T : 0.0, k0, s1, s2));
     if (threadIdx.x == 0) partial[blockIdx.x] = m;
 }
 
 // Stage 2.  One block folds the partials into batch_out = (count, mean, m2); nblk = 0 leaves the empty record.
 __global__ __launch_bounds__(256) void k_ret_moments_fold(const Moment *__restrict__ partial, int32_t nblk, double *__restrict__ batch_out) {
-    Moment m{0.0, 0.0, 0.0};
-    for (int32_t b = threadIdx.x; b < nblk; b += 256) m = chan(m, partial[b]);
-    m = block_chan(m);
+    const Moment m = fold_partials(partial, nblk);
     if (threadIdx.x == 0) {
         batch_out[0] = m.n;
         batch_out[1] = m.mean;
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(256) void k_ret_moments_fold(const Moment *__restri
 
 // the fp32 table from the running state
 __device__ __forceinline__ void ret_norm_table(RetNormStats *st, double count, double m2, double eps, float clip) {
-    st->rstd_f = (float)(1.0 / sqrt(m2 / count + eps));
+    st->rstd_f = rstd_entry(count, m2, eps);
     st->clip_f = clip;
 }
 
@@ -122,24 +117,21 @@ __global__ __launch_bounds__(64) void k_ret_norm_init(RetNormStats *st, float cl
     ret_norm_table(st, count0, count0, eps, clip);
 }
 
-// running state <- running state merged with n_batches records, in order (k_obs_norm_merge for one scalar)
+// running state <- running state merged with n_batches records, in order (k_obs_norm_merge for one scalar: chan() per record).
+// chan() takes a running count of exactly 0 as "no sample yet" and returns the record as it is; _init refuses count0 <= 0, so only a
+// buffer written by the caller can hold one.
 __global__ __launch_bounds__(64) void k_ret_norm_merge(RetNormStats *st, const double *__restrict__ batch, int32_t n_batches) {
     if (threadIdx.x != 0) return;
-    double count = st->count, mean = st->mean, m2 = st->m2;
+    Moment run{st->count, st->mean, st->m2};
     for (int32_t b = 0; b < n_batches; ++b) {
         const double *rec = batch + (int64_t)b * kRetMomentWords;
-        const double bc = rec[0];
-        if (!(bc > 0.0)) continue;
-        const double tot = count + bc;
-        const double d = rec[1] - mean;
-        mean += d * bc / tot;
-        m2 = m2 + rec[2] + d * d * count * bc / tot;
-        count = tot;
+        if (!(rec[0] > 0.0)) continue;
+        run = chan(run, Moment{rec[0], rec[1], rec[2]});
     }
-    st->count = count;
-    st->mean = mean;
-    st->m2 = m2;
-    ret_norm_table(st, count, m2, st->eps, st->clip);
+    st->count = run.n;
+    st->mean = run.mean;
+    st->m2 = run.m2;
+    ret_norm_table(st, run.n, run.m2, st->eps, st->clip);
 }
 
 // out = clamp((rew_scale * in) * rstd_f, -clip, clip), one element per thread; out == in allowed
@@ -161,67 +153,9 @@ __global__ __launch_bounds__(256) void k_gae_norm(const float *__restrict__ rew,
                                                   const RetNormStats *__restrict__ st, float *__restrict__ adv, float *__restrict__ ret,
                                                   int64_t n, int32_t T, float gamma, float lam, float rew_scale,
                                                   double *__restrict__ partial) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const float rstd = st->rstd_f, clip = st->clip_f;
-    float s1 = 0.0f, s2 = 0.0f;
-    if (i < n) {
-        float v_next = val[(int64_t)T * n + i];
-        float last = 0.0f;
-        const float gl = gamma * lam;
-        int32_t t = T - 1;
-        auto step = [&](int64_t o, float r, float v, float nt, float b) {
-            const float z = ret_norm_apply(r, rew_scale, rstd, clip);
-            const float delta = BOOT ? fmaf(gamma * nt, v_next, fmaf(gamma, b, z - v)) : fmaf(gamma * nt, v_next, z - v);
-            last = fmaf(gl * nt, last, delta);
-            adv[o] = last;
-            ret[o] = last + v;
-            s1 += last;
-            s2 = fmaf(last, last, s2);
-            v_next = v;
-        };
-        // head: bring t + 1 to a multiple of the unroll factor
-        for (; t >= 0 && ((t + 1) % kGaeUnroll) != 0; --t) {
-            const int64_t o = (int64_t)t * n + i;
-            step(o, rew[o], val[o], done[o] ? 0.0f : 1.0f, BOOT ? boot[o] : 0.0f);
-        }
-        for (; t >= 0; t -= kGaeUnroll) {
-            float r[kGaeUnroll], v[kGaeUnroll], nt[kGaeUnroll], b[kGaeUnroll];
-#pragma unroll
-            for (int j = 0; j < kGaeUnroll; ++j) {
-                const int64_t o = (int64_t)(t - j) * n + i;
-                r[j] = rew[o];
-                v[j] = val[o];
-                b[j] = BOOT ? boot[o] : 0.0f;
-                nt[j] = done[o] ? 0.0f : 1.0f;
-            }
-#pragma unroll
-            for (int j = 0; j < kGaeUnroll; ++j) step((int64_t)(t - j) * n + i, r[j], v[j], nt[j], b[j]);
-        }
-    }
-    if (partial) {   // block partial of (sum A, sum A^2), as k_gae
-        __shared__ double sh[2][4];
-        double d1 = (double)s1, d2 = (double)s2;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            d1 += __shfl_down(d1, off, 64);
-            d2 += __shfl_down(d2, off, 64);
-        }
-        const int w = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) {
-            sh[0][w] = d1;
-            sh[1][w] = d2;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double a1 = 0.0, a2 = 0.0;
-            for (int k = 0; k < (int)(blockDim.x >> 6); ++k) {
-                a1 += sh[0][k];
-                a2 += sh[1][k];
-            }
-            partial[2 * blockIdx.x] = a1;
-            partial[2 * blockIdx.x + 1] = a2;
-        }
-    }
+    gae_body<BOOT>(rew, done, val, boot, adv, ret, n, T, gamma, lam,
+                   [=](float r, float v) { return ret_norm_apply(r, rew_scale, rstd, clip) - v; }, partial);
 }
 
 }  // namespace rmav

@@ -304,17 +304,13 @@ class BatchedQuadrotor:
         adv, ret = out if out is not None else (torch.empty_like(rew), torch.empty_like(rew))
         if boot is not None:
             assert tuple(boot.shape) == (T, self.num_envs) and boot.dtype == torch.float32
+        fn, extra = self._lib.rmav_gae, ()
         if ret_norm is not None:
-            A.check(self._lib.rmav_gae_norm(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), self._ptr(boot),
-                                            C.c_void_p(ret_norm.data_ptr()), float(gamma), float(lam), float(reward_scale), self._ptr(adv),
-                                            self._ptr(ret), self._ptr(sums)))
-            return adv, ret
-        if boot is not None:
-            A.check(self._lib.rmav_gae_boot(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), self._ptr(boot), float(gamma),
-                                            float(lam), float(reward_scale), self._ptr(adv), self._ptr(ret), self._ptr(sums)))
-            return adv, ret
-        A.check(self._lib.rmav_gae(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), float(gamma), float(lam),
-                                   float(reward_scale), self._ptr(adv), self._ptr(ret), self._ptr(sums)))
+            fn, extra = self._lib.rmav_gae_norm, (self._ptr(boot), C.c_void_p(ret_norm.data_ptr()))
+        elif boot is not None:
+            fn, extra = self._lib.rmav_gae_boot, (self._ptr(boot),)
+        A.check(fn(self._h, T, self._ptr(rew), self._ptr(done), self._ptr(values), *extra, float(gamma), float(lam), float(reward_scale),
+                   self._ptr(adv), self._ptr(ret), self._ptr(sums)))
         return adv, ret
 
     def normalize_(self, x, mean: float, rstd: float):

@@ -23,54 +23,28 @@ import ctypes as C
 
 import numpy as np
 import torch
-import torch.distributed as dist
+
+from ._running import RunningStats
 
 N_FEAT = 16           # features of the buffer (the widest kind has 16 state components)
 N_BYTES = 432         # rmav_obs_norm_bytes()
 REC = 1 + 2 * N_FEAT  # a batch record: count, mean[16], m2[16]
-_O_COUNT, _O_MEAN, _O_M2, _O_EPS, _O_CLIP, _O_MEAN_F, _O_RSTD_F, _O_CLIP_F = 0, 8, 136, 264, 272, 288, 352, 416
 
 
-class RunningObsNorm:
+class RunningObsNorm(RunningStats):
+    N_BYTES, N_FEAT = N_BYTES, N_FEAT
+    _OFF = {"count": 0, "mean": 8, "m2": 136, "eps": 264, "clip": 272, "mean_f": 288, "rstd_f": 352, "clip_f": 416}
+    _WHAT = "observations"
+    _BAD_STATE = "state_dict of another observation size / buffer layout"
+
     def __init__(self, n_obs: int, device="cpu", clip: float = 10.0, eps: float = 1e-8, count0: float = 1e-4):
         """``clip``: baselines' ``clipob`` (``float('inf')`` = none); ``eps``: the epsilon under the square root; ``count0``: the
         count the statistics start from (mean 0, var 1).  ``freeze = True`` turns ``update`` into a no-op (evaluation)."""
         if not 1 <= int(n_obs) <= N_FEAT:
             raise ValueError(f"n_obs must be in [1, {N_FEAT}]")
-        if not clip > 0 or not eps >= 0 or not count0 > 0:
-            raise ValueError("clip must be > 0 (inf = no clip), eps >= 0, count0 > 0")
-        self.n_obs, self.device, self.freeze = int(n_obs), torch.device(device), False
-        host = np.zeros(N_BYTES, np.uint8)
-        host[_O_COUNT:_O_MEAN].view(np.float64)[0] = count0
-        host[_O_M2:_O_EPS].view(np.float64)[:] = count0                      # var = 1
-        host[_O_EPS:_O_CLIP].view(np.float64)[0] = eps
-        host[_O_CLIP:_O_CLIP + 4].view(np.float32)[0] = clip
-        self._alloc(host)
-        self._write_tables_host(host)
-        self.buf.copy_(torch.from_numpy(host))
-
-    def _alloc(self, host):
-        self.buf = torch.zeros(N_BYTES, dtype=torch.uint8, device=self.device)
-        assert self.buf.data_ptr() % 16 == 0
-        b = self.buf
-        self._count, self._mean, self._m2 = (b[_O_COUNT:_O_MEAN].view(torch.float64), b[_O_MEAN:_O_M2].view(torch.float64),
-                                             b[_O_M2:_O_EPS].view(torch.float64))
-        self._mean_f, self._rstd_f = b[_O_MEAN_F:_O_RSTD_F].view(torch.float32), b[_O_RSTD_F:_O_CLIP_F].view(torch.float32)
-        self._clip_f = b[_O_CLIP_F:_O_CLIP_F + 4].view(torch.float32)
-        self._eps = float(host[_O_EPS:_O_CLIP].view(np.float64)[0])
-        self._clip = float(host[_O_CLIP:_O_CLIP + 4].view(np.float32)[0])
-        self._batch = None   # device records of update(): [world, 33] float64
-
-    def _write_tables_host(self, host):
-        """tables from the fp64 state, as the merge kernel writes them (features >= n_obs: mean 0, scale 1)"""
-        n = self.n_obs
-        count = host[_O_COUNT:_O_MEAN].view(np.float64)[0]
-        mean, m2 = host[_O_MEAN:_O_M2].view(np.float64), host[_O_M2:_O_EPS].view(np.float64)
-        mf, rf = host[_O_MEAN_F:_O_RSTD_F].view(np.float32), host[_O_RSTD_F:_O_CLIP_F].view(np.float32)
-        mf[:], rf[:] = 0.0, 1.0
-        mf[:n] = mean[:n].astype(np.float32)
-        rf[:n] = (1.0 / np.sqrt(m2[:n] / count + self._eps)).astype(np.float32)
-        host[_O_CLIP_F:_O_CLIP_F + 4].view(np.float32)[0] = self._clip
+        self.n_obs = int(n_obs)
+        super().__init__(n_obs, device, clip, eps, count0)
+        self._mean_f = self._view("mean_f", torch.float32)
 
     # ---- what the consumers read: views of the buffer (no copy, no synchronisation, valid under graph replay) -------------------------
     @property
@@ -85,22 +59,7 @@ class RunningObsNorm:
     def clip_f(self) -> torch.Tensor:
         return self._clip_f
 
-    @property
-    def clip(self) -> float:
-        return self._clip
-
-    @property
-    def eps(self) -> float:
-        return self._eps
-
-    def data_ptr(self) -> int:
-        return self.buf.data_ptr()
-
     # ---- the running state (these synchronise) -----------------------------------------------------------------------------------------
-    @property
-    def count(self) -> float:
-        return float(self._count.cpu()[0])
-
     @property
     def mean(self) -> np.ndarray:
         return self._mean[:self.n_obs].cpu().numpy().copy()
@@ -111,15 +70,12 @@ class RunningObsNorm:
 
     def state_dict(self) -> dict:
         """the whole buffer (state, settings and tables: a round trip is exact) - keep it in a checkpoint beside the weights"""
-        return {"n_obs": self.n_obs, "buffer": self.buf.cpu().clone()}
+        return {"n_obs": self.n_obs, **super().state_dict()}
 
     def load_state_dict(self, sd: dict):
-        if int(sd["n_obs"]) != self.n_obs or tuple(sd["buffer"].shape) != (N_BYTES,) or sd["buffer"].dtype != torch.uint8:
-            raise ValueError("state_dict of another observation size / buffer layout")
-        host = sd["buffer"].cpu().numpy()
-        self._eps = float(host[_O_EPS:_O_CLIP].view(np.float64)[0])
-        self._clip = float(host[_O_CLIP:_O_CLIP + 4].view(np.float32)[0])
-        self.buf.copy_(sd["buffer"])   # in place: the pointer the kernels and captured graphs hold stays valid
+        if int(sd["n_obs"]) != self.n_obs:
+            raise ValueError(self._BAD_STATE)
+        super().load_state_dict(sd)
 
     # ---- normalise ------------------------------------------------------------------------------------------------------------------------
     def normalize(self, obs: torch.Tensor, out=None, layout: str = "soa", env=None):
@@ -167,35 +123,20 @@ class RunningObsNorm:
         statistics with RunningMeanStd's rule.  CUDA tensors need ``env`` (the ``BatchedQuadrotor`` whose batch this is): moments and
         merge are launches on its stream.  ``group`` (or the default process group, when one is initialised) with more than one rank:
         every rank's 33-double record is all-gathered and merged in rank order, so all ranks end with the same bits."""
-        if self.freeze:
-            return self
-        world = 1
-        if dist.is_available() and dist.is_initialized():
-            world = dist.get_world_size(group)
-        if obs.is_cuda:
-            from . import _abi as A
+        return self._update(env, group, obs, layout)
 
-            if env is None:
-                raise ValueError("update() of CUDA observations needs env= (the BatchedQuadrotor they belong to)")
-            n_rows, lay, pitch = self._rows(obs, layout, env)
-            if self._batch is None or self._batch.shape[0] != world:
-                self._batch = torch.zeros((world, REC), dtype=torch.float64, device=self.buf.device)
-            rank = dist.get_rank(group) if world > 1 else 0
-            A.check(A.lib().rmav_obs_moments(env._h, C.c_void_p(obs.data_ptr()), lay, n_rows, pitch, C.c_void_p(self._batch[rank].data_ptr())))
-            if world > 1:
-                dist.all_gather_into_tensor(self._batch.view(-1), self._batch[rank].clone(), group=group)
-            A.check(A.lib().rmav_obs_norm_merge(env._h, C.c_void_p(self.data_ptr()), C.c_void_p(self._batch.data_ptr()), world))
-            return self
-        rec = self._moments_cpu(obs, layout)
-        recs = [rec]
-        if world > 1:
-            recs = [torch.zeros_like(rec) for _ in range(world)]
-            dist.all_gather(recs, rec, group=group)
-        for r in recs:
-            self._merge_cpu(r)
-        return self
+    def _moments_gpu(self, env, rec, obs, layout):
+        from . import _abi as A
 
-    def _moments_cpu(self, obs, layout):
+        n_rows, lay, pitch = self._rows(obs, layout, env)
+        A.check(A.lib().rmav_obs_moments(env._h, C.c_void_p(obs.data_ptr()), lay, n_rows, pitch, rec))
+
+    def _merge_gpu(self, env, recs, n):
+        from . import _abi as A
+
+        A.check(A.lib().rmav_obs_norm_merge(env._h, C.c_void_p(self.data_ptr()), recs, n))
+
+    def _moments_cpu(self, env, obs, layout):
         n = self.n_obs
         x = obs.detach().to(torch.float64)
         x = (x.movedim(-2, -1) if layout == "soa" else x).reshape(-1, n)
@@ -208,15 +149,5 @@ class RunningObsNorm:
         return rec
 
     def _merge_cpu(self, rec):
-        n, bc = self.n_obs, float(rec[0])
-        if not bc > 0:
-            return
-        count = float(self._count[0])
-        tot = count + bc
-        d = rec[1:1 + n] - self._mean[:n]
-        self._mean[:n] += d * bc / tot
-        self._m2[:n] = self._m2[:n] + rec[1 + N_FEAT:1 + N_FEAT + n] + d * d * count * bc / tot
-        self._m2[n:] = tot
-        self._count[0] = tot
-        self._mean_f[:n] = self._mean[:n].to(torch.float32)
-        self._rstd_f[:n] = (1.0 / torch.sqrt(self._m2[:n] / tot + self._eps)).to(torch.float32)
+        if super()._merge_cpu(rec):
+            self._mean_f[:self.n_obs] = self._mean[:self.n_obs].to(torch.float32)

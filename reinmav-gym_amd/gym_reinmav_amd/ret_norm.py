@@ -29,84 +29,52 @@ import weakref
 
 import numpy as np
 import torch
-import torch.distributed as dist
+
+from ._running import RunningStats
 
 N_BYTES = 64   # rmav_ret_norm_bytes()
 REC = 3        # a batch record: count, mean, m2
-_O_COUNT, _O_MEAN, _O_M2, _O_EPS, _O_CLIP, _O_RSTD_F, _O_CLIP_F = 0, 8, 16, 24, 32, 48, 52
 
 
-class RunningReturnNorm:
+class RunningReturnNorm(RunningStats):
+    N_BYTES, N_FEAT = N_BYTES, 1
+    _OFF = {"count": 0, "mean": 8, "m2": 16, "eps": 24, "clip": 32, "rstd_f": 48, "clip_f": 52}
+    _WHAT = "rewards"
+    _BAD_STATE = "state_dict of another buffer layout"
+
     def __init__(self, device="cpu", gamma: float = 0.99, clip: float = 10.0, eps: float = 1e-8, count0: float = 1e-4):
         """``gamma``: the discount of the return carry (baselines: 0.99); ``clip``: baselines' ``cliprew`` (``float('inf')`` = none);
         ``eps``: the epsilon under the square root; ``count0``: the count the statistics start from (mean 0, var 1).
         ``freeze = True`` turns ``update`` into a no-op (evaluation)."""
-        if not clip > 0 or not eps >= 0 or not count0 > 0:
-            raise ValueError("clip must be > 0 (inf = no clip), eps >= 0, count0 > 0")
-        self.gamma, self.device, self.freeze = float(gamma), torch.device(device), False
-        host = np.zeros(N_BYTES, np.uint8)
-        f64 = host[:_O_CLIP].view(np.float64)
-        f64[0], f64[1], f64[2], f64[3] = count0, 0.0, count0, eps   # var = 1
-        host[_O_CLIP:_O_CLIP + 4].view(np.float32)[0] = clip
-        host[_O_RSTD_F:_O_RSTD_F + 4].view(np.float32)[0] = np.float32(1.0 / np.sqrt(1.0 + eps))
-        host[_O_CLIP_F:_O_CLIP_F + 4].view(np.float32)[0] = clip
-        self.buf = torch.zeros(N_BYTES, dtype=torch.uint8, device=self.device)
-        assert self.buf.data_ptr() % 16 == 0
-        b = self.buf
-        self._state = b[_O_COUNT:_O_EPS].view(torch.float64)   # count, mean, m2
-        self._rstd_f = b[_O_RSTD_F:_O_RSTD_F + 4].view(torch.float32)[0]
-        self._clip_f = b[_O_CLIP_F:_O_CLIP_F + 4].view(torch.float32)[0]
-        self._eps, self._clip = float(eps), float(np.float32(clip))
-        self._batch = None    # device records of update(): [world, 3] float64
+        super().__init__(1, device, clip, eps, count0)
+        self.gamma = float(gamma)
         self._carry = {}      # id(env) -> (weak reference or None, R [N])
-        self.buf.copy_(torch.from_numpy(host))
 
     # ---- what the consumers read: views of the buffer (no copy, no synchronisation, valid under graph replay) -------------------------
     @property
     def rstd_f(self) -> torch.Tensor:
-        return self._rstd_f
+        return self._rstd_f[0]
 
     @property
     def clip_f(self) -> torch.Tensor:
-        return self._clip_f
-
-    @property
-    def clip(self) -> float:
-        return self._clip
-
-    @property
-    def eps(self) -> float:
-        return self._eps
-
-    def data_ptr(self) -> int:
-        return self.buf.data_ptr()
+        return self._clip_f[0]
 
     # ---- the running state (these synchronise) -----------------------------------------------------------------------------------------
     @property
-    def count(self) -> float:
-        return float(self._state.cpu()[0])
-
-    @property
     def mean(self) -> float:
-        return float(self._state.cpu()[1])
+        return float(self._mean.cpu()[0])
 
     @property
     def var(self) -> float:
-        s = self._state.cpu()
-        return float(s[2] / s[0])
+        return float(self._m2.cpu()[0] / self._count.cpu()[0])
 
     def state_dict(self) -> dict:
         """the whole buffer (state, settings and table: a round trip is exact) and gamma; the per-env carry is not part of it"""
-        return {"gamma": self.gamma, "buffer": self.buf.cpu().clone()}
+        return {"gamma": self.gamma, **super().state_dict()}
 
     def load_state_dict(self, sd: dict):
-        if tuple(sd["buffer"].shape) != (N_BYTES,) or sd["buffer"].dtype != torch.uint8:
-            raise ValueError("state_dict of another buffer layout")
-        host = sd["buffer"].cpu().numpy()
+        super().load_state_dict(sd)
         self.gamma = float(sd["gamma"])
-        self._eps = float(host[_O_EPS:_O_CLIP].view(np.float64)[0])
-        self._clip = float(host[_O_CLIP:_O_CLIP + 4].view(np.float32)[0])
-        self.buf.copy_(sd["buffer"])   # in place: the pointer the kernels and captured graphs hold stays valid
 
     # ---- the per-env discounted return ----------------------------------------------------------------------------------------------------
     def carry(self, env, like: torch.Tensor = None) -> torch.Tensor:
@@ -149,9 +117,9 @@ class RunningReturnNorm:
             A.check(A.lib().rmav_ret_normalize(env._h, C.c_void_p(self.data_ptr()), C.c_void_p(rew.data_ptr()), C.c_void_p(dst.data_ptr()),
                                                rew.numel(), float(reward_scale)))
             return dst
-        z = (rew * float(reward_scale)) * self._rstd_f
-        neg = -self._clip_f
-        return torch.clamp(z, neg, self._clip_f, out=out) if out is not None else torch.clamp(z, neg, self._clip_f)
+        z = (rew * float(reward_scale)) * self.rstd_f
+        c = self.clip_f
+        return torch.clamp(z, -c, c, out=out) if out is not None else torch.clamp(z, -c, c)
 
     # ---- update ---------------------------------------------------------------------------------------------------------------------------
     def update(self, rew: torch.Tensor, done: torch.Tensor, env=None, reward_scale: float = 1.0, group=None):
@@ -160,43 +128,28 @@ class RunningReturnNorm:
         ``BatchedQuadrotor`` whose batch this is): scan and merge are launches on its stream.  ``group`` (or the default process group,
         when one is initialised) with more than one rank: every rank's 3-double record is all-gathered and merged in rank order, so
         all ranks end with the same bits."""
-        if self.freeze:
-            return self
-        world = 1
-        if dist.is_available() and dist.is_initialized():
-            world = dist.get_world_size(group)
         if rew.dim() == 1:
             rew, done = rew[None], done[None]
+        return self._update(env, group, rew, done, float(reward_scale))
+
+    def _moments_gpu(self, env, rec, rew, done, scale):
+        from . import _abi as A
+
+        T, N = rew.shape
+        assert tuple(done.shape) == (T, N) and N == env.num_envs
+        assert rew.dtype == torch.float32 and rew.is_contiguous() and done.is_contiguous() and done.element_size() == 1
+        A.check(A.lib().rmav_ret_moments(env._h, T, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()), scale, self.gamma,
+                                         C.c_void_p(self.carry(env).data_ptr()), rec))
+
+    def _merge_gpu(self, env, recs, n):
+        from . import _abi as A
+
+        A.check(A.lib().rmav_ret_norm_merge(env._h, C.c_void_p(self.data_ptr()), recs, n))
+
+    def _moments_cpu(self, env, rew, done, scale):
         T, N = rew.shape
         assert tuple(done.shape) == (T, N)
-        if rew.is_cuda:
-            from . import _abi as A
-
-            if env is None:
-                raise ValueError("update() of CUDA rewards needs env= (the BatchedQuadrotor they belong to)")
-            assert rew.dtype == torch.float32 and rew.is_contiguous() and done.is_contiguous() and done.element_size() == 1
-            assert N == env.num_envs
-            R = self.carry(env)
-            if self._batch is None or self._batch.shape[0] != world:
-                self._batch = torch.zeros((world, REC), dtype=torch.float64, device=self.buf.device)
-            rank = dist.get_rank(group) if world > 1 else 0
-            A.check(A.lib().rmav_ret_moments(env._h, T, C.c_void_p(rew.data_ptr()), C.c_void_p(done.data_ptr()), float(reward_scale),
-                                             self.gamma, C.c_void_p(R.data_ptr()), C.c_void_p(self._batch[rank].data_ptr())))
-            if world > 1:
-                dist.all_gather_into_tensor(self._batch.view(-1), self._batch[rank].clone(), group=group)
-            A.check(A.lib().rmav_ret_norm_merge(env._h, C.c_void_p(self.data_ptr()), C.c_void_p(self._batch.data_ptr()), world))
-            return self
-        rec = self._moments_cpu(rew, done, self.carry(env, like=rew), float(reward_scale))
-        recs = [rec]
-        if world > 1:
-            recs = [torch.zeros_like(rec) for _ in range(world)]
-            dist.all_gather(recs, rec, group=group)
-        for r in recs:
-            self._merge_cpu(r)
-        return self
-
-    def _moments_cpu(self, rew, done, R, scale):
-        T = rew.shape[0]
+        R = self.carry(env, like=rew)
         x, d = rew.detach().to(torch.float64) * float(np.float32(scale)), done != 0   # the kernels take the scale as a float
         rets = torch.empty_like(x)
         for t in range(T):
@@ -210,16 +163,3 @@ class RunningReturnNorm:
             rec[1] = rets.mean()
             rec[2] = rets.var(unbiased=False) * B
         return rec
-
-    def _merge_cpu(self, rec):
-        bc = float(rec[0])
-        if not bc > 0:
-            return
-        s = self._state
-        count = float(s[0])
-        tot = count + bc
-        d = float(rec[1]) - float(s[1])
-        s[1] += d * bc / tot
-        s[2] = float(s[2]) + float(rec[2]) + d * d * count * bc / tot
-        s[0] = tot
-        self._rstd_f.fill_(float(np.float32(1.0 / np.sqrt(float(s[2]) / tot + self._eps))))

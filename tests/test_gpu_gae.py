@@ -3,6 +3,8 @@ recursion and the plain torch fp32 loop.  Floating point: tolerance 1e-5 * max(1
 import numpy as np
 import pytest
 
+from test_bootstrap_host import ref_f64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -14,18 +16,6 @@ def G(built):
     import gym_reinmav_amd as g
 
     return g
-
-
-def _ref_f64(rew, val, done, gamma, lam, scale):
-    T, N = rew.shape
-    adv = np.zeros((T, N))
-    last = np.zeros(N)
-    for t in reversed(range(T)):
-        nt = 1.0 - done[t].astype(np.float64)
-        delta = scale * rew[t].astype(np.float64) + gamma * val[t + 1].astype(np.float64) * nt - val[t]
-        last = delta + gamma * lam * nt * last
-        adv[t] = last
-    return adv, adv + val[:T]
 
 
 @pytest.mark.parametrize("N,T", [(1, 1), (63, 7), (64, 8), (1000, 17), (20037, 33), (65536, 32), (4096, 257)])
@@ -42,7 +32,7 @@ def test_gae_matches_float64_recursion_and_torch(G, N, T):
     r, v, d = torch.from_numpy(rew).cuda(), torch.from_numpy(val).cuda(), torch.from_numpy(done).cuda()
     sums = torch.zeros(2, dtype=torch.float64, device="cuda")
     adv, ret = env.gae(r, d, v, gamma, lam, reward_scale=scale, sums=sums)
-    exp_a, exp_r = _ref_f64(rew, val, done, gamma, lam, scale)
+    exp_a, exp_r = ref_f64(rew, val, done, np.zeros_like(rew), gamma, lam, scale)
     tol = 1e-5 * max(1.0, np.abs(exp_a).max())
     assert np.abs(adv.cpu().numpy() - exp_a).max() < tol
     assert np.abs(ret.cpu().numpy() - exp_r).max() < tol
