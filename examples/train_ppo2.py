@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import torch
 
 import gym_reinmav_amd as g
+from gym_reinmav_amd.evaluate import evaluate_policy
 from gym_reinmav_amd.obs_norm import RunningObsNorm
 from gym_reinmav_amd.ppo import PPO, FusedPolicyCollector, MlpPolicy
 from gym_reinmav_amd.ret_norm import RunningReturnNorm
@@ -41,6 +42,15 @@ def main():
     ap.add_argument("--randomize", action="append", default=[], metavar="NAME=LO:HI",
                     help="per-episode domain randomisation inside the kernels, e.g. mass=0.8:1.2 (mass | load_mass | tether_length; "
                          "repeatable); not with --actor bf16")
+    ap.add_argument("--clip-actions", dest="clip_actions", action="store_true",
+                    help="the dynamics take clip(action, Box.low, Box.high), inside the kernel; the learner keeps the unclipped action and "
+                         "its log-probability (stable-baselines' PPO2 runner); not with --actor bf16")
+    ap.add_argument("--eval-every", dest="eval_every", type=int, default=0, metavar="K",
+                    help="every K iterations: the deterministic (mean-action, clipped) return of the policy on a separate eval env "
+                         "with the same seed base, time limit and ranges (evaluate_policy); not with --actor bf16")
+    ap.add_argument("--eval-envs", dest="eval_envs", type=int, default=1024, metavar="M")
+    ap.add_argument("--eval-steps", dest="eval_steps", type=int, default=0,
+                    help="steps of an evaluation; default --max_episode_steps (every env then finishes one episode), 256 without one")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -74,8 +84,13 @@ def main():
     elif kind in ("quad3d", "quad3d_sl"):
         with torch.no_grad():
             policy.pi[2].bias[0] = 9.8                      # start around hover thrust
-    collector = FusedPolicyCollector(env, policy, args.nsteps, bf16_mfma=(args.actor == "bf16"), f16_mfma=(args.actor == "f16"),
-                                     bootstrap_truncated=args.bootstrap_truncated)
+    actor_kw = dict(bf16_mfma=(args.actor == "bf16"), f16_mfma=(args.actor == "f16"))
+    collector = FusedPolicyCollector(env, policy, args.nsteps, bootstrap_truncated=args.bootstrap_truncated, clip_actions=args.clip_actions,
+                                     **actor_kw)
+    eval_env = None
+    if args.eval_every > 0:   # its own handle: the training envs' states, episode clocks and statistics are not disturbed
+        eval_env = g.BatchedQuadrotor(kind, args.eval_envs, seed=args.seed, env_id_base=args.num_env,
+                                      max_episode_steps=args.max_episode_steps or None, randomize=randomize or None)
     learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()
@@ -89,6 +104,12 @@ def main():
             print(f"iter {it:4d}  timesteps {(it + 1) * args.num_env * args.nsteps:.3g}  eprewmean {tot['return_sum'] / max(1, tot['episodes']):8.2f}  "
                   f"eplenmean {tot['length_sum'] / max(1, tot['episodes']):7.1f}  explained_variance {stats['explained_variance']:.3f}  "
                   f"{(it + 1) * args.num_env * args.nsteps / (time.perf_counter() - t0):.3g} steps/s", flush=True)
+        if eval_env is not None and ((it + 1) % args.eval_every == 0 or it == iters - 1):
+            ev = evaluate_policy(policy, eval_env, n_steps=args.eval_steps or args.max_episode_steps or 256, **actor_kw)
+            print(f"iter {it:4d}  eval (deterministic, clipped): mean_return {ev['mean_return']:8.2f} +- {ev['std_return']:.2f}  "
+                  f"mean_length {ev['mean_length']:7.1f}  episodes {ev['episodes']}  unfinished {ev['unfinished']}", flush=True)
+    if eval_env is not None:
+        eval_env.close()
     env.close()
     if args.save_path:                                      # run.py:186 model.save(save_path)
         torch.save(policy.state_dict(), args.save_path)

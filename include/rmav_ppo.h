@@ -166,7 +166,30 @@ int rmav_rollout_policy_norm(rmav_handle h, int32_t n_steps, const float *weight
                              float *rew_out, uint8_t *done_out, float *logp_out, float *value_out, float *boot_out, uint8_t *trunc_out,
                              int precision);
 
-/* ---- return normalisation: the reward half of baselines' VecNormalize(ret=True) in front of GAE -------------------------------------
+/* ---- the action rule of rmav_rollout_policy / _boot / _norm: clipping to the action space, deterministic evaluation -----------------
+ * What the in-kernel actors do between the policy's mean head and the dynamics.  stable-baselines' PPO2 runner steps the env with
+ * clip(action, Box.low, Box.high) but stores the unclipped action and ITS log-probability for the learner; predict(deterministic=True)
+ * takes the mean.  Handle state, host only (no launch, no synchronisation), default (0, -inf, +inf):
+ *   deterministic  0 | 1                 noise = deterministic ? 0.0f : 1.0f
+ *   clip_lo <= clip_hi, neither NaN       -inf / +inf = no bound on that side; anything else is RMAV_ERR_INVALID
+ * THE arithmetic, in fp32, uncontracted, in this order (z = the launch's unit Gaussian draw of (seed, env, step), as without a rule):
+ *     std_eff[c] = exp(logstd[c]) * noise                       once per launch
+ *     a[c]       = fma(std_eff[c], z[c], mean[c])               -> actions_out: the STORED action is never clipped
+ *     logp       = fma(-0.5, noise * sum_c z[c]^2, logp0)       logp0 = -sum(logstd) - nA/2 ln(2 pi); deterministic: logp = logp0
+ *     u[c]       = min(max(a[c], clip_lo), clip_hi)             -> the dynamics; obs, reward, done, the episode statistics and the
+ *                                                                  boot / trunc outputs all follow from u
+ * A non-finite a[c] is not specified.  IDENTITY: with (0, -inf, +inf) every output has the bits it has without a rule for finite
+ * actions (std * 1.0f, 1.0f * q and min / max against the infinities are exact), and such a handle launches exactly the kernels it
+ * launched before.  Any other rule routes the call as a parameter range does: it runs the normalised kernel of its actor (with
+ * identity tables when the call brought no statistics, and the handle's own scratch boot_out when the handle has a time limit and the
+ * call asked for no bootstrap term), so RMAV_POLICY_FP32, RMAV_POLICY_BF16_MFMA and RMAV_REINMAV return RMAV_ERR_INVALID.
+ * The rule affects these three entry points only: rmav_step, rmav_rollout (caller, random and controller actions) never read it - the
+ * caller owns those actions.  The values are kernel arguments: a captured graph keeps the rule it was captured with, as it keeps the
+ * time limit. */
+int rmav_set_policy_action_rule(rmav_handle h, int32_t deterministic, float clip_lo, float clip_hi);
+int rmav_get_policy_action_rule(rmav_handle h, int32_t *deterministic, float *clip_lo, float *clip_hi);
+
+/* ---- return normalisation:the reward half of baselines' VecNormalize(ret=True) in front of GAE -------------------------------------
  * baselines (third-party behaviour restated from memory), per env-step and per env:
  *     R = R * gamma + rew                    R: one float per env, 0 after reset(); gamma = 0.99
  *     ret_rms.update(R)                      ONE scalar RunningMeanStd (mean 0, var 1, count 1e-4; Chan's merge) over all envs

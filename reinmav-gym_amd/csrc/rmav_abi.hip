@@ -747,6 +747,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
     h->flags = flags;
     h->params = pr;
     for (int i = 0; i < RMAV_TUNE_COUNT; ++i) h->tune[i] = -1;
+    h->rule_lo = -__builtin_inff();   // the identity action rule (rmav_set_policy_action_rule)
+    h->rule_hi = __builtin_inff();
     if (adopt_stream(h, hip_stream)) {
         (void)hipGetLastError();
         free_all(h);

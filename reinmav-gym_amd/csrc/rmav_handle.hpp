@@ -95,7 +95,14 @@ struct rmav_env_s {
     float *ident_norm;
     float *boot_scratch;
     size_t boot_scratch_bytes;
+    // action rule of the policy rollouts (rmav_set_policy_action_rule): deterministic = the mean action, [lo, hi] = what the dynamics
+    // clip the action to.  The identity (0, -inf, +inf; rmav_create) launches what a handle without a rule launches; any other rule
+    // routes rmav_rollout_policy / _boot / _norm as a parameter range does - to the normalised kernels, which take it (ActRuleArgs)
+    int32_t rule_det;
+    float rule_lo, rule_hi;
 };
+inline bool has_act_rule(const rmav_env_s *h) { return h->rule_det != 0 || h->rule_lo != -__builtin_inff() || h->rule_hi != __builtin_inff(); }
+inline rmav::ActRuleArgs act_rule_args(const rmav_env_s *h) { return rmav::ActRuleArgs{h->rule_det ? 0.0f : 1.0f, h->rule_lo, h->rule_hi}; }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
 inline rmav::RangeArgs range_args(const rmav_env_s *h, uint32_t mask) {

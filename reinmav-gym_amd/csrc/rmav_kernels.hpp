@@ -299,6 +299,19 @@ __device__ __forceinline__ void range_apply(const RangeArgs &dr, const float *co
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[w]), __builtin_amdgcn_make_buffer_rsrc(dr.pe[w], 0, -1, 0x00020000), off, 0, 0);
 }
 
+// The action rule of the policy rollouts (rmav_set_policy_action_rule; the *_nrm and *_dr policy kernels), trailing as well: what the
+// actors do between the mean head and Env<K>::step.  Three wave-uniform values, by value (scalar registers) - per handle, so not in the
+// caller's statistics buffer, which collectors share.
+//   noise   1.0f = sample, 0.0f = deterministic: std_eff[c] = std[c] * noise (once per launch), stored action a[c] = fma(std_eff[c], z[c],
+//           mean[c]), logp = fma(-0.5, noise * sum z^2, logp0)
+//   lo, hi  the action handed to Env<K>::step is min(max(a[c], lo), hi) (one v_med3_f32; lo <= hi); what is stored stays a[c]
+// The identity {1, -inf, +inf} - what a handle without a rule passes - leaves the bits of every finite action: std * 1.0f, 1.0f * q and
+// the clamp against -inf / +inf are exact.
+struct ActRuleArgs {
+    float noise, lo, hi;
+};
+__device__ __forceinline__ float act_clip(const ActRuleArgs &ar, float a) { return __builtin_amdgcn_fmed3f(a, ar.lo, ar.hi); }
+
 __device__ __forceinline__ uint32_t ep_clock0(const RolloutArgs &a) { return (uint32_t)a.t0; }
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
@@ -427,6 +440,7 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
                                                     const ParamsT<double> pc_shared) {
     constexpr bool TL = false, BOOT = false, NORM = false, DR = false;
     [[maybe_unused]] const RangeArgs dr{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -440,6 +454,7 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
     constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false;
     [[maybe_unused]] const RangeArgs dr{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     static_assert(!is_split(MODE) && K != REINMAV, "time-limited launches run the one-wavefront kernels");
@@ -453,6 +468,7 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_bo
                                                          const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
     constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false;
     [[maybe_unused]] const RangeArgs dr{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const NormArgs nm{};
     static_assert(MODE == ACT_POLICY_F32M && K != REINMAV, "the one-wavefront actor of time-limited handles");
 #include "rmav_rollout_body.inc"
@@ -464,7 +480,7 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_bo
 template <int K, bool BOOT>
 __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
-                                                                            const BootArgs bt) {
+                                                                            const BootArgs bt, const ActRuleArgs ar) {
     // The table pointer rides in RolloutArgs::act_in, which the policy modes do not read: the argument block is k_rollout_boot's.  As a
     // trailing NormArgs (the pair kernels take it that way) the 8 more bytes moved the scalar loads of the argument block, and the
     // quadrotor2d and quadrotor3d kernels came out with a stack frame (64 / 32 bytes per lane, no VGPR spill: these kernels run out of
@@ -483,6 +499,7 @@ template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr) {
     constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "ranged launches run the one-wavefront kernels");
@@ -495,7 +512,7 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_dr
 template <int K, bool BOOT>
 __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                const ParamsT<double> pc_shared, const TimeLimitArgs tl,
-                                                                               const BootArgs bt, const RangeArgs *drp) {
+                                                                               const BootArgs bt, const RangeArgs *drp, const ActRuleArgs ar) {
     // (the range by pointer - the handle's device copy, read with scalar loads on the reset path: as 60 more bytes of kernel arguments
     // it cost three of these kernels, which run out of scalar registers first, a stack frame)
     const RangeArgs &dr = *drp;

@@ -1,7 +1,8 @@
 // rmav_pair_shared_body.inc - the body of k_rollout_pair_shared / k_rollout_pair_shared_tl (rmav_policy_pair.hpp), included into both kernels: textually, for the
 // reason rmav_rollout_body.inc gives.  In scope: template parameters K, the constexpr bools TL, BOOT (k_rollout_pair_shared_boot: the launch also leaves
 // the bootstrap term of its truncated steps) and NORM (k_rollout_pair_shared_nrm: the net takes normalised observations; the tables sit between the
-// weights and the tiles) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm.
+// weights and the tiles) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm, ar (ActRuleArgs: the NORM kernels apply the
+// handle's action rule).
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     using L = MfmaLayout;
     using PT = PairTile<NS, NA>;
@@ -63,14 +64,15 @@
         const float logp0 = -sl - 0.5f * (float)NA * 1.8378770664093453f;
         float *logp_out = a.logp_out, *val_out = a.val_out;
         auto draw = [&](int32_t k) {
-            float z[4];
-            gaussian4(a.seed, env_id, a.t0 + (uint64_t)k, z);
+            float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (!NORM || ar.noise != 0.0f) gaussian4(a.seed, env_id, a.t0 + (uint64_t)k, z);   // (wave-uniform: a deterministic launch draws nothing)
             float *zt = ztile + (k & 1) * PT::Z_HALF;
             float q = 0.0f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) zt[c * 64] = z[c];
 #pragma unroll
             for (int c = 0; c < NA; ++c) q = rfma(z[c], z[c], q);
+            if constexpr (NORM) q *= ar.noise;   // the action rule (deterministic: the log-density of the mean)
             buf_st(make_rsrc(logp_out), off, 0, rfma(-0.5f, q, logp0));
             logp_out += n;
         };
@@ -199,7 +201,7 @@
     }
     float pol_std[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < NA; ++c) pol_std[c] = expf(logstd[c]);
+    for (int c = 0; c < NA; ++c) pol_std[c] = NORM ? expf(logstd[c]) * ar.noise : expf(logstd[c]);   // the action rule: std_eff
     // value of env gi - 32 (tile 0's column lane - 32) leaves through this lane
     const bool vvalid = h && (uint64_t)(gi - 32u) < (uint64_t)n;
     const uint32_t voff = (gi - 32u) * 4u;
@@ -255,7 +257,14 @@
             done = true;
             r = 90.0f;
         } else {
-            Env<K>::step(s, act, p, dist, done);
+            if constexpr (NORM) {   // the action rule: the dynamics take the clipped action, the stored one stays what the policy drew
+                float ca[NA];
+#pragma unroll
+                for (int c = 0; c < NA; ++c) ca[c] = act_clip(ar, act[c]);
+                Env<K>::step(s, ca, p, dist, done);
+            } else {
+                Env<K>::step(s, act, p, dist, done);
+            }
             r = -dist;
             if (done) {
                 r = (sb < 0) ? 1.0f : 0.0f;

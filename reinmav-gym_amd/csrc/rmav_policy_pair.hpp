@@ -240,6 +240,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const R
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
+    [[maybe_unused]] const ActRuleArgs ar{};
 #include "rmav_pair_body.inc"
 }
 // ... under an episode time limit (separate symbols: see k_rollout_tl)
@@ -249,6 +250,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tl(cons
     constexpr bool TL = true, BOOT = false, NORM = false;
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
 #include "rmav_pair_body.inc"
 }
@@ -259,6 +261,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_boot(co
                                                                                const BootArgs bt) {
     constexpr bool TL = true, BOOT = true, NORM = false;
     [[maybe_unused]] const NormArgs nm{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV && FMT == FMT_F16, "the (actor, critic) pair of time-limited handles");
 #include "rmav_pair_body.inc"
 }
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_boot(co
 template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
-                                                                              const BootArgs bt, const NormArgs nm) {
+                                                                              const BootArgs bt, const NormArgs nm, const ActRuleArgs ar) {
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
@@ -279,7 +282,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_nrm(con
 template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl,
-                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr) {
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const ActRuleArgs ar) {
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
@@ -404,6 +407,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
+    [[maybe_unused]] const ActRuleArgs ar{};
 #include "rmav_pair_shared_body.inc"
 }
 template <int K>
@@ -412,6 +416,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     constexpr bool TL = true, BOOT = false, NORM = false;
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
 #include "rmav_pair_shared_body.inc"
 }
@@ -421,6 +426,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
                                                                                       const BootArgs bt) {
     constexpr bool TL = true, BOOT = true, NORM = false;
     [[maybe_unused]] const NormArgs nm{};
+    [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
 #include "rmav_pair_shared_body.inc"
 }
@@ -428,7 +434,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
 template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                      const ParamsT<double> pc_shared, const TimeLimitArgs tl,
-                                                                                     const BootArgs bt, const NormArgs nm) {
+                                                                                     const BootArgs bt, const NormArgs nm, const ActRuleArgs ar) {
     constexpr bool TL = BOOT, NORM = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_shared_body.inc"
@@ -437,7 +443,7 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
 template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl,
-                                                                                    const BootArgs bt, const NormArgs nm, const RangeArgs dr) {
+                                                                                    const BootArgs bt, const NormArgs nm, const RangeArgs dr, const ActRuleArgs ar) {
     constexpr bool TL = BOOT, NORM = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR

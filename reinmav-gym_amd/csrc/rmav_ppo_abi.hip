@@ -93,11 +93,20 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
     h->xchg.allow = true;
     // A handle with a parameter range runs ONE ranged kernel per actor, the normalised one: a call without
     // statistics gets identity tables - z then has the bits of x (rmav_ppo.h) - and a call on a time-limited handle that asked for no
-    // bootstrap term a boot_out of the handle's own.
+    // bootstrap term a boot_out of the handle's own.  A handle whose policy action rule is not the identity goes the same way: the
+    // normalised kernels are the ones that take the rule.
     BootArgs bt_r{};
     NormArgs nm_r{};
-    if (h->range_mask) {
-        if (int rc = need_variants(precision, "a handle with a parameter range", "ranged")) return rc;
+    const bool ruled = has_act_rule(h);
+    if (ruled) {
+        if (h->kind == RMAV_REINMAV)
+            return rmav_fail(RMAV_ERR_INVALID, "a handle with a policy action rule (rmav_set_policy_action_rule) runs the four quadrotor kinds, "
+                                               "not RMAV_REINMAV: there is no action-rule kernel for it");
+        if (int rc = need_variants(precision, "a handle with a policy action rule (rmav_set_policy_action_rule)", "action-rule")) return rc;
+    }
+    if (h->range_mask || ruled) {
+        if (h->range_mask)
+            if (int rc = need_variants(precision, "a handle with a parameter range", "ranged")) return rc;
         if (!nm) {
             if (int rc = ensure_ident_norm(h)) return rc;
             nm_r.tab = h->ident_norm;
@@ -137,6 +146,28 @@ int rmav_rollout_policy_boot(rmav_handle h, int32_t n_steps, const float *weight
     if (int rc = check_policy_args(n_steps, weights, logp_out, value_out, true, boot_out)) return rc;
     const BootArgs bt{boot_out, trunc_out};
     return launch_policy_call(h, n_steps, weights, actions_out, obs_out, rew_out, done_out, logp_out, value_out, precision, &bt, nullptr);
+}
+
+// ---- the action rule of the three entry points above and rmav_rollout_policy_norm: handle state, host only ----------------------------
+int rmav_set_policy_action_rule(rmav_handle h, int32_t deterministic, float clip_lo, float clip_hi) {
+    CHECK_HANDLE(h);
+    if (deterministic != 0 && deterministic != 1) return rmav_fail(RMAV_ERR_INVALID, "deterministic must be 0 or 1, got %d", (int)deterministic);
+    if (!(clip_lo <= clip_hi))   // (false for a NaN on either side)
+        return rmav_fail(RMAV_ERR_INVALID, "the policy action rule needs clip_lo <= clip_hi, neither NaN (-inf / +inf = no bound), got [%g, %g]",
+                         (double)clip_lo, (double)clip_hi);
+    h->rule_det = deterministic;
+    h->rule_lo = clip_lo;
+    h->rule_hi = clip_hi;
+    return RMAV_OK;
+}
+
+int rmav_get_policy_action_rule(rmav_handle h, int32_t *deterministic, float *clip_lo, float *clip_hi) {
+    CHECK_HANDLE(h);
+    if (!deterministic || !clip_lo || !clip_hi) return rmav_fail(RMAV_ERR_INVALID, "deterministic, clip_lo and clip_hi are required");
+    *deterministic = h->rule_det;
+    *clip_lo = h->rule_lo;
+    *clip_hi = h->rule_hi;
+    return RMAV_OK;
 }
 
 // ---- learner-side helpers on the trajectory ----------------------------------------------------

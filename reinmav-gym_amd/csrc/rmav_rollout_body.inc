@@ -3,8 +3,8 @@
 // rather than the kernel's constant argument block - before inlining it, and the kernels came out with a different instruction
 // stream (tools/isa_compare.py, profiles/r07/time_limit.md).  In scope: template parameters K, MODE, ST, FIXED, the constexpr
 // bool TL (the launch has an episode time limit), the constexpr bool BOOT (it also leaves the bootstrap term of truncated steps:
-// k_rollout_boot), the constexpr bool NORM (the nets take normalised observations: k_rollout_nrm) and the kernel arguments a,
-// p_shared, pc_shared, tl, bt, nm.
+// k_rollout_boot), the constexpr bool NORM (the nets take normalised observations: k_rollout_nrm - the kernels that also apply the
+// handle's action rule `ar`, ActRuleArgs) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm, ar.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     constexpr int AUX = StoreAux<ST>::value;
     // ACT_RANDOM_SPLIT: 128-thread workgroups, both wavefronts address the same 64 envs
@@ -536,6 +536,7 @@
             for (int c = 0; c < NA; ++c) {
                 const float ls = lds_w[(MODE == ACT_POLICY ? PolicyLayout<NS>::LOGSTD : MODE == ACT_POLICY_F32M ? Mfma32Layout::LOGSTD : MfmaLayout::LOGSTD) + c];
                 pol_std[c] = expf(ls);
+                if constexpr (NORM) pol_std[c] *= ar.noise;   // the action rule: std_eff (noise = 1: the same bits)
                 sl += ls;
             }
             pol_logp0 = -sl - 0.5f * (float)NA * 1.8378770664093453f;
@@ -615,6 +616,7 @@
                     act[c] = rfma(pol_std[c], z[c], mean[c]);
                     q = rfma(z[c], z[c], q);
                 }
+                if constexpr (NORM) q *= ar.noise;   // deterministic: the log-density of the mean
                 buf_st(make_rsrc(logp_out), off, 0, rfma(-0.5f, q, pol_logp0));
                 buf_st(make_rsrc(val_out), off, 0, val0);
                 logp_out += n;
@@ -695,7 +697,14 @@
                 done = true;   // reinmav_env.py:110
                 r = 90.0f;     // reinmav_env.py:111-116: 100 - 10, every step
             } else {
-                Env<K>::step(s, act, p, dist, done);
+                if constexpr (NORM) {   // the action rule: the dynamics take the clipped action, `act` (stored below) stays what the policy drew
+                    float ca[NA];
+#pragma unroll
+                    for (int c = 0; c < NA; ++c) ca[c] = act_clip(ar, act[c]);
+                    Env<K>::step(s, ca, p, dist, done);
+                } else {
+                    Env<K>::step(s, act, p, dist, done);
+                }
                 // reward / steps_beyond_done machine  (quadrotor3d.py:112-122 and siblings)
                 r = -dist;
                 if (done) {

@@ -145,6 +145,8 @@ PROTOTYPES = {
     "rmav_obs_norm_merge": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int32]),
     "rmav_obs_normalize": (C.c_int, [C.c_void_p, _vp, _fp, _fp, C.c_int, C.c_int32, C.c_int64]),
     "rmav_rollout_policy_norm": (C.c_int, [C.c_void_p, C.c_int32, _fp, _vp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),
+    "rmav_set_policy_action_rule": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float]),
+    "rmav_get_policy_action_rule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rmav_ret_norm_bytes": (C.c_int64, []),
     "rmav_ret_norm_init": (C.c_int, [C.c_void_p, _vp, C.c_float, C.c_double, C.c_double]),
     "rmav_ret_moments": (C.c_int, [C.c_void_p, C.c_int32, _fp, _u8p, C.c_float, C.c_float, _fp, _vp]),

@@ -36,6 +36,27 @@ def _layout(layout: str) -> int:
     return A.AOS if layout == "aos" else A.SOA
 
 
+def policy_action_rule(deterministic, clip, box=None):
+    """The arguments of ``rmav_set_policy_action_rule`` from the Python form: -> ``(deterministic 0 | 1, lo, hi)``.  ``clip``: ``None`` /
+    ``False`` = no bound, ``True`` = ``box()`` (the env's action space), ``(lo, hi)`` = explicit.  Raises ValueError on anything else."""
+    if not isinstance(deterministic, (bool, np.bool_)) and not (isinstance(deterministic, (int, np.integer)) and deterministic in (0, 1)):
+        raise ValueError(f"deterministic must be a bool, got {deterministic!r}")
+    if clip is None or clip is False:
+        lo, hi = -np.inf, np.inf
+    elif clip is True:
+        if box is None:
+            raise ValueError("clip=True needs an action space")
+        lo, hi = (float(v) for v in box())
+    else:
+        try:
+            lo, hi = (float(v) for v in clip)
+        except (TypeError, ValueError):
+            raise ValueError(f"clip must be None, True or a pair (lo, hi), got {clip!r}") from None
+    if not lo <= hi:   # (false for a NaN on either side)
+        raise ValueError(f"clip needs lo <= hi, neither NaN; got ({lo}, {hi})")
+    return int(bool(deterministic)), lo, hi
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
@@ -124,6 +145,23 @@ class BatchedQuadrotor:
     @max_episode_steps.setter
     def max_episode_steps(self, h: Optional[int]):
         A.check(self._lib.rmav_set_time_limit(self._h, int(h or 0)))
+
+    def set_policy_action_rule(self, deterministic: bool = False, clip=None):
+        """What the in-kernel policy rollouts (``rmav_rollout_policy`` / ``_boot`` / ``_norm``: :class:`~gym_reinmav_amd.ppo.FusedPolicyCollector`)
+        do between the policy's mean head and the dynamics (``rmav_set_policy_action_rule``, include/rmav_ppo.h).
+
+        ``deterministic=True``: the mean action (stable-baselines' ``predict(deterministic=True)``); ``logp`` is then the log-density of
+        the mean.  ``clip``: ``None`` / ``False`` = none, ``True`` = the env's action space ``(params.act_lo, params.act_hi)``,
+        ``(lo, hi)`` = explicit bounds; the dynamics take ``clip(action, lo, hi)`` while the STORED action and its ``logp`` stay
+        unclipped, as in stable-baselines' PPO2 runner.  ``step``, ``rollout`` and the per-step collectors never read the rule.  Host only."""
+        det, lo, hi = policy_action_rule(deterministic, clip, lambda: (self.params.act_lo, self.params.act_hi))
+        A.check(self._lib.rmav_set_policy_action_rule(self._h, det, lo, hi))
+
+    def get_policy_action_rule(self):
+        """``(deterministic, (lo, hi))`` as :meth:`set_policy_action_rule` stored them; no clip is ``(-inf, inf)``."""
+        d, lo, hi = C.c_int32(), C.c_float(), C.c_float()
+        A.check(self._lib.rmav_get_policy_action_rule(self._h, C.byref(d), C.byref(lo), C.byref(hi)))
+        return bool(d.value), (lo.value, hi.value)
 
     def episode_truncated(self, device_out: bool = False):
         """u8 [N]: 1 where the env's most recently finished episode was truncated by the time limit, 0 where it terminated

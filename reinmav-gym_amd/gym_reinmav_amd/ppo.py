@@ -27,7 +27,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from .core import BatchedQuadrotor
+from .core import BatchedQuadrotor, policy_action_rule
 
 
 class _LinearFM(torch.autograd.Function):
@@ -126,14 +126,23 @@ class MlpPolicy(torch.nn.Module):
 class RolloutCollector:
     """Collects ``nsteps`` transitions of every env into device-resident, time-major, feature-major buffers."""
 
-    def __init__(self, env: BatchedQuadrotor, policy: MlpPolicy, nsteps: int, graph: bool = False, bootstrap_truncated: bool = False):
-        """``bootstrap_truncated=True`` (needs ``env.max_episode_steps``): the collector also owns ``boot [T, N]`` - the value net on
+    def __init__(self, env: BatchedQuadrotor, policy: MlpPolicy, nsteps: int, graph: bool = False, bootstrap_truncated: bool = False,
+                 deterministic: bool = False, clip_actions=False):
+        """``deterministic=True``: the mean action, no noise (``logp`` = the log-density of the mean).  ``clip_actions``: ``True`` = the
+        env steps with ``clamp(act, params.act_lo, params.act_hi)``, ``(lo, hi)`` = explicit bounds; ``act`` and ``logp`` stay those of
+        the unclipped action, as in stable-baselines' PPO2 runner.  The semantics of :class:`FusedPolicyCollector`'s arguments of the
+        same names (``rmav_set_policy_action_rule``); ``graph=True`` still captures.
+
+        ``bootstrap_truncated=True`` (needs ``env.max_episode_steps``): the collector also owns ``boot [T, N]`` - the value net on
         the state a truncated episode ended in (``rmav_step_final``'s ``final_obs``, which the auto-reset has replaced in ``obs``), 0
         where the step was not truncated - and ``trunc [T, N]``; ``PPO.update`` then targets ``r + gamma V(s_final)`` on those steps.
         One more policy forward per step, no host synchronisation: ``graph=True`` still captures (the env's ``step_count`` then stays
         where it was at the capture: the replayed launches carry their episode clock with them, see ``_capture``)."""
         assert env.auto_reset, "rollouts need VecEnv semantics (auto-reset)"
         self.env, self.policy, self.T = env, policy, int(nsteps)
+        det, lo, hi = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
+        self.deterministic = bool(det)
+        self.clip = None if (lo, hi) == (-math.inf, math.inf) else (lo, hi)
         self.boot = self.trunc = None
         if bootstrap_truncated:
             if not env.max_episode_steps:
@@ -151,6 +160,7 @@ class RolloutCollector:
         self.val = torch.empty((T + 1, N), **f32)
         self.rew = torch.empty((T, N), **f32)
         self.done = torch.empty((T, N), dtype=torch.uint8, device=dev)
+        self._act_env = torch.empty((nA, N), **f32) if self.clip is not None else None   # what the env is stepped with
         self.obs[0].copy_(env.get_state(layout="soa", device_out=True))
         self._graph = None
         if graph:
@@ -159,14 +169,21 @@ class RolloutCollector:
     # one env-step of the loop baselines' Runner.run() executes (model.step -> env.step)
     def _step(self, t: int):
         mean, v = self.policy(self.obs[t])
-        noise = torch.randn_like(mean)
-        torch.addcmul(mean, noise, torch.exp(self.policy.logstd)[:, None], out=self.act[t])
-        self.logp[t] = -0.5 * (noise * noise).sum(0) - self.policy.logstd.sum() - 0.5 * mean.shape[0] * math.log(2 * math.pi)
-        self.val[t] = v
-        if self.boot is None:
-            self.env.step(self.act[t], layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t]))
+        if self.deterministic:   # noise x 0: the mean, and the log-density of the mean
+            self.act[t].copy_(mean)
+            self.logp[t] = -self.policy.logstd.sum() - 0.5 * mean.shape[0] * math.log(2 * math.pi)
         else:
-            self.env.step_final(self.act[t], layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t], self._final, self.trunc[t]))
+            noise = torch.randn_like(mean)
+            torch.addcmul(mean, noise, torch.exp(self.policy.logstd)[:, None], out=self.act[t])
+            self.logp[t] = -0.5 * (noise * noise).sum(0) - self.policy.logstd.sum() - 0.5 * mean.shape[0] * math.log(2 * math.pi)
+        self.val[t] = v
+        act = self.act[t]   # stored (and learned from) unclipped; the env takes the clipped one
+        if self.clip is not None:
+            act = torch.clamp(act, self.clip[0], self.clip[1], out=self._act_env)
+        if self.boot is None:
+            self.env.step(act, layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t]))
+        else:
+            self.env.step_final(act, layout="soa", out=(self.obs[t + 1], self.rew[t], self.done[t], self._final, self.trunc[t]))
             torch.where(self.trunc[t] != 0, self.policy(self._final)[1], self.boot.new_zeros(()), out=self.boot[t])
 
     def _body(self):
@@ -466,8 +483,18 @@ class FusedPolicyCollector:
     that owns the env (``rmav_rollout_policy``), so nothing but the trajectory touches HBM."""
 
     def __init__(self, env: BatchedQuadrotor, policy: MlpPolicy, nsteps: int, bf16_mfma: bool = False,
-                 f32_mfma: Optional[bool] = None, native_pack: bool = True, f16_mfma: bool = False, bootstrap_truncated: bool = False):
-        """Actor arithmetic: fp32 on the fp32-input matrix instructions (``v_mfma_f32_32x32x2_f32``; the default),
+                 f32_mfma: Optional[bool] = None, native_pack: bool = True, f16_mfma: bool = False, bootstrap_truncated: bool = False,
+                 deterministic: bool = False, clip_actions=False, store_trajectory: bool = True):
+        """``store_trajectory=False``: the launch gets NULL for ``actions_out`` / ``obs_out`` (``act`` and ``obs`` are None) and only
+        ``rew``, ``done``, ``logp``, ``val`` (and ``boot`` / ``trunc``) reach HBM - what an evaluation needs (``evaluate.py``); such a
+        collector cannot feed ``PPO.update``.
+
+        ``deterministic`` / ``clip_actions`` (``True`` = the env's action space, or ``(lo, hi)``): the action rule of the launch
+        (``BatchedQuadrotor.set_policy_action_rule``) - the mean action instead of a sample, and dynamics that take the clipped action
+        while ``act`` / ``logp`` stay those of the unclipped one.  ``collect()`` sets the rule on the env before every launch, so a
+        training collector and an evaluating one can share an env.  The fp32 matrix-core actor, ``f16_mfma=True`` or a shared-trunk policy.
+
+        Actor arithmetic: fp32 on the fp32-input matrix instructions (``v_mfma_f32_32x32x2_f32``; the default),
         ``f32_mfma=False`` fp32 FMAs on the vector ALU (same precision class - only the summation order differs - at
         half the speed), ``bf16_mfma=True`` bf16 operands on the matrix cores (~1e-2 on means), ``f16_mfma=True`` f16
         operands with tanh folded into the next layer (the fastest, ~1e-3 on means; csrc/rmav_policy_pair.hpp).
@@ -506,6 +533,9 @@ class FusedPolicyCollector:
                 refuse("an env with randomize= / set_env_param_range", "ranged")
             if norm is not None:
                 refuse("a policy with obs_norm", "normalised")
+        self._rule = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
+        if not has_variants and self._rule != (0, -math.inf, math.inf):
+            refuse("deterministic= / clip_actions=", "action-rule")
         if norm is not None:
             if limited and not bootstrap_truncated:
                 raise ValueError("a policy with obs_norm on an env with max_episode_steps needs bootstrap_truncated=True "
@@ -519,8 +549,8 @@ class FusedPolicyCollector:
         dev = torch.device("cuda", env.device)
         N, nS, nA, T = env.num_envs, env.nS, env.nA, self.T
         f32 = dict(dtype=torch.float32, device=dev)
-        self.obs = torch.empty((T + 1, nS, N), **f32)
-        self.act = torch.empty((T, nA, N), **f32)
+        self.obs = torch.empty((T + 1, nS, N), **f32) if store_trajectory else None
+        self.act = torch.empty((T, nA, N), **f32) if store_trajectory else None
         self.logp = torch.empty((T, N), **f32)
         self.val = torch.empty((T + 1, N), **f32)
         self.rew = torch.empty((T, N), **f32)
@@ -530,7 +560,8 @@ class FusedPolicyCollector:
         assert self.weights.data_ptr() % 16 == 0
         self._packer = _PolicyPacker(policy, env.nS, actor)
         assert self._packer.n_out == n_w, (self._packer.n_out, n_w)
-        self.obs[0].copy_(env.get_state(layout="soa", device_out=True))
+        if store_trajectory:
+            self.obs[0].copy_(env.get_state(layout="soa", device_out=True))
         # The weight repack before every rollout: one gather launch behind the C ABI (rmav_pack_policy).  As ~8 dependent torch
         # launches (cat, gather, bf16 conversion, cat, copy) it cost ~38 us of a 0.21 ms rollout at 65 536 envs x 32 steps; a
         # hipGraph of those launches replayed no faster (the dependent-launch floor, not the host, is what they cost).
@@ -550,7 +581,8 @@ class FusedPolicyCollector:
             fn, stats, boot = A.lib().rmav_rollout_policy_boot, (), (p(self.boot), p(self.trunc))
         else:
             fn, stats, boot = A.lib().rmav_rollout_policy, (), ()
-        outs = (p(self.act), p(self.obs[1:]), p(self.rew), p(self.done), p(self.logp), p(self.val))
+        traj = (p(self.act), p(self.obs[1:])) if store_trajectory else (None, None)
+        outs = traj + (p(self.rew), p(self.done), p(self.logp), p(self.val))
         self._call = (fn, self.T, p(self.weights)) + stats + outs + boot + (getattr(A, precision),)
 
     def _pack(self):
@@ -559,16 +591,23 @@ class FusedPolicyCollector:
         else:
             self._packer.pack(out=self.weights)
 
-    def collect(self):
+    def collect(self, nsteps: Optional[int] = None):
+        """One launch of ``nsteps`` steps (default, and at most, the collector's ``nsteps``: a shorter launch fills the first rows of
+        the buffers and leaves its bootstrap value in ``val[nsteps]``)."""
         if self.env._h is None:
             raise self._A.RmavError(self._A.ERR_INVALID, "the env of this collector is closed")
+        T = self.T if nsteps is None else int(nsteps)
+        if not 0 < T <= self.T:
+            raise ValueError(f"nsteps must be in [1, {self.T}]")
         self._pack()
         fn = self._call[0]
-        self._A.check(fn(self.env._h, *self._call[1:]))
+        self._A.check(self._A.lib().rmav_set_policy_action_rule(self.env._h, *self._rule))   # host only: this collector's rule, not the last one's
+        self._A.check(fn(self.env._h, T, *self._call[2:]))
         return self
 
     def roll_over(self):
-        self.obs[0].copy_(self.obs[self.T])
+        if self.obs is not None:
+            self.obs[0].copy_(self.obs[self.T])
 
 
 def gae(rew, val, done, gamma: float = 0.99, lam: float = 0.95, boot=None):
