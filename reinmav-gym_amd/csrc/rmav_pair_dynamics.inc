@@ -1,0 +1,38 @@
+// rmav_pair_dynamics.inc - one env-step of the stepping wavefront once its action is known: the dynamics, the reward /
+// steps_beyond_done machine and the head of the time limit, in the step loop of both pair bodies.
+//   expects:  K, NA, the constexpr bools TL and NORM, the kernel arguments ar (ActRuleArgs) and - TL - tl (TimeLimitArgs); act[NA] (the
+//             action the policy drew), p, li, el
+//   defines:  dist, r (the step's reward), done (terminated or - TL - truncated)
+//   modifies: s (the state after the step), tenv (REINMAV), sb; stores one byte of tl.last_trunc where an episode ends (TL)
+//   leaves OPEN: the block of its last statement, `if constexpr (TL) {`, with `const bool trunc` (this lane's episode ran into the limit
+//             in this step) declared in it.  The includer follows the include with its BOOT part, which needs trunc and differs between
+//             the two bodies, and closes the block.  (Declaring trunc in front of the block instead, so that the fragment could close
+//             it, changed the register numbering of two kernels WITHOUT a time limit: profiles/r15/body_fragments.md.)
+//   barriers: none (between X(k) / B(k - 1) and the barrier that ends step k)
+        float dist = 0.0f, r;
+        bool done;
+        if constexpr (K == REINMAV) {
+            float fm0[4];
+            Env<K>::step(s, act, false, tenv, p, fm0);
+            done = true;   // reinmav_env.py:110
+            r = 90.0f;     // reinmav_env.py:111-116
+        } else {
+            if constexpr (NORM) {   // the action rule: the dynamics take the clipped action, the stored one stays what the policy drew
+                float ca[NA];
+#pragma unroll
+                for (int c = 0; c < NA; ++c) ca[c] = act_clip(ar, act[c]);
+                Env<K>::step(s, ca, p, dist, done);
+            } else {
+                Env<K>::step(s, act, p, dist, done);
+            }
+            r = -dist;     // reward / steps_beyond_done machine  (quadrotor3d.py:112-122 and siblings)
+            if (done) {
+                r = (sb < 0) ? 1.0f : 0.0f;
+                sb = (sb < 0) ? 0 : sb + 1;
+            }
+        }
+        // time limit (see k_rollout): after the reward / steps_beyond_done machine, before the episode hand-off
+        if constexpr (TL) {
+            const bool trunc = !done && el + 1 >= tl.max_steps;
+            done = done || trunc;
+            if (done) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(tl.last_trunc), li, 0, 0);

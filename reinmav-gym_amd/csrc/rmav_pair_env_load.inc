@@ -1,0 +1,60 @@
+// rmav_pair_env_load.inc - what the stepping wavefront (the actor of rmav_pair_body.inc, wavefront A of rmav_pair_shared_body.inc)
+// carries through the step loop besides the state: the first statements of its part in both pair bodies.
+//   expects:  K, NS, NA, L (MfmaLayout), the constexpr bools TL and NORM, the preprocessor flag RMAV_PAIR_DR (set by the *_dr wrappers
+//             around the include of the BODY, rmav_policy_pair.hpp; a nested include sees it), the kernel arguments a, p_shared,
+//             pc_shared, ar and - RMAV_PAIR_DR - dr; logstd, env_id, li, off, T, track, auto_reset
+//   defines:  the episode totals of this lane fin_n, fin_len, fin_ret; the running episode er (return), el (length); the env's record
+//             sb (steps_beyond_done), rc (reset counter); the env's constants pl and the reference p the dynamics take; tenv; the spare
+//             reset state spare[NS] with have_spare and - RMAV_PAIR_DR - the constants of the episode it starts, spare_pe[3]; pol_std[4]
+//   modifies: nothing else (loads only: a.ep_ret, a.rec, a.pe, a.env_time)
+//   barriers: in front of the barrier that opens the step loop (B / P): it reads logstd, not the tiles
+    unsigned int fin_n = 0, fin_len = 0;
+    float fin_ret = 0.0f;
+    float er = 0.0f;
+    int32_t el = 0;
+    int32_t sb;   // the env's record (EnvRec): steps_beyond_done, reset counter and - when tracking - the episode's start in ONE access
+    uint32_t rc;
+    if (track) {
+        er = buf_ld(make_rsrc(a.ep_ret), off, 0);
+        const u32x3_t q = rec_ld3(make_rsrc(a.rec), li);
+        sb = (int32_t)q.x;
+        rc = q.y;
+        el = (int32_t)(ep_clock0(a) - q.z);
+    } else if (TL) {   // (the running length is counted whether or not the handle tracks episodes)
+        const u32x3_t q = rec_ld3(make_rsrc(a.rec), li);
+        sb = (int32_t)q.x;
+        rc = q.y;
+        el = (int32_t)(ep_clock0(a) - q.z);
+    } else {
+        const u32x2_t q = rec_ld2(make_rsrc(a.rec), li);
+        sb = (int32_t)q.x;
+        rc = q.y;
+    }
+    typename Env<K>::P pl = p_shared;
+    if constexpr (K != REINMAV) {
+        if (a.pe[0] || a.pe[1] || a.pe[2]) {
+            const double m = a.pe[0] ? (double)a.pe[0][li] : (double)pc_shared.mass;
+            const double ml = a.pe[1] ? (double)a.pe[1][li] : (double)pc_shared.load_mass;
+            const double Lt = a.pe[2] ? (double)a.pe[2][li] : (double)pc_shared.L;
+            override_params(pl, m, ml, Lt);
+        }
+    }
+    const typename Env<K>::P &p = pl;
+    double tenv = 0.0;
+    if constexpr (K == REINMAV) tenv = a.env_time[li];
+    // spare reset state, drawn once per launch (see k_rollout)
+    float spare[NS];
+    bool have_spare = false;
+#if RMAV_PAIR_DR   // the *_dr kernels: the constants of the episode the spare state starts (the ranged parameters' elements)
+    float spare_pe[3] = {0.0f, 0.0f, 0.0f};
+#endif
+    if (K != REINMAV && auto_reset && T >= 8) {
+        reset_state<K>(a.seed, env_id, rc, spare);
+#if RMAV_PAIR_DR
+        range_draw(dr, a.seed, env_id, rc, spare_pe);
+#endif
+        have_spare = true;
+    }
+    float pol_std[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < NA; ++c) pol_std[c] = NORM ? expf(logstd[c]) * ar.noise : expf(logstd[c]);   // the action rule: std_eff

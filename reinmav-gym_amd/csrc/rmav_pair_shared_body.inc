@@ -3,21 +3,15 @@
 // the bootstrap term of its truncated steps) and NORM (k_rollout_pair_shared_nrm: the net takes normalised observations; the tables sit between the
 // weights and the tiles) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm, ar (ActRuleArgs: the NORM kernels apply the
 // handle's action rule).
+//
+// The statements this body has in common with rmav_pair_body.inc are nested fragments both include, one file each (rmav_pair_index.inc,
+// _draw, _env_load, _dynamics, _episode, _epilogue): each opens with the names it expects, defines and modifies and the barrier it sits
+// next to.  What differs between the two kernels - how the nets are evaluated, the hand-over of the means, the BOOT parts - is here.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     using L = MfmaLayout;
     using PT = PairTile<NS, NA>;
     using ST_ = SharedTile<NS, NA>;
-    const uint32_t G = blockDim.x >> 7;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool helper = wave >= G;
-    const uint32_t pair = helper ? wave - G : wave, lane = threadIdx.x & 63u, h = lane >> 5;
-    const uint32_t gi = (blockIdx.x * G + pair) * 64u + lane;
-    const int64_t n = a.n;
-    const bool valid = gi < (uint64_t)n;
-    const uint32_t li = valid ? gi : (uint32_t)n - 1u;
-    const uint32_t col = (uint32_t)n * 4u, off = li * 4u;
-    const int32_t T = a.n_steps;
-    const bool track = (a.flags & F_TRACK) != 0, auto_reset = (a.flags & F_AUTO_RESET) != 0;
+#include "rmav_pair_index.inc"   // G, wave, helper (wavefront B), pair, lane, h, gi, n, valid, li, col, off, T, track, auto_reset
     [[maybe_unused]] const float *ntab = lds_w + kSharedWeights;
     float *tile = lds_w + kSharedWeights + (NORM ? kNormWords : 0) + pair * (BOOT ? SharedBootTile<NS, NA>::WORDS : ST_::WORDS);
     float *ztile = tile + lane, *otile = tile + PT::Z_WORDS + lane, *mtile = tile + ST_::MEAN;
@@ -58,24 +52,7 @@
 
     if (helper) {
         // ---- B: tile 1 of the net, noise one step ahead, log-prob, every trajectory store ---------------------------------------
-        float sl = 0.0f;
-#pragma unroll
-        for (int c = 0; c < NA; ++c) sl += logstd[c];
-        const float logp0 = -sl - 0.5f * (float)NA * 1.8378770664093453f;
-        float *logp_out = a.logp_out, *val_out = a.val_out;
-        auto draw = [&](int32_t k) {
-            float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (!NORM || ar.noise != 0.0f) gaussian4(a.seed, env_id, a.t0 + (uint64_t)k, z);   // (wave-uniform: a deterministic launch draws nothing)
-            float *zt = ztile + (k & 1) * PT::Z_HALF;
-            float q = 0.0f;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) zt[c * 64] = z[c];
-#pragma unroll
-            for (int c = 0; c < NA; ++c) q = rfma(z[c], z[c], q);
-            if constexpr (NORM) q *= ar.noise;   // the action rule (deterministic: the log-density of the mean)
-            buf_st(make_rsrc(logp_out), off, 0, rfma(-0.5f, q, logp0));
-            logp_out += n;
-        };
+#include "rmav_pair_draw.inc"   // logp0, logp_out, val_out, draw(k)
         // the net for envs 32..63 of the pair from the obs tile half `half`: lane (n, h) takes components [8h, 8h + 8) of env 32 + n
         auto eval_tile1 = [&](int half) {
             const float *obs = tile + PT::Z_WORDS + half * PT::O_HALF + 32u + (lane & 31u);
@@ -153,55 +130,7 @@
     float s[NS];
 #pragma unroll
     for (int c = 0; c < NS; ++c) s[c] = buf_ld(r_state, off, (uint32_t)c * col);
-    unsigned int fin_n = 0, fin_len = 0;
-    float fin_ret = 0.0f;
-    float er = 0.0f;
-    int32_t el = 0;
-    int32_t sb;   // the env's record (EnvRec): steps_beyond_done, reset counter and - when tracking - the episode's start in ONE access
-    uint32_t rc;
-    if (track) {
-        er = buf_ld(make_rsrc(a.ep_ret), off, 0);
-        const u32x3_t q = rec_ld3(make_rsrc(a.rec), li);
-        sb = (int32_t)q.x;
-        rc = q.y;
-        el = (int32_t)(ep_clock0(a) - q.z);
-    } else if (TL) {   // (the running length is counted whether or not the handle tracks episodes)
-        const u32x3_t q = rec_ld3(make_rsrc(a.rec), li);
-        sb = (int32_t)q.x;
-        rc = q.y;
-        el = (int32_t)(ep_clock0(a) - q.z);
-    } else {
-        const u32x2_t q = rec_ld2(make_rsrc(a.rec), li);
-        sb = (int32_t)q.x;
-        rc = q.y;
-    }
-    typename Env<K>::P pl = p_shared;
-    if constexpr (K != REINMAV) {
-        if (a.pe[0] || a.pe[1] || a.pe[2]) {
-            const double m = a.pe[0] ? (double)a.pe[0][li] : (double)pc_shared.mass;
-            const double ml = a.pe[1] ? (double)a.pe[1][li] : (double)pc_shared.load_mass;
-            const double Lt = a.pe[2] ? (double)a.pe[2][li] : (double)pc_shared.L;
-            override_params(pl, m, ml, Lt);
-        }
-    }
-    const typename Env<K>::P &p = pl;
-    double tenv = 0.0;
-    if constexpr (K == REINMAV) tenv = a.env_time[li];
-    float spare[NS];
-    bool have_spare = false;
-#if RMAV_PAIR_DR   // the *_dr kernels: the constants of the episode the spare state starts (the ranged parameters' elements)
-    float spare_pe[3] = {0.0f, 0.0f, 0.0f};
-#endif
-    if (K != REINMAV && auto_reset && T >= 8) {
-        reset_state<K>(a.seed, env_id, rc, spare);
-#if RMAV_PAIR_DR
-        range_draw(dr, a.seed, env_id, rc, spare_pe);
-#endif
-        have_spare = true;
-    }
-    float pol_std[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < NA; ++c) pol_std[c] = NORM ? expf(logstd[c]) * ar.noise : expf(logstd[c]);   // the action rule: std_eff
+#include "rmav_pair_env_load.inc"   // fin_*, er, el, sb, rc, pl / p, tenv, spare, have_spare, pol_std
     // value of env gi - 32 (tile 0's column lane - 32) leaves through this lane
     const bool vvalid = h && (uint64_t)(gi - 32u) < (uint64_t)n;
     const uint32_t voff = (gi - 32u) * 4u;
@@ -249,33 +178,7 @@
                 act[c] = rfma(pol_std[c], zt[c * 64], mean);
             }
         }
-        float dist = 0.0f, r;
-        bool done;
-        if constexpr (K == REINMAV) {
-            float fm0[4];
-            Env<K>::step(s, act, false, tenv, p, fm0);
-            done = true;
-            r = 90.0f;
-        } else {
-            if constexpr (NORM) {   // the action rule: the dynamics take the clipped action, the stored one stays what the policy drew
-                float ca[NA];
-#pragma unroll
-                for (int c = 0; c < NA; ++c) ca[c] = act_clip(ar, act[c]);
-                Env<K>::step(s, ca, p, dist, done);
-            } else {
-                Env<K>::step(s, act, p, dist, done);
-            }
-            r = -dist;
-            if (done) {
-                r = (sb < 0) ? 1.0f : 0.0f;
-                sb = (sb < 0) ? 0 : sb + 1;
-            }
-        }
-        // time limit (see k_rollout): after the reward / steps_beyond_done machine, before the episode hand-off
-        if constexpr (TL) {
-            const bool trunc = !done && el + 1 >= tl.max_steps;
-            done = done || trunc;
-            if (done) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(trunc ? 1 : 0), make_rsrc(tl.last_trunc), li, 0, 0);
+#include "rmav_pair_dynamics.inc"   // dist, r, done; LEAVES OPEN `if constexpr (TL) {` with `const bool trunc` in it:
             // k_rollout_pair_shared_boot: on a step with a truncated lane both wavefronts run the net once more on the state the reset
             // below replaces - this one for envs 0..31 from its registers (the value of env n leaves lane 32 + n, as eval_tile0's), B
             // for envs 32..63 from the row's terminal area (SharedBootTile); the DONE word tells B which lanes
@@ -312,88 +215,12 @@
                 if (vvalid) buf_st(make_rsrc(bt.boot_out + (int64_t)k * n), voff, 0, bv);
                 otile[(k & 1) * PT::O_HALF + PT::DONE] = trunc ? 2.0f : (done ? 1.0f : 0.0f);
             }
-        }
-        if (track) {
-            er += r;
-            el += 1;
-            if (done) {
-                buf_st(make_rsrc(a.last_ret), off, 0, er);
-                rec_st_last_len(make_rsrc(a.rec), li, el);
-                if (valid) {
-                    fin_n += 1;
-                    fin_len += (unsigned int)el;
-                    fin_ret += er;
-                }
-                er = 0.0f;
-                el = 0;
-            }
-        } else if (TL) {
-            el += 1;
-            if (done) el = 0;
-        }
-        if (K != REINMAV && auto_reset) {
-            if (__ballot(done && !have_spare) != 0) {
-                if (!have_spare) {   // every lane that has used its spare up (see k_rollout)
-                    reset_state<K>(a.seed, env_id, rc, spare);
-            #if RMAV_PAIR_DR
-        range_draw(dr, a.seed, env_id, rc, spare_pe);
-#endif
-                    have_spare = true;
-                }
-            }
-            if (done) {
-#pragma unroll
-                for (int c = 0; c < NS; ++c) s[c] = spare[c];
-#if RMAV_PAIR_DR
-                range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl);   // the new episode's constants, re-derived and stored
-#endif
-                have_spare = false;
-                rc += 1;
-            }
-        }
-        float *row = otile + (k & 1) * PT::O_HALF;
-#pragma unroll
-        for (int c = 0; c < NS; ++c) row[c * 64] = s[c];
-        row[PT::REW] = r;
-        if constexpr (!BOOT) row[PT::DONE] = done ? 1.0f : 0.0f;
-#pragma unroll
-        for (int c = 0; c < NA; ++c) row[PT::ACT + c * 64] = act[c];
+        }   // if constexpr (TL), opened in rmav_pair_dynamics.inc
+#include "rmav_pair_episode.inc"   // episode bookkeeping, auto-reset, the row of step k
         __syncthreads();                                                  // Y(k)
     }
     {
         float o4[4];
         eval_tile0(o4);                                                   // bootstrap values of envs 0..31
     }
-#pragma unroll
-    for (int c = 0; c < NS; ++c) buf_st(r_state, off, (uint32_t)c * col, s[c]);
-    if constexpr (K == REINMAV) a.env_time[li] = tenv;
-    if (track) {
-        buf_st(make_rsrc(a.ep_ret), off, 0, er);
-        rec_st3(make_rsrc(a.rec), li, u32x3_t{(uint32_t)sb, rc, ep_clock0(a) + (uint32_t)a.n_steps - (uint32_t)el});
-    } else if (TL) {
-        rec_st3(make_rsrc(a.rec), li, u32x3_t{(uint32_t)sb, rc, ep_clock0(a) + (uint32_t)a.n_steps - (uint32_t)el});
-    } else {
-        rec_st2(make_rsrc(a.rec), li, u32x2_t{(uint32_t)sb, rc});
-    }
-    if (track && __ballot(fin_n != 0) != 0) {
-        Totals *slot = a.totals + (gi >> 6);
-        const unsigned int wn = wave_sum_x(fin_n);
-        const unsigned int wl = wave_sum_x(fin_len);
-        const float wr = wave_sum_x(fin_ret);
-        if (lane == 0) {
-            atomicAdd(&slot->episodes, (unsigned long long)wn);
-            atomicAdd(&slot->length_sum, (unsigned long long)wl);
-            atomicAdd(&slot->return_sum, (double)wr);
-        }
-    }
-    if (a.xsend) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (valid) {
-            const float lr = a.last_ret[li];
-            const int32_t ll = a.rec[li].last_len;
-            __hip_atomic_store(a.xsend + li, __builtin_bit_cast(int32_t, lr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(a.xsend + a.xcmax + li, ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0 && valid) __hip_atomic_store(a.xarrive + (gi >> 6), a.xseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+#include "rmav_pair_epilogue.inc"   // state and record write-back, episode totals, statistics-exchange snapshot

@@ -30,9 +30,9 @@
 
 #include "rmav_kernels.hpp"
 
-// RMAV_PAIR_DR: the pair bodies (rmav_pair_body.inc, rmav_pair_shared_body.inc) compile the redraw of a ranged handle's constants
-// (rmav_set_env_param_range) only where a *_dr wrapper sets it around its #include.  A preprocessor flag, not a constexpr one like TL /
-// BOOT / NORM: even a dead local declaration in the bodies changed the register allocation of the bf16 pair kernels.
+// RMAV_PAIR_DR: the pair bodies compile the redraw of a ranged handle's constants (rmav_set_env_param_range; the flag's uses are in the
+// fragments both include, rmav_pair_env_load.inc and rmav_pair_episode.inc) only where a *_dr wrapper sets it around its #include.  Not a
+// constexpr flag like TL / BOOT / NORM: even a dead local declaration in the bodies changed the register allocation of the bf16 pair kernels.
 #define RMAV_PAIR_DR 0
 
 namespace rmav {

@@ -4,7 +4,8 @@
 // stream (tools/isa_compare.py, profiles/r07/time_limit.md).  In scope: template parameters K, MODE, ST, FIXED, the constexpr
 // bool TL (the launch has an episode time limit), the constexpr bool BOOT (it also leaves the bootstrap term of truncated steps:
 // k_rollout_boot), the constexpr bool NORM (the nets take normalised observations: k_rollout_nrm - the kernels that also apply the
-// handle's action rule `ar`, ActRuleArgs) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm, ar.
+// handle's action rule `ar`, ActRuleArgs) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm, ar.  The same idiom one level
+// down: the auto-reset of the step loop is the fragment rmav_rollout_reset.inc, included behind each form of the episode bookkeeping.
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     constexpr int AUX = StoreAux<ST>::value;
     // ACT_RANDOM_SPLIT: 128-thread workgroups, both wavefronts address the same 64 envs
@@ -769,9 +770,10 @@
             // step in which no lane of the wavefront finishes (every step of a hovering rollout) skips the ~25 predicated
             // instructions of the episode hand-off and the reset copy: 65 536 envs, controller-driven, same box, quadrotor3d
             // 47.4 -> 45.8 us, quadrotor2d 34.8 -> 31.2, quadrotor3d-slungload 71.5 -> 66.3.  Under random actions most wavefronts
-            // have a finishing lane in most steps and the extra branch costs 1-3 %, so there the block stays predicated.  (Two
-            // copies of the same statements rather than shared lambdas: the register allocation of the 1024-thread kernels
-            // is tight enough to spill with the latter - tests/test_resource_usage.py.)
+            // have a finishing lane in most steps and the extra branch costs 1-3 %, so there the block stays predicated.  The
+            // bookkeeping of the two forms differs on purpose and is written out in each; the reset behind it is the same statements
+            // and is ONE fragment, rmav_rollout_reset.inc, included in both places.  (Shared as text rather than as a lambda: the register
+            // allocation of the 1024-thread kernels is tight enough to spill with the latter - tests/test_resource_usage.py.)
             constexpr bool SKIP_QUIET = MODE == ACT_CONTROLLER || MODE == ACT_CONTROLLER_SPLIT || is_buffer(MODE) || MODE == ACT_BUFFER_SPLIT;
             if constexpr (SKIP_QUIET) {
                 if (track) {
@@ -797,32 +799,7 @@
                         er = 0.0f;
                         el = 0;
                     }
-                    if (K != REINMAV && auto_reset) {
-                        const bool rst = done;
-                        if (__ballot(rst && !have_spare) != 0) {
-                            if (!have_spare) {
-                                float sp[NS];
-                                reset_state<K>(a.seed, env_id, rc, sp);
-#pragma unroll
-                                for (int c = 0; c < NS; ++c) {
-                                    if constexpr (SPARE_LDS) lds_spare[c * 64] = sp[c];
-                                    else spare[c] = sp[c];
-                                }
-                                if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);
-                                have_spare = true;
-                            }
-                        }
-                        if (rst) {
-#pragma unroll
-                            for (int c = 0; c < NS; ++c) {
-                                if constexpr (SPARE_LDS) s[c] = lds_spare[c * 64];
-                                else s[c] = spare[c];
-                            }
-                            if constexpr (DR) range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl, pcl);   // the new episode's constants, re-derived and stored
-                            have_spare = false;
-                            rc += 1;
-                        }
-                    }
+#include "rmav_rollout_reset.inc"
                 }
             } else {
                 if (track) {
@@ -843,32 +820,7 @@
                     el += 1;
                     if (done) el = 0;
                 }
-                if (K != REINMAV && auto_reset) {
-                    const bool rst = done;
-                    if (__ballot(rst && !have_spare) != 0) {
-                        if (!have_spare) {
-                            float sp[NS];
-                            reset_state<K>(a.seed, env_id, rc, sp);
-#pragma unroll
-                            for (int c = 0; c < NS; ++c) {
-                                if constexpr (SPARE_LDS) lds_spare[c * 64] = sp[c];
-                                else spare[c] = sp[c];
-                            }
-                            if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);
-                            have_spare = true;
-                        }
-                    }
-                    if (rst) {
-#pragma unroll
-                        for (int c = 0; c < NS; ++c) {
-                            if constexpr (SPARE_LDS) s[c] = lds_spare[c * 64];
-                            else s[c] = spare[c];
-                        }
-                        if constexpr (DR) range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl, pcl);   // the new episode's constants, re-derived and stored
-                        have_spare = false;
-                        rc += 1;
-                    }
-                }
+#include "rmav_rollout_reset.inc"
             }
             if constexpr (SPLIT) {
                 // hand obs / reward / done (and the controller's action) to the memory wavefront; it drains this

@@ -1,0 +1,34 @@
+// rmav_rollout_reset.inc - the auto-reset of rmav_rollout_body.inc: draw a spare reset state if a finishing lane has none, copy it,
+// re-derive a ranged handle's constants.  Included twice, behind each of the two forms of the episode bookkeeping (SKIP_QUIET and
+// predicated: see the comment above them) - the same statements, so a field added to the reset goes here once.
+//   expects:  K, NS, the constexpr bools SPARE_LDS and DR, the kernel arguments a, pc_shared and - DR - dr; done (after the time limit),
+//             auto_reset, env_id, li, off; the spare state in spare[] or - SPARE_LDS - behind lds_spare (this lane's words only)
+//   defines:  nothing that outlives it
+//   modifies: s, have_spare, rc, the spare state and - DR - spare_pe, pl, pcl, the handle's per-env arrays a.pe
+//   barriers: none (the LDS spare is read back by the lane that wrote it)
+                if (K != REINMAV && auto_reset) {
+                    const bool rst = done;
+                    if (__ballot(rst && !have_spare) != 0) {
+                        if (!have_spare) {
+                            float sp[NS];
+                            reset_state<K>(a.seed, env_id, rc, sp);
+#pragma unroll
+                            for (int c = 0; c < NS; ++c) {
+                                if constexpr (SPARE_LDS) lds_spare[c * 64] = sp[c];
+                                else spare[c] = sp[c];
+                            }
+                            if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);
+                            have_spare = true;
+                        }
+                    }
+                    if (rst) {
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) {
+                            if constexpr (SPARE_LDS) s[c] = lds_spare[c * 64];
+                            else s[c] = spare[c];
+                        }
+                        if constexpr (DR) range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl, pcl);   // the new episode's constants, re-derived and stored
+                        have_spare = false;
+                        rc += 1;
+                    }
+                }

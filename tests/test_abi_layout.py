@@ -42,6 +42,24 @@ def test_every_header_is_implemented_by_its_own_source():
             assert defined[source].count(n) == 1, n
 
 
+def test_every_fragment_resolves_and_is_shared():
+    """The kernel bodies are shared as text: every #include "….inc" names a file of csrc/, and a fragment that another
+    .inc includes has at least two users - one with a single user shares nothing and belongs back in the file that includes it."""
+    users = {}
+    sources = sorted(p for p in glob.glob(os.path.join(CSRC, "*")) if p.endswith((".hip", ".hpp", ".inc")))
+    for p in sources:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+\.inc)"', _code(p), flags=re.M):
+            assert os.path.isfile(os.path.join(CSRC, inc)), f"{os.path.basename(p)} includes {inc}, which is not in csrc/"
+            users.setdefault(inc, []).append(os.path.basename(p))
+    assert users, "no .inc is included at all: the pattern above no longer matches the sources"
+    on_disk = sorted(os.path.basename(p) for p in sources if p.endswith(".inc"))
+    assert sorted(users) == on_disk, f"never included: {sorted(set(on_disk) - set(users))}"
+    nested = {inc: who for inc, who in users.items() if any(w.endswith(".inc") for w in who)}
+    assert nested, "the pair bodies and the one-wavefront body share their common statements as nested fragments"
+    for inc, who in sorted(nested.items()):
+        assert len(who) >= 2, f"{inc} is included once, from {who[0]}: inline it back"
+
+
 def test_no_undeclared_entry_point():
     declared = set().union(*(_declared(h) for h in PAIRS))
     for p in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
