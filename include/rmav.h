@@ -352,6 +352,38 @@ int rmav_get_time_limit(rmav_handle h, int32_t *out);
  * the handle first had a limit (written at every episode end of a time-limited handle, tracked or not). */
 int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem);
 
+/* ---- frame skip: hold each action for k dynamics steps ---------------------------------------------------------------------------
+ * With k > 1 one AGENT step of an env is up to k ordinary steps of its dynamics (each the same step, reward and steps_beyond_done
+ * machine as without a skip) under one action, evaluated once and held; the first termination ends the agent step:
+ *     u = the action (for policy rollouts, after the action rule's clip); evaluated ONCE and held
+ *     for j = 0 .. k-1:
+ *         (s, dist, term) = step(s, u)
+ *         r_j = -dist;  if term: r_j = (sbd < 0) ? 1 : 0;  sbd = (sbd < 0) ? 0 : sbd + 1
+ *         R = (j == 0) ? r_0 : R + r_j          -- fp32 add, uncontracted, in this order (R = r_0, not 0 + r_0: a -0.0f keeps its sign)
+ *         if term: break
+ *     obs = s, reward = R, done = term
+ * Everything above the dynamics counts agent steps:
+ *   - the step counter t (rmav_get_step_count) advances by 1 per agent step; the random-action and policy-noise streams draw once per
+ *     agent step; last_length, length_sum, running lengths and the time limit H are in agent steps;
+ *   - truncation is tested once, after the loop (termination wins); the running return adds R;
+ *   - the auto-reset, and the redraw of a ranged handle's constants, happen once, after the agent step: the old episode's constants
+ *     hold for all of its sub-steps.  Without RMAV_F_AUTO_RESET a finished env executes one sub-step per agent step (it terminates at
+ *     once; sbd advances by 1);
+ *   - rmav_step_final reports the state after the last executed sub-step; rmav_rollout_policy_boot / _norm leave V of that state in
+ *     boot_out where the agent step was truncated; value_out[t] / logp_out[t] belong to the agent step: the actor runs once per agent step;
+ *   - RMAV_ACT_CONTROLLER and rmav_control_step evaluate control() once per agent step and hold it (zero-order hold);
+ *     rmav_step_control returns RMAV_ERR_INVALID on such a handle (call rmav_control and rmav_step).
+ * Launches of such a handle run kernels of their own: fused rollouts use the one-wavefront kernels, as for a
+ * ranged handle (the split, slice, step-lazy and step-store tuning keys do not apply; a chunk-major call is one launch per chunk;
+ * fused = 0 gives the bits of fused = 1; results never depend on the store policy); rmav_rollout_policy / _boot / _norm accept
+ * RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA and RMAV_POLICY_F16_SHARED (the others return RMAV_ERR_INVALID).
+ * The setting is host state only: no launch, no synchronisation.  k is a kernel argument, so a captured graph keeps the value it was
+ * captured with.  A handle with k = 1 - also one set back to 1 - launches exactly the kernels it launched before.  Quadrotor kinds
+ * only (RMAV_REINMAV already sub-steps: RMAV_ERR_INVALID for k > 1).  Callers detect the feature by the symbols; RMAV_VERSION is
+ * unchanged. */
+int rmav_set_frame_skip(rmav_handle h, int32_t k);   /* k in [1, 1024]; 1 = none, the default */
+int rmav_get_frame_skip(rmav_handle h, int32_t *out);
+
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that
  * bootstraps a truncated episode (target r + gamma V(s_final): a truncated episode is not a failure) needs the state the dynamics

@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->frame_skip > 1) {   // a handle with a frame skip: k_rollout_fs, which takes the range and the time limit as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_skip_rollout(h, MODE, ST, a)) return rc;
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no frame-skip kernel for action mode %d", MODE);
+        }
     } else if (h->range_mask) {   // a handle with a parameter range: k_rollout_dr, with or without a time limit (launch_rollout_km routes it here)
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_ranged_rollout(h, MODE, ST, a)) return rc;
@@ -321,7 +327,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
     // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
     // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask)) {
+    // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -396,7 +403,9 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->range_mask) {   // a handle with a parameter range: k_step_dr for every batch size (eager record load, default store policy)
+    if (h->frame_skip > 1) {   // a handle with a frame skip: k_step_fs for every batch size (rollout_impl has refused the control() form)
+        if (int rc = rmav_launch_skip_step(h, a, bs, FinalArgs{})) return rc;
+    } else if (h->range_mask) {   // a handle with a parameter range: k_step_dr for every batch size (eager record load, default store policy)
         if (int rc = rmav_launch_ranged_step(h, a, ctrl, bs, FinalArgs{})) return rc;
     } else if (h->time_limit > 0) {   // every batch size: the eager record load, k_step's preloaded arguments (k_step_tl)
         const TimeLimitArgs tl = tl_args(h);
@@ -427,7 +436,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->range_mask) {
+    if (h->frame_skip > 1) {
+        if (int rc = rmav_launch_skip_step(h, a, bs, fa)) return rc;
+    } else if (h->range_mask) {
         if (int rc = rmav_launch_ranged_step(h, a, false, bs, fa)) return rc;
     } else dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(step_store(h), [&](auto s) {
         constexpr int ST = decltype(s)::value;
@@ -631,6 +642,8 @@ void free_all(rmav_handle h) {
 
 }  // namespace
 
+int ensure_range_dev(rmav_handle h) { return h->range_dev ? (int)RMAV_OK : sync_range_dev(h); }
+
 // =================================================================================================
 extern "C" {
 
@@ -749,6 +762,7 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
     for (int i = 0; i < RMAV_TUNE_COUNT; ++i) h->tune[i] = -1;
     h->rule_lo = -__builtin_inff();   // the identity action rule (rmav_set_policy_action_rule)
     h->rule_hi = __builtin_inff();
+    h->frame_skip = 1;
     if (adopt_stream(h, hip_stream)) {
         (void)hipGetLastError();
         free_all(h);
@@ -997,6 +1011,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
         return rmav_fail(RMAV_ERR_INVALID, "RMAV_ACT_BUFFER needs actions_in");
     if (ctrl_out && h->kind == RMAV_REINMAV)
         return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv's controller runs inside its step (the controller action mode); there is no separate control()");
+    if (ctrl_out && h->frame_skip > 1)
+        return rmav_fail(RMAV_ERR_INVALID, "rmav_step_control has no frame-skip kernel: call rmav_control and rmav_step on a handle with a frame skip");
     const size_t n = pitch ? (size_t)pitch : (size_t)h->n, T = (size_t)n_steps;   // (the trajectory arrays' column pitch)
     const size_t nS = kStateDim[h->kind], nA = kActionDim[h->kind];
     const size_t b_act = T * nA * n * sizeof(float), b_obs = T * nS * n * sizeof(float);
@@ -1345,6 +1361,24 @@ int rmav_episode_buffers(rmav_handle h, float *last_return, int32_t *last_length
             if (int rc = copy_out(h, (const int32_t *)dst, cur_length, n, RMAV_HOST)) return rc;
     }
     if (mem == RMAV_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
+    return RMAV_OK;
+}
+
+// Frame skip: handle state, host only.  Every stepping launch reads it (launch_rollout_kms, launch_step_k, launch_step_final_k;
+// rmav_policy_abi.hip) and passes it to its kernel as an argument.
+int rmav_set_frame_skip(rmav_handle h, int32_t k) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (k < 1 || k > 1024) return rmav_fail(RMAV_ERR_INVALID, "the frame skip must be in [1, 1024] (1 = none), got %d", (int)k);
+    if (h->kind == RMAV_REINMAV && k > 1)
+        return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv sub-steps inside its own step: it takes no frame skip");
+    h->frame_skip = k;
+    return RMAV_OK;
+}
+
+int rmav_get_frame_skip(rmav_handle h, int32_t *out) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
+    *out = h->frame_skip;
     return RMAV_OK;
 }
 

@@ -1,7 +1,7 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus two that only launch kernels (rmav_policy_abi.hip,
-// rmav_range_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus three that only launch kernels (rmav_policy_abi.hip,
+// rmav_range_abi.hip, rmav_skip_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -100,9 +100,17 @@ struct rmav_env_s {
     // routes rmav_rollout_policy / _boot / _norm as a parameter range does - to the normalised kernels, which take it (ActRuleArgs)
     int32_t rule_det;
     float rule_lo, rule_hi;
+    // frame skip (rmav_set_frame_skip): dynamics sub-steps per agent step, 1 = none (rmav_create).  > 1 routes every stepping launch to the
+    // *_fs kernels - before the range and the time limit, which those kernels take as well
+    int32_t frame_skip;
 };
+inline rmav::FrameSkipArgs skip_args(const rmav_env_s *h) { return rmav::FrameSkipArgs{h->frame_skip}; }
 inline bool has_act_rule(const rmav_env_s *h) { return h->rule_det != 0 || h->rule_lo != -__builtin_inff() || h->rule_hi != __builtin_inff(); }
 inline rmav::ActRuleArgs act_rule_args(const rmav_env_s *h) { return rmav::ActRuleArgs{h->rule_det ? 0.0f : 1.0f, h->rule_lo, h->rule_hi}; }
+inline rmav::PolicySkipArgs policy_skip_args(const rmav_env_s *h) {
+    const rmav::ActRuleArgs r = act_rule_args(h);
+    return rmav::PolicySkipArgs{r.noise, r.lo, r.hi, h->frame_skip};
+}
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
 inline rmav::RangeArgs range_args(const rmav_env_s *h, uint32_t mask) {
@@ -144,6 +152,8 @@ RMAV_INTERNAL rmav::RolloutArgs base_args(rmav_handle h);
 RMAV_INTERNAL int ensure_scratch(rmav_handle h, size_t bytes);
 RMAV_INTERNAL int ensure_ident_norm(rmav_handle h);
 RMAV_INTERNAL int ensure_boot_scratch(rmav_handle h, size_t bytes);
+// ... and the device copy of the handle's ranges on first use (the kernels that take the range by pointer: k_rollout_nrm_dr / _fs)
+RMAV_INTERNAL int ensure_range_dev(rmav_handle h);
 
 constexpr int kExchangeDepth = 8;   // buffer pairs of the overlapped statistics exchange
 // bounds of k_wait_arrivals, in ticks of the 100 MHz wall clock: 2 s once the armed launch has begun, 10 min overall
@@ -285,3 +295,9 @@ RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rma
 // fa = what rmav_step_final wants (NULL pointers otherwise).  The caller checks hipGetLastError.
 RMAV_INTERNAL int rmav_launch_ranged_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
 RMAV_INTERNAL int rmav_launch_ranged_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
+
+// rmav_skip_abi.hip: the launches of a handle with a frame skip (rmav_set_frame_skip), shaped as the ranged ones.  _rollout: ONE launch of
+// k_rollout_fs<K, mode, st, time limit?> over the envs a names; _step: k_step_fs at bs threads per workgroup (there is no form that
+// ends with control()).  Both take the handle's range (mask = 0 without one).  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_skip_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_skip_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);

@@ -312,6 +312,22 @@ struct ActRuleArgs {
 };
 __device__ __forceinline__ float act_clip(const ActRuleArgs &ar, float a) { return __builtin_amdgcn_fmed3f(a, ar.lo, ar.hi); }
 
+// Frame skip (rmav_set_frame_skip; the *_fs kernels), trailing as well: the action of an agent step is evaluated once and held for up to
+// k dynamics sub-steps - each an ordinary Env<K>::step with the reward / steps_beyond_done machine behind it - and the first termination
+// ends the agent step.  The agent step's reward is R = r_0, then R + r_j in sub-step order (fp32, uncontracted; r_0 keeps its sign bit);
+// everything behind the loop - time limit, episode bookkeeping, auto-reset, the stores - sees (state, R, terminated) once, as after one
+// step.  The loop is rolled: ONE call site of Env<K>::step under the lane's `live` predicate, left when no lane is live or j reaches k.
+//   k   sub-steps per agent step, 2 .. 1024 (a handle with k = 1 launches the kernels without the loop)
+struct FrameSkipArgs {
+    int32_t k;
+};
+// ... and what the frame-skip POLICY kernels take in its place: the bound with the handle's action rule (ActRuleArgs' three values), as ONE
+// trailing argument - these kernels sit at their scalar-register limit, and the rule and the bound are read together, once per launch
+struct PolicySkipArgs {
+    float noise, lo, hi;
+    int32_t k;
+};
+
 __device__ __forceinline__ uint32_t ep_clock0(const RolloutArgs &a) { return (uint32_t)a.t0; }
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
@@ -438,7 +454,8 @@ __device__ __forceinline__ void wide_cols(const float *tile, rsrc_t r, uint32_t 
 template <int K, int MODE, int ST = ST_DEFAULT, bool FIXED = false>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                     const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false, DR = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, DR = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const TimeLimitArgs tl{};
@@ -452,7 +469,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false;
+    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
@@ -466,7 +484,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                          const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
-    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false;
+    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const NormArgs nm{};
@@ -487,7 +506,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     // scalar registers) wherever the argument was placed (profiles/r09/obs_norm.md).
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RangeArgs dr{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
@@ -498,7 +518,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr) {
-    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -518,7 +539,39 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     const RangeArgs &dr = *drp;
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#include "rmav_rollout_body.inc"
+}
+
+// The one-wavefront kernels of a handle with a frame skip (rmav_set_frame_skip): k_rollout_dr - the most general body: a handle without
+// a range passes mask = 0 - whose step loop holds each action for up to fs.k sub-steps (FrameSkipArgs).  Symbols of their own: the kernels
+// above keep their instruction streams.
+template <int K, int MODE, int ST, bool TL>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_fs(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs) {
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "frame-skip launches run the one-wavefront kernels");
+#include "rmav_rollout_body.inc"
+}
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_dr with the sub-step loop, for rmav_rollout_policy, _boot and _norm
+// alike (identity tables, a range with mask = 0 and a scratch boot_out where the call or the handle has none).  The actor runs once per
+// agent step; the action rule's clip is applied once, in front of the loop.
+template <int K, bool BOOT>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_fs(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicySkipArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
 }
@@ -593,10 +646,12 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // TL: the launch has an episode time limit (tl; k_step_tl) - with the eager record load only: every lane needs ep_start every step.
 // FIN: the launch also reports what the auto-reset destroys (fa; k_step_final).
 // DR: the handle has a parameter range (dr; k_step_dr): a finishing lane draws and stores the constants of its new episode.
-template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false>
+template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
-                                          const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{}) {
+                                          const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
+                                          [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}) {
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
+    static_assert(!(FS && LAZY), "the frame-skip loop runs the reward machine per sub-step: every lane's record, eagerly");
     static_assert(!(TL && LAZY), "a time limit needs every lane's episode start");
     constexpr int NS = Dims<K>::NS, NA = Dims<K>::NA;
     constexpr int AUX = StoreAux<ST>::value;   // cache policy of the per-env stores (RMAV_TUNE_STEP_STORE; measured in profiles/r04/step_store_policy.md)
@@ -681,7 +736,30 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
 
     float dist = 0.0f;
     bool done;
-    Env<K>::step(s, act, pl, dist, done);
+    // FS (k_step_fs): the action is held for up to fs.k sub-steps; the reward machine runs behind each, r accumulates in sub-step order
+    [[maybe_unused]] float r_fs = 0.0f;
+    if constexpr (FS) {
+        bool live = true;
+        done = false;
+        int32_t j = 0;
+        do {
+            if (live) {
+                bool term;
+                Env<K>::step(s, act, pl, dist, term);
+                float rj = -dist;
+                if (term) {
+                    rj = (sb < 0) ? 1.0f : 0.0f;
+                    sb = (sb < 0) ? 0 : sb + 1;
+                }
+                r_fs = (j == 0) ? rj : r_fs + rj;
+                done = term;
+                live = !term;
+            }
+            ++j;
+        } while (j < fs.k && __ballot(live) != 0);
+    } else {
+        Env<K>::step(s, act, pl, dist, done);
+    }
     // Where and how the step's outputs are stored (same values on both paths): reward, done, running return
     auto store_scalars = [&](float r_, bool done_, float er_) {
         if (a.rew_out) buf_st_aux<AUX>(make_rsrc(a.rew_out), off, 0, r_);
@@ -721,7 +799,9 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     }
     // reward / steps_beyond_done machine  (quadrotor3d.py:112-122 and siblings)
     float r = -dist;
-    if (done) {
+    if constexpr (FS) {
+        r = r_fs;   // (the machine ran inside the loop)
+    } else if (done) {
         r = (sb < 0) ? 1.0f : 0.0f;
         sb = (sb < 0) ? 0 : sb + 1;
     }
@@ -902,6 +982,26 @@ __global__ __launch_bounds__(kBlock) void k_step_dr(float *state_pl, int64_t n_p
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, CTRL, false, ST_DEFAULT, TL, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr);
+}
+
+// The single-step kernel of a handle with a frame skip (rmav_set_frame_skip), for every batch size: k_step_dr's body and argument list -
+// a handle without a range passes mask = 0, one without a limit TL = false, a call that wants neither of fa's outputs NULL pointers -
+// with the sub-step loop, whose bound trails.  No CTRL form: control() is evaluated per agent step by rmav_control (rmav_step_control
+// refuses such a handle).
+template <int K, bool TL>
+__global__ __launch_bounds__(kBlock) void k_step_fs(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs);
 }
 
 // reset() of every env

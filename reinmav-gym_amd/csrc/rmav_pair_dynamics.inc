@@ -1,6 +1,6 @@
 // rmav_pair_dynamics.inc - one env-step of the stepping wavefront once its action is known: the dynamics, the reward /
 // steps_beyond_done machine and the head of the time limit, in the step loop of both pair bodies.
-//   expects:  K, NA, the constexpr bools TL and NORM, the kernel arguments ar (ActRuleArgs) and - TL - tl (TimeLimitArgs); act[NA] (the
+//   expects:  K, NA, the constexpr bools TL, NORM and FS, the kernel arguments ar (ActRuleArgs), - FS - fs (FrameSkipArgs) and - TL - tl (TimeLimitArgs); act[NA] (the
 //             action the policy drew), p, li, el
 //   defines:  dist, r (the step's reward), done (terminated or - TL - truncated)
 //   modifies: s (the state after the step), tenv (REINMAV), sb; stores one byte of tl.last_trunc where an episode ends (TL)
@@ -17,6 +17,32 @@
             done = true;   // reinmav_env.py:110
             r = 90.0f;     // reinmav_env.py:111-116
         } else {
+            if constexpr (FS) {
+                // frame skip (FrameSkipArgs, see k_rollout_fs): the clipped action is held for up to fs.k sub-steps, the reward machine runs
+                // behind each; closed HERE, in front of the time limit - between the same two barriers as the single step
+                float ca[NA];
+#pragma unroll
+                for (int c = 0; c < NA; ++c) ca[c] = NORM ? act_clip(ar, act[c]) : act[c];
+                bool live = true;
+                done = false;
+                r = 0.0f;
+                int32_t j = 0;
+                do {
+                    if (live) {
+                        bool term;
+                        Env<K>::step(s, ca, p, dist, term);
+                        float rj = -dist;
+                        if (term) {
+                            rj = (sb < 0) ? 1.0f : 0.0f;
+                            sb = (sb < 0) ? 0 : sb + 1;
+                        }
+                        r = (j == 0) ? rj : r + rj;
+                        done = term;
+                        live = !term;
+                    }
+                    ++j;
+                } while (j < fs.k && __ballot(live) != 0);
+            } else {
             if constexpr (NORM) {   // the action rule: the dynamics take the clipped action, the stored one stays what the policy drew
                 float ca[NA];
 #pragma unroll
@@ -29,6 +55,7 @@
             if (done) {
                 r = (sb < 0) ? 1.0f : 0.0f;
                 sb = (sb < 0) ? 0 : sb + 1;
+            }
             }
         }
         // time limit (see k_rollout): after the reward / steps_beyond_done machine, before the episode hand-off

@@ -32,7 +32,7 @@ inline BootArgs variant_boot(rmav_handle h, const BootArgs *bt) { return (h->tim
 constexpr size_t kNormBytes = sizeof(float) * kNormWords;   // the *_nrm kernels' tables, in LDS behind the weights
 
 // ---- the three actor families -------------------------------------------------------------------------------------------------------
-// A family names its kernels once - plain(), tl(), boot(), nrm<BOOT>, dr<BOOT>: the seven slots (the last four take the handle's
+// A family names its kernels once - plain(), tl(), boot(), nrm<BOOT>, dr<BOOT>, fs<BOOT>: the nine slots (the last six take the handle's
 // action rule, act_rule_args: the identity unless rmav_set_policy_action_rule said otherwise) - and says what differs between the
 // families around them: envs behind one arrival word, the workgroup (pairs sharing one LDS copy of the weights, envs, threads), the LDS
 // bytes, and how the *_nrm / *_dr kernels take the tables and the range.  kVariants = false: the plain kernel is the only one.
@@ -67,6 +67,9 @@ template <int KIND, int MODE> struct OneWave {
     template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) {
         v.a.act_in = v.nm->tab, go(k_rollout_nrm_dr<K, BOOT>, v.tl, v.b, (const RangeArgs *)v.h->range_dev, act_rule_args(v.h));
     }
+    template <bool BOOT, typename Go> static void fs(Go go, const VariantArgs &v) {
+        v.a.act_in = v.nm->tab, go(k_rollout_nrm_fs<K, BOOT>, v.tl, v.b, (const RangeArgs *)v.h->range_dev, policy_skip_args(v.h));
+    }
 };
 
 // The matrix-core actors as (actor, critic) wavefront pairs (rmav_policy_pair.hpp).  Pairs per workgroup: the pairs of a
@@ -93,6 +96,7 @@ template <int KIND, int FMT> struct Pair {   // (time-limited handles: RMAV_POLI
     static auto boot() { return k_rollout_pair_boot<K, FMT>; }
     template <bool BOOT, typename Go> static void nrm(Go go, const VariantArgs &v) { go(k_rollout_pair_nrm<K, BOOT>, v.tl, v.b, *v.nm, act_rule_args(v.h)); }
     template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) { go(k_rollout_pair_dr<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), act_rule_args(v.h)); }
+    template <bool BOOT, typename Go> static void fs(Go go, const VariantArgs &v) { go(k_rollout_pair_fs<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), policy_skip_args(v.h)); }
 };
 
 // RMAV_POLICY_F16_SHARED: one trunk, both wavefronts of a pair evaluate it for one 32-env column tile each (k_rollout_pair_shared)
@@ -107,6 +111,7 @@ template <int KIND> struct SharedPair {
     static auto boot() { return k_rollout_pair_shared_boot<K>; }
     template <bool BOOT, typename Go> static void nrm(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_nrm<K, BOOT>, v.tl, v.b, *v.nm, act_rule_args(v.h)); }
     template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_dr<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), act_rule_args(v.h)); }
+    template <bool BOOT, typename Go> static void fs(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_fs<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), policy_skip_args(v.h)); }
 };
 
 // ---- the one ladder: which of family F's kernels this launch runs, with which LDS size and trailing arguments ---------------------------
@@ -127,7 +132,11 @@ template <typename F> int launch_family(rmav_handle h, const RolloutArgs &a_in, 
         v = policy_variant(h, bt, nm);
         const VariantArgs va{h, a, variant_tl(h), variant_boot(h, bt), nm};
         // a handle with a parameter range: the ranged *_nrm kernels (rmav_ppo_abi.hip hands every such call statistics and, with a limit, a boot_out)
-        if (h->range_mask && v == V_NRM) F::template dr<false>(go(false), va);
+        // a handle with a frame skip first: the *_fs kernels take the range (mask = 0 without one) and the rule as well
+        if (h->frame_skip > 1 && v == V_NRM) F::template fs<false>(go(false), va);
+        else if (h->frame_skip > 1 && v == V_NRM_BOOT) F::template fs<true>(go(true), va);
+        else if (h->frame_skip > 1) return rmav_fail(RMAV_ERR_INVALID, "a handle with a frame skip runs the normalised kernels");
+        else if (h->range_mask && v == V_NRM) F::template dr<false>(go(false), va);
         else if (h->range_mask && v == V_NRM_BOOT) F::template dr<true>(go(true), va);
         else if (h->range_mask) return rmav_fail(RMAV_ERR_INVALID, "a ranged handle runs the normalised kernels");
         else if (has_act_rule(h) && v != V_NRM && v != V_NRM_BOOT) return rmav_fail(RMAV_ERR_INVALID, "a handle with a policy action rule runs the normalised kernels");
@@ -142,8 +151,8 @@ template <typename F> int launch_family(rmav_handle h, const RolloutArgs &a_in, 
 
 template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs *nm) {
     // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
-    if ((nm || h->range_mask || has_act_rule(h)) && (K == REINMAV || !policy_has_variants(kmode)))
-        return rmav_fail(RMAV_ERR_INVALID, "no %s kernel for policy mode %d", nm ? "normalised" : h->range_mask ? "ranged" : "action-rule", kmode);
+    if ((nm || h->range_mask || has_act_rule(h) || h->frame_skip > 1) && (K == REINMAV || !policy_has_variants(kmode)))
+        return rmav_fail(RMAV_ERR_INVALID, "no %s kernel for policy mode %d", nm ? "normalised" : h->range_mask ? "ranged" : h->frame_skip > 1 ? "frame-skip" : "action-rule", kmode);
     switch (kmode) {
     case RMAV_ACT_POLICY: return launch_family<OneWave<K, ACT_POLICY>>(h, a, nullptr, nullptr);
     case RMAV_ACT_POLICY_BF16:

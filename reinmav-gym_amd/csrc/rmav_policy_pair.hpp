@@ -236,7 +236,8 @@ __device__ __forceinline__ void state_frags(const float (&x)[16], typename PairO
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                           const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -247,7 +248,8 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const R
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, BOOT = false, NORM = false;
+    constexpr bool TL = true, BOOT = false, NORM = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
@@ -259,7 +261,8 @@ template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                const BootArgs bt) {
-    constexpr bool TL = true, BOOT = true, NORM = false;
+    constexpr bool TL = true, BOOT = true, NORM = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV && FMT == FMT_F16, "the (actor, critic) pair of time-limited handles");
@@ -273,7 +276,8 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_nrm(con
                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                               const BootArgs bt, const NormArgs nm, const ActRuleArgs ar) {
     constexpr int FMT = FMT_F16;
-    constexpr bool TL = BOOT, NORM = true;
+    constexpr bool TL = BOOT, NORM = true, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_body.inc"
 }
@@ -284,7 +288,26 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_dr(cons
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                              const BootArgs bt, const NormArgs nm, const RangeArgs dr, const ActRuleArgs ar) {
     constexpr int FMT = FMT_F16;
-    constexpr bool TL = BOOT, NORM = true;
+    constexpr bool TL = BOOT, NORM = true, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with a frame skip (rmav_set_frame_skip; FrameSkipArgs in rmav_kernels.hpp): k_rollout_pair_dr - the most general body: a
+// handle without a range passes mask = 0, a call without statistics the identity tables - whose actor wavefront holds each action for
+// up to fs.k sub-steps between the same two barriers.
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_fs(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicySkipArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1
@@ -403,7 +426,8 @@ __device__ __forceinline__ void shared_boot_tile1(const float *tile, int half, c
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                  const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -413,7 +437,8 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, BOOT = false, NORM = false;
+    constexpr bool TL = true, BOOT = false, NORM = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
@@ -424,7 +449,8 @@ template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                       const BootArgs bt) {
-    constexpr bool TL = true, BOOT = true, NORM = false;
+    constexpr bool TL = true, BOOT = true, NORM = false, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
@@ -435,7 +461,8 @@ template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                      const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                      const BootArgs bt, const NormArgs nm, const ActRuleArgs ar) {
-    constexpr bool TL = BOOT, NORM = true;
+    constexpr bool TL = BOOT, NORM = true, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_shared_body.inc"
 }
@@ -444,7 +471,23 @@ template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                     const BootArgs bt, const NormArgs nm, const RangeArgs dr, const ActRuleArgs ar) {
-    constexpr bool TL = BOOT, NORM = true;
+    constexpr bool TL = BOOT, NORM = true, FS = false;
+    [[maybe_unused]] const FrameSkipArgs fs{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with a frame skip: k_rollout_pair_shared_dr with the sub-step loop (see k_rollout_pair_fs).
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_fs(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                                    const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicySkipArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1

@@ -2,7 +2,7 @@
 // Textually, not as a shared __device__ function: the optimiser simplifies such a function on its own - with `a` an opaque pointer
 // rather than the kernel's constant argument block - before inlining it, and the kernels came out with a different instruction
 // stream (tools/isa_compare.py, profiles/r07/time_limit.md).  In scope: template parameters K, MODE, ST, FIXED, the constexpr
-// bool TL (the launch has an episode time limit), the constexpr bool BOOT (it also leaves the bootstrap term of truncated steps:
+// bool TL (the launch has an episode time limit), the constexpr bool FS (k_rollout_fs: each action is held for up to fs.k sub-steps), the constexpr bool BOOT (it also leaves the bootstrap term of truncated steps:
 // k_rollout_boot), the constexpr bool NORM (the nets take normalised observations: k_rollout_nrm - the kernels that also apply the
 // handle's action rule `ar`, ActRuleArgs) and the kernel arguments a, p_shared, pc_shared, tl, bt, nm, ar.  The same idiom one level
 // down: the auto-reset of the step loop is the fragment rmav_rollout_reset.inc, included behind each form of the episode bookkeeping.
@@ -698,6 +698,33 @@
                 done = true;   // reinmav_env.py:110
                 r = 90.0f;     // reinmav_env.py:111-116: 100 - 10, every step
             } else {
+                if constexpr (FS) {
+                    // frame skip (FrameSkipArgs): the action - clipped ONCE, in front of the loop - is held for up to fs.k sub-steps, each
+                    // an ordinary step with the reward / steps_beyond_done machine behind it; a lane leaves at its first termination,
+                    // the wavefront when no lane is live.  What follows sees (s, r, done) as after one step.
+                    float ca[NA];
+#pragma unroll
+                    for (int c = 0; c < NA; ++c) ca[c] = NORM ? act_clip(ar, act[c]) : act[c];
+                    bool live = true;
+                    done = false;
+                    r = 0.0f;
+                    int32_t j = 0;
+                    do {
+                        if (live) {
+                            bool term;
+                            Env<K>::step(s, ca, p, dist, term);
+                            float rj = -dist;
+                            if (term) {
+                                rj = (sb < 0) ? 1.0f : 0.0f;
+                                sb = (sb < 0) ? 0 : sb + 1;
+                            }
+                            r = (j == 0) ? rj : r + rj;
+                            done = term;
+                            live = !term;
+                        }
+                        ++j;
+                    } while (j < fs.k && __ballot(live) != 0);
+                } else {
                 if constexpr (NORM) {   // the action rule: the dynamics take the clipped action, `act` (stored below) stays what the policy drew
                     float ca[NA];
 #pragma unroll
@@ -711,6 +738,7 @@
                 if (done) {
                     r = (sb < 0) ? 1.0f : 0.0f;
                     sb = (sb < 0) ? 0 : sb + 1;
+                }
                 }
             }
             if (act_out) {

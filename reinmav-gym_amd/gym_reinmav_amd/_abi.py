@@ -135,6 +135,8 @@ PROTOTYPES = {
     "rmav_episode_buffers": (C.c_int, [C.c_void_p, _fp, _vp, _fp, _vp, C.c_int]),
     "rmav_set_time_limit": (C.c_int, [C.c_void_p, C.c_int32]),
     "rmav_get_time_limit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "rmav_set_frame_skip": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rmav_get_frame_skip": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

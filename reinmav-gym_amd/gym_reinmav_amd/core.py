@@ -57,18 +57,34 @@ def policy_action_rule(deterministic, clip, box=None):
     return int(bool(deterministic)), lo, hi
 
 
+FRAME_SKIP_MAX = 1024
+
+
+def check_frame_skip(k) -> int:
+    """``frame_skip`` as ``rmav_set_frame_skip`` takes it: an integer in ``[1, FRAME_SKIP_MAX]`` (1 = none).  Refused here, before the
+    library: bools, floats (also integral ones), strings and anything out of range."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"frame_skip must be an integer, got {k!r}")
+    if not 1 <= int(k) <= FRAME_SKIP_MAX:
+        raise ValueError(f"frame_skip must be in [1, {FRAME_SKIP_MAX}] (1 = none), got {k}")
+    return int(k)
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
     def __init__(self, kind, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
-                 randomize: Optional[dict] = None):
+                 randomize: Optional[dict] = None, frame_skip: int = 1):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
         ``randomize``: per-episode domain randomisation, ``{"mass": (lo, hi), "load_mass": ..., "tether_length": ...}``: every env
-        draws the constant anew from ``[lo, hi)`` whenever its state is reset, inside the kernels (:meth:`set_env_param_range`)."""
+        draws the constant anew from ``[lo, hi)`` whenever its state is reset, inside the kernels (:meth:`set_env_param_range`).
+
+        ``frame_skip``: dynamics steps per action (gym MuJoCo's ``frame_skip``; :attr:`frame_skip`), held inside the kernels; 1 = none."""
+        frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
@@ -93,6 +109,8 @@ class BatchedQuadrotor:
             self.max_episode_steps = max_episode_steps
         for name, (lo, hi) in (randomize or {}).items():
             self.set_env_param_range(name, lo, hi)
+        if frame_skip != 1:
+            self.frame_skip = frame_skip
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -145,6 +163,19 @@ class BatchedQuadrotor:
     @max_episode_steps.setter
     def max_episode_steps(self, h: Optional[int]):
         A.check(self._lib.rmav_set_time_limit(self._h, int(h or 0)))
+
+    @property
+    def frame_skip(self) -> int:
+        """Dynamics steps per agent step (``rmav_set_frame_skip``, include/rmav.h): every ``step`` / rollout step holds its action for
+        up to ``k`` steps of the integrator, ends at the first termination and returns the summed reward; step counters, episode
+        lengths and ``max_episode_steps`` count agent steps.  Assignable at any time (host state only); 1 = none."""
+        v = C.c_int32()
+        A.check(self._lib.rmav_get_frame_skip(self._h, C.byref(v)))
+        return v.value
+
+    @frame_skip.setter
+    def frame_skip(self, k: int):
+        A.check(self._lib.rmav_set_frame_skip(self._h, check_frame_skip(k)))
 
     def set_policy_action_rule(self, deterministic: bool = False, clip=None):
         """What the in-kernel policy rollouts (``rmav_rollout_policy`` / ``_boot`` / ``_norm``: :class:`~gym_reinmav_amd.ppo.FusedPolicyCollector`)

@@ -40,7 +40,7 @@ class NativeQuadrotorEnv(_EnvBase):
     _action_box = None    # (low, high, dtype)
     _reading_2d = None
 
-    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None):
+    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None, frame_skip: int = 1):
         kind = A.KIND_BY_NAME[self._kind]
         nS, nA = A.STATE_DIM[kind], A.ACTION_DIM[kind]
         lo, hi, dt = self._action_box
@@ -54,10 +54,12 @@ class NativeQuadrotorEnv(_EnvBase):
         # (No 'terminal_observation' here: this env never auto-resets, so the obs step() returns for a finished episode IS its
         # terminal observation - rmav_step_final / QuadrotorVecEnv(terminal_observation=True) are for the batched, auto-resetting path.)
         # randomize ({"mass": (lo, hi), ...}): the constants are drawn anew by every reset() (this env never auto-resets).
+        # frame_skip (gym.make(id, frame_skip=k)): step() holds its action for k dynamics steps inside the kernel.  rmav_step_control has
+        # no such kernel: step() is then rmav_step, and control() a launch of its own (rmav_control) on the state step() left.
         self._limited = bool(max_episode_steps)
         self._batch = BatchedQuadrotor(kind, 1, device=device, seed=self._seed_value, auto_reset=False,
                                        track_episodes=self._limited, reading_2d=self._reading_2d,
-                                       max_episode_steps=max_episode_steps, randomize=randomize)
+                                       max_episode_steps=max_episode_steps, randomize=randomize, frame_skip=frame_skip)
         self._dim = 2 if nS in (5, 9) else 3
         self._has_load = nS in (9, 16)
         # Lean per-call path: preallocated host arrays and cached ctypes pointers, so a step() is one ABI call
@@ -75,6 +77,7 @@ class NativeQuadrotorEnv(_EnvBase):
         vp = lambda x: C.c_void_p(x.ctypes.data)  # noqa: E731
         self._pa, self._po, self._pr, self._pd, self._pc = vp(self._a), vp(self._o), vp(self._r), vp(self._d), vp(self._c)
         self._step_control = self._batch._lib.rmav_step_control
+        self._step_plain = self._batch._lib.rmav_step
         self._hnd = self._batch._h
         self._ctrl_valid = False
 
@@ -98,10 +101,13 @@ class NativeQuadrotorEnv(_EnvBase):
         self._a[0, :] = action          # casts float64 -> float32, raises on a wrong length like the reference's unpacking
         if self._hnd is None:
             raise A.RmavError(A.ERR_INVALID, "step() on a closed env")
-        rc = self._step_control(self._hnd, self._pa, self._po, self._pr, self._pd, self._pc, A.HOST, A.AOS)
+        if self._batch.frame_skip > 1:
+            rc = self._step_plain(self._hnd, self._pa, self._po, self._pr, self._pd, A.HOST, A.AOS)
+        else:
+            rc = self._step_control(self._hnd, self._pa, self._po, self._pr, self._pd, self._pc, A.HOST, A.AOS)
         if rc < 0:
             A.check(rc)
-        self._ctrl_valid = True
+        self._ctrl_valid = rc == 0 and self._batch.frame_skip == 1
         done = bool(self._d[0])
         info = {}
         if done and self._limited:   # gym's TimeLimit: present (True) only when the limit ended the episode
@@ -121,6 +127,16 @@ class NativeQuadrotorEnv(_EnvBase):
         self._hnd = None                # the cached raw handle must not outlive the library's
         self._ctrl_valid = False
         self._batch.close()
+
+    @property
+    def frame_skip(self) -> int:
+        """Dynamics steps per ``step()`` (``BatchedQuadrotor.frame_skip``); assignable."""
+        return self._batch.frame_skip
+
+    @frame_skip.setter
+    def frame_skip(self, k):
+        self._ctrl_valid = False
+        self._batch.frame_skip = k
 
     # -- public attributes of the reference ---------------------------------------------------------------
     @property
