@@ -41,6 +41,10 @@ def main():
                     help="VecNormalize(ret=True) in front of GAE: rewards divided by the running std of the discounted return")
     ap.add_argument("--frame-skip", dest="frame_skip", type=int, default=1,
                     help="dynamics steps per action, held inside the kernels (gym MuJoCo's frame_skip); lengths and the time limit count actions")
+    ap.add_argument("--reward", default=None, metavar="SPEC",
+                    help="tracking reward inside the kernels in place of the reference's -|pos|, e.g. "
+                         "goal=0,0,2:alive=1:w_pos=1:w_vel=0.1:w_act=0.01:terminal=-10 (goal defaults to the controller's set-point, act_ref to "
+                         "the hover action); not with --actor bf16")
     ap.add_argument("--randomize", action="append", default=[], metavar="NAME=LO:HI",
                     help="per-episode domain randomisation inside the kernels, e.g. mass=0.8:1.2 (mass | load_mass | tether_length; "
                          "repeatable); not with --actor bf16")
@@ -72,8 +76,12 @@ def main():
         except ValueError:
             ap.error(f"--randomize wants NAME=LO:HI, got {item!r}")
         randomize[name] = (lo, hi)
+    try:
+        reward = g.TrackingReward.parse(args.reward) if args.reward is not None else None
+    except (TypeError, ValueError) as e:
+        ap.error(str(e))
     env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None,
-                             randomize=randomize or None, frame_skip=args.frame_skip)
+                             randomize=randomize or None, frame_skip=args.frame_skip, reward=reward)
     obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
     ret_norm = RunningReturnNorm(f"cuda:{env.device}") if args.normalize_reward else None   # ... and its ret=True half
     policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()
@@ -93,7 +101,7 @@ def main():
     if args.eval_every > 0:   # its own handle: the training envs' states, episode clocks and statistics are not disturbed
         eval_env = g.BatchedQuadrotor(kind, args.eval_envs, seed=args.seed, env_id_base=args.num_env,
                                       max_episode_steps=args.max_episode_steps or None, randomize=randomize or None,
-                                      frame_skip=args.frame_skip)
+                                      frame_skip=args.frame_skip, reward=reward)
     learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()

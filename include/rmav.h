@@ -384,6 +384,50 @@ int rmav_episode_truncated(rmav_handle h, uint8_t *out, int mem);
 int rmav_set_frame_skip(rmav_handle h, int32_t k);   /* k in [1, 1024]; 1 = none, the default */
 int rmav_get_frame_skip(rmav_handle h, int32_t *out);
 
+/* ---- tracking reward: goal, costs, alive bonus --------------------------------------------------------------------------------------
+ * With a spec set the reward of every ordinary dynamics step of a quadrotor handle is, in place of the reference's -|pos| / first-
+ * termination literal,
+ *     e_i = P_i - goal_i
+ *     d = root(fma(e0,e0, fma(e1,e1, e2*e2)))        (2-D kinds: root(fma(e0,e0, e1*e1)); the root() of the step norms)
+ *     v = the same expression over V
+ *     c = the same fma chain, without the root, over (u_c - act_ref_c), c = 0 .. nA-1 (the last component is the plain product)
+ *     r_live = fma(-w_act, c, fma(-w_vel, v, fma(-w_pos, d, alive)))
+ *     r = terminated ? terminal : r_live
+ * in fp32 on the STORED post-step state, uncontracted except where fma is written.  P / V are the position / velocity of the tracked
+ * body - the one whose distance the reference rewards: quadrotor2d s[0:2] / s[3:5]; quadrotor2d-slungload (the quadrotor) s[0:2] /
+ * s[3:5]; quadrotor3d s[0:3] / s[7:10]; quadrotor3d-slungload (the load) s[10:13] / s[13:16].  u is the action handed to the dynamics:
+ * for policy rollouts after the action rule's clip (the stored action stays unclipped), for the 2-D kinds before thrust_scale, for
+ * rmav_control_step and RMAV_ACT_CONTROLLER the controller's action.
+ *   - steps_beyond_done advances exactly as without a spec (it is state); `terminal` does not depend on it.  The state, done, the
+ *     truncated flags, the reset stream and the constants of a ranged handle never depend on the spec.
+ *   - everything that consumes the step's reward consumes this r: a truncated step has not terminated and gets r_live; the running
+ *     return, last_return and the episode totals add r; under frame skip r_j is this r per sub-step and R sums as the frame-skip
+ *     contract states (c is computed once per agent step: the action is held).  rmav_gae*, rmav_ret_*, rmav_normalize and the
+ *     statistics exchange read stored rewards and need no change.
+ *   - with goal = 0, alive = 0, w_pos = 1, w_vel = w_act = 0 every non-terminating step has the bits of the reference's reward.
+ * Launches of such a handle run kernels of their own, the frame-skip kernels' restrictions apply: fused rollouts
+ * use the one-wavefront kernels (the split, slice, step-lazy and step-store tuning keys do not apply; a chunk-major call is one launch
+ * per chunk; fused = 0 gives the bits of fused = 1; results never depend on the store policy); rmav_step_control is k_step's launch
+ * followed by rmav_control's (with a frame skip k > 1 it stays RMAV_ERR_INVALID); rmav_rollout_policy / _boot / _norm accept
+ * RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA and RMAV_POLICY_F16_SHARED (the others return RMAV_ERR_INVALID).
+ * Every value must be finite (RMAV_ERR_INVALID otherwise); RMAV_REINMAV takes no spec (RMAV_ERR_INVALID for a non-NULL one).  NULL
+ * switches back to the reference's reward: such a handle, like one that never set a spec, launches exactly the kernels it launched before.
+ * Ordering: rmav_set_reward is ordered on the handle's stream - launches enqueued after it see the new spec - and neither
+ * synchronises nor allocates (the device copy is part of the handle since rmav_create).  The step and one-wavefront rollout kernels take the spec by value: a captured graph keeps the values it was captured
+ * with.  The policy rollouts read the handle's device copy, which rmav_set_reward rewrites with a small launch on the stream: a
+ * captured graph reads, at replay, whatever the copy holds then (a set captured into the graph is replayed with it).
+ * rmav_get_reward: the last spec set (zeros before the first), and whether it is in force; either pointer may be NULL.
+ * Callers detect the feature by the symbols; RMAV_VERSION is unchanged. */
+typedef struct rmav_reward_spec {
+    float goal[3];      /* 2-D kinds read [0..1] */
+    float alive;        /* added on every non-terminating step */
+    float w_pos, w_vel, w_act;
+    float act_ref[4];   /* 2-action kinds read [0..1] */
+    float terminal;     /* the reward of a terminating step */
+} rmav_reward_spec;
+int rmav_set_reward(rmav_handle h, const rmav_reward_spec *spec);   /* NULL: back to the reference's reward */
+int rmav_get_reward(rmav_handle h, rmav_reward_spec *out, int32_t *enabled);   /* either pointer may be NULL */
+
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that
  * bootstraps a truncated episode (target r + gamma V(s_final): a truncated episode is not a failure) needs the state the dynamics

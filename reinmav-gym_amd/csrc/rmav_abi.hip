@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->reward_on) {   // a handle with a tracking reward: k_rollout_rw, which takes the skip, the range and the time limit as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_reward_rollout(h, MODE, ST, a)) return rc;
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no tracking-reward kernel for action mode %d", MODE);
+        }
     } else if (h->frame_skip > 1) {   // a handle with a frame skip: k_rollout_fs, which takes the range and the time limit as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_skip_rollout(h, MODE, ST, a)) return rc;
@@ -327,8 +333,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
     // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
     // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
-    // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1)) {
+    // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -398,12 +404,18 @@ void launch_step_hot(rmav_handle h, const RolloutArgs &a, const KindParams<K> &k
     hipLaunchKernelGGL(kernel, grid, dim3(bs), 0, h->stream, a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a, kp.p, kp.pc, tail...);
 }
 
+int launch_control(rmav_handle h, float *act_dev, int layout);
+
 // n_steps == 1 with caller actions: the latency-cut single-step kernel
 template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctrl) {
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->frame_skip > 1) {   // a handle with a frame skip: k_step_fs for every batch size (rollout_impl has refused the control() form)
+    if (h->reward_on) {   // a handle with a tracking reward: k_step_rw for every batch size; the control() form is k_control behind it
+        if (int rc = rmav_launch_reward_step(h, a, bs, FinalArgs{})) return rc;
+        if (ctrl)
+            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
+    } else if (h->frame_skip > 1) {   // a handle with a frame skip: k_step_fs for every batch size (rollout_impl has refused the control() form)
         if (int rc = rmav_launch_skip_step(h, a, bs, FinalArgs{})) return rc;
     } else if (h->range_mask) {   // a handle with a parameter range: k_step_dr for every batch size (eager record load, default store policy)
         if (int rc = rmav_launch_ranged_step(h, a, ctrl, bs, FinalArgs{})) return rc;
@@ -436,7 +448,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->frame_skip > 1) {
+    if (h->reward_on) {
+        if (int rc = rmav_launch_reward_step(h, a, bs, fa)) return rc;
+    } else if (h->frame_skip > 1) {
         if (int rc = rmav_launch_skip_step(h, a, bs, fa)) return rc;
     } else if (h->range_mask) {
         if (int rc = rmav_launch_ranged_step(h, a, false, bs, fa)) return rc;
@@ -784,6 +798,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         const size_t o_time = off; off += (kind == RMAV_REINMAV) ? up(n * sizeof(double)) : 0;
         const size_t o_er = off; off += tr ? up(n * sizeof(float)) : 0;
         const size_t o_lr = off; off += tr ? up(n * sizeof(float)) : 0;
+        // (the device copy of a tracking reward's spec: here, so that rmav_set_reward never allocates - it may be captured into a graph)
+        const size_t o_rw = off; off += (kind != RMAV_REINMAV) ? up(sizeof(RewardArgs)) : 0;
         if (hipMalloc(&h->arena, off) != hipSuccess) {
             (void)hipGetLastError();
             h->arena = nullptr;
@@ -795,6 +811,7 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         h->rec = (EnvRec *)(b + o_rec);
         h->totals = (Totals *)(b + o_tot);
         if (kind == RMAV_REINMAV) h->env_time = (double *)(b + o_time);
+        else h->reward_dev = (RewardArgs *)(b + o_rw);
         if (tr) {
             h->ep_ret = (float *)(b + o_er);
             h->last_ret = (float *)(b + o_lr);
@@ -1076,7 +1093,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // One wavefront, one k_step launch, outputs in the pinned block: the kernel publishes its completion in a pinned word and
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV) {
+    // (not rmav_step_control of a handle with a tracking reward: k_control runs behind k_step_rw, which would publish too early)
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && h->reward_on)) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {
@@ -1379,6 +1397,37 @@ int rmav_get_frame_skip(rmav_handle h, int32_t *out) {
     if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
     if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
     *out = h->frame_skip;
+    return RMAV_OK;
+}
+
+// Tracking reward: the spec on the handle (what the step and one-wavefront rollout launches pass by value) and its device copy (what the
+// policy rollouts read by pointer), rewritten on the handle's stream.  Every stepping launch reads reward_on (launch_rollout_kms,
+// launch_step_k, launch_step_final_k; rmav_policy_abi.hip).
+int rmav_set_reward(rmav_handle h, const rmav_reward_spec *spec) {
+    CHECK_HANDLE(h);
+    if (!spec) {   // back to the reference's reward: the launches of a handle that never had a spec
+        h->reward_on = 0;
+        return RMAV_OK;
+    }
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv's reward is its own (100 - 10 every step): it takes no tracking reward");
+    const float *v = &spec->goal[0];
+    static_assert(sizeof(rmav_reward_spec) == 12 * sizeof(float), "twelve floats");
+    for (int i = 0; i < 12; ++i)
+        if (!(v[i] - v[i] == 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "every value of a reward spec must be finite (value %d is not)", i);
+    const rmav_reward_spec old = h->reward;
+    h->reward = *spec;
+    if (int rc = rmav_sync_reward_dev(h)) {
+        h->reward = old;
+        return rc;
+    }
+    h->reward_on = 1;
+    return RMAV_OK;
+}
+
+int rmav_get_reward(rmav_handle h, rmav_reward_spec *out, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (out) *out = h->reward;   // (the last spec set - zeros before the first - also while it is switched off)
+    if (enabled) *enabled = h->reward_on;
     return RMAV_OK;
 }
 

@@ -1,14 +1,16 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus three that only launch kernels (rmav_policy_abi.hip,
-// rmav_range_abi.hip, rmav_skip_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus four that only launch kernels (rmav_policy_abi.hip,
+// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 #include <rccl/rccl.h>   // types only: the RCCL entry points are resolved with dlopen/dlsym on first use
@@ -103,13 +105,31 @@ struct rmav_env_s {
     // frame skip (rmav_set_frame_skip): dynamics sub-steps per agent step, 1 = none (rmav_create).  > 1 routes every stepping launch to the
     // *_fs kernels - before the range and the time limit, which those kernels take as well
     int32_t frame_skip;
+    // tracking reward (rmav_set_reward): the spec, whether one is set, and its device copy for the kernels that take it by pointer (the
+    // policy rollouts; a piece of the arena, rewritten in stream order by every set).  reward_on routes every stepping launch to
+    // the *_rw kernels - before the skip, the range and the time limit, which those kernels take as well
+    int32_t reward_on;
+    rmav_reward_spec reward;
+    rmav::RewardArgs *reward_dev;
 };
+static_assert(sizeof(rmav_reward_spec) == sizeof(rmav::RewardArgs) && offsetof(rmav_reward_spec, act_ref) == offsetof(rmav::RewardArgs, act_ref) &&
+                  offsetof(rmav_reward_spec, terminal) == offsetof(rmav::RewardArgs, terminal),
+              "RewardArgs is rmav_reward_spec, field for field");
+inline rmav::RewardArgs reward_args(const rmav_env_s *h) {
+    rmav::RewardArgs r;
+    memcpy(&r, &h->reward, sizeof(r));
+    return r;
+}
 inline rmav::FrameSkipArgs skip_args(const rmav_env_s *h) { return rmav::FrameSkipArgs{h->frame_skip}; }
 inline bool has_act_rule(const rmav_env_s *h) { return h->rule_det != 0 || h->rule_lo != -__builtin_inff() || h->rule_hi != __builtin_inff(); }
 inline rmav::ActRuleArgs act_rule_args(const rmav_env_s *h) { return rmav::ActRuleArgs{h->rule_det ? 0.0f : 1.0f, h->rule_lo, h->rule_hi}; }
 inline rmav::PolicySkipArgs policy_skip_args(const rmav_env_s *h) {
     const rmav::ActRuleArgs r = act_rule_args(h);
     return rmav::PolicySkipArgs{r.noise, r.lo, r.hi, h->frame_skip};
+}
+inline rmav::PolicyRewardArgs policy_reward_args(const rmav_env_s *h) {
+    const rmav::ActRuleArgs r = act_rule_args(h);
+    return rmav::PolicyRewardArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev};
 }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
@@ -301,3 +321,11 @@ RMAV_INTERNAL int rmav_launch_ranged_step(rmav_handle h, const rmav::RolloutArgs
 // ends with control()).  Both take the handle's range (mask = 0 without one).  The caller checks hipGetLastError.
 RMAV_INTERNAL int rmav_launch_skip_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
 RMAV_INTERNAL int rmav_launch_skip_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+
+// rmav_reward_abi.hip: the launches of a handle with a tracking reward (rmav_set_reward), shaped as the frame-skip ones, whose arguments
+// they take as well (k = 1 without a skip, mask = 0 without a range).  _rollout: ONE launch of k_rollout_rw<K, mode, st, time limit?>;
+// _step: k_step_rw at bs threads per workgroup; _sync: the handle's device copy of the spec, rewritten on the handle's stream (one small launch: no
+// allocation, no synchronisation).  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_reward_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_reward_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_sync_reward_dev(rmav_handle h);

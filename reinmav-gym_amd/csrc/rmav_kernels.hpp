@@ -328,6 +328,58 @@ struct PolicySkipArgs {
     int32_t k;
 };
 
+// The tracking reward (rmav_set_reward; the *_rw kernels), trailing as well: rmav_reward_spec of include/rmav.h, field for field
+// (rmav_handle.hpp asserts the layout).  With it the reward of a dynamics step is no longer -dist / the steps_beyond_done literal but
+//     r = terminated ? terminal : fma(-w_act, c, fma(-w_vel, v, fma(-w_pos, d, alive)))
+// with d = |P - goal|, v = |V| of the tracked body (RewardBody<K>: the body whose distance the reference rewards) on the stored post-step
+// state, and c = |u - act_ref|^2 of the action handed to Env<K>::step.  steps_beyond_done advances as ever; nothing but r depends on it.
+struct RewardArgs {
+    float goal[3];
+    float alive, w_pos, w_vel, w_act;
+    float act_ref[4];
+    float terminal;
+};
+// ... and what the tracking-reward POLICY kernels take in PolicySkipArgs' place: its four values and the handle's device copy of the spec
+// (rmav_env_s::reward_dev) by pointer - 2 scalar registers instead of 12 in kernels at their scalar-register limit; read at its use
+struct PolicyRewardArgs {
+    float noise, lo, hi;
+    int32_t k;
+    const RewardArgs *rw;
+};
+// where the tracked body's position and velocity sit in the state, and their dimension
+template <int K> struct RewardBody;
+template <> struct RewardBody<QUAD2D>    { static constexpr int P = 0,  V = 3,  D = 2; };
+template <> struct RewardBody<QUAD2D_SL> { static constexpr int P = 0,  V = 3,  D = 2; };   // the quadrotor
+template <> struct RewardBody<QUAD3D>    { static constexpr int P = 0,  V = 7,  D = 3; };
+template <> struct RewardBody<QUAD3D_SL> { static constexpr int P = 10, V = 13, D = 3; };   // the load
+// the sums in the component order of the step norms (rmav_math.hpp): the last component is the plain product
+template <int N> __device__ __forceinline__ float reward_sumsq(const float (&e)[N]) {
+    float q = e[N - 1] * e[N - 1];
+#pragma unroll
+    for (int c = N - 2; c >= 0; --c) q = rfma(e[c], e[c], q);
+    return q;
+}
+// c of an agent step: the action is held, so the *_rw bodies compute it once, in front of the sub-step loop
+template <int K> __device__ __forceinline__ float reward_act_cost(const float (&u)[Dims<K>::NA], const RewardArgs &rw) {
+    float e[Dims<K>::NA];
+#pragma unroll
+    for (int c = 0; c < Dims<K>::NA; ++c) e[c] = u[c] - rw.act_ref[c];
+    return reward_sumsq(e);
+}
+// THE reward of one dynamics step of a handle with a spec: s = the state Env<K>::step left, c = reward_act_cost of its action
+template <int K> __device__ __forceinline__ float reward_rw(const float (&s)[Dims<K>::NS], float c, const RewardArgs &rw, bool term) {
+    using B = RewardBody<K>;
+    float e[B::D], w[B::D];
+#pragma unroll
+    for (int i = 0; i < B::D; ++i) {
+        e[i] = s[B::P + i] - rw.goal[i];
+        w[i] = s[B::V + i];
+    }
+    const float d = root(reward_sumsq(e)), v = root(reward_sumsq(w));
+    const float live = rfma(-rw.w_act, c, rfma(-rw.w_vel, v, rfma(-rw.w_pos, d, rw.alive)));
+    return term ? rw.terminal : live;
+}
+
 __device__ __forceinline__ uint32_t ep_clock0(const RolloutArgs &a) { return (uint32_t)a.t0; }
 
 template <typename T> __device__ __forceinline__ T wave_sum(T v) {
@@ -454,8 +506,9 @@ __device__ __forceinline__ void wide_cols(const float *tile, rsrc_t r, uint32_t 
 template <int K, int MODE, int ST = ST_DEFAULT, bool FIXED = false>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                     const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false, DR = false, FS = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, DR = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const TimeLimitArgs tl{};
@@ -469,8 +522,9 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false, FS = false;
+    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
@@ -484,8 +538,9 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                          const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
-    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false, FS = false;
+    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const NormArgs nm{};
@@ -506,8 +561,9 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     // scalar registers) wherever the argument was placed (profiles/r09/obs_norm.md).
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false, FS = false;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
@@ -518,8 +574,9 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr) {
-    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = false;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -539,8 +596,9 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     const RangeArgs &dr = *drp;
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = false;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
 }
@@ -552,7 +610,8 @@ template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_fs(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
                                                        const FrameSkipArgs fs) {
-    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, RW = false;
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -571,7 +630,39 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     const RangeArgs &dr = *drp;
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, RW = false;
+    [[maybe_unused]] const RewardArgs rw{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#include "rmav_rollout_body.inc"
+}
+
+// The one-wavefront kernels of a handle with a tracking reward (rmav_set_reward): k_rollout_fs - a handle without a skip passes k = 1, and
+// the rolled loop then leaves R = r_0, the bits of the loop-free body - whose sub-steps are rewarded by reward_rw (RewardArgs, by value).
+// Symbols of their own: the kernels above keep their instruction streams.
+template <int K, int MODE, int ST, bool TL>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_rw(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs, const RewardArgs rw) {
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, RW = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "tracking-reward launches run the one-wavefront kernels");
+#include "rmav_rollout_body.inc"
+}
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_fs with reward_rw; the spec is read through the handle's device copy
+// (PolicyRewardArgs), the action cost from the clipped action.
+template <int K, bool BOOT>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_rw(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicyRewardArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    const RewardArgs &rw = *ps.rw;
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, RW = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
 }
@@ -646,10 +737,12 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // TL: the launch has an episode time limit (tl; k_step_tl) - with the eager record load only: every lane needs ep_start every step.
 // FIN: the launch also reports what the auto-reset destroys (fa; k_step_final).
 // DR: the handle has a parameter range (dr; k_step_dr): a finishing lane draws and stores the constants of its new episode.
-template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false>
+// RW: the handle has a tracking reward (rw; k_step_rw, on FS's loop - k = 1 without a skip): reward_rw in the literal's place.
+template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
                                           const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
-                                          [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}) {
+                                          [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{}) {
+    static_assert(!RW || FS, "the tracking reward is evaluated in the sub-step loop");
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
     static_assert(!(FS && LAZY), "the frame-skip loop runs the reward machine per sub-step: every lane's record, eagerly");
     static_assert(!(TL && LAZY), "a time limit needs every lane's episode start");
@@ -739,6 +832,8 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     // FS (k_step_fs): the action is held for up to fs.k sub-steps; the reward machine runs behind each, r accumulates in sub-step order
     [[maybe_unused]] float r_fs = 0.0f;
     if constexpr (FS) {
+        [[maybe_unused]] float c_rw = 0.0f;   // RW: the action cost of the agent step - the action is held, so once
+        if constexpr (RW) c_rw = reward_act_cost<K>(act, rw);
         bool live = true;
         done = false;
         int32_t j = 0;
@@ -747,7 +842,10 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
                 bool term;
                 Env<K>::step(s, act, pl, dist, term);
                 float rj = -dist;
-                if (term) {
+                if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
+                    rj = reward_rw<K>(s, c_rw, rw, term);
+                    if (term) sb = (sb < 0) ? 0 : sb + 1;
+                } else if (term) {
                     rj = (sb < 0) ? 1.0f : 0.0f;
                     sb = (sb < 0) ? 0 : sb + 1;
                 }
@@ -1002,6 +1100,28 @@ __global__ __launch_bounds__(kBlock) void k_step_fs(float *state_pl, int64_t n_p
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, false, false, ST_DEFAULT, TL, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs);
+}
+
+// The single-step kernel of a handle with a tracking reward (rmav_set_reward): k_step_fs (k = 1 without a skip) with reward_rw, the spec
+// trailing by value.  No CTRL form either: rmav_step_control launches k_control behind it.
+// (quadrotor3d: the twelve values of the spec take k_step_fs's 94 scalar registers past the 96 that eight wavefronts per SIMD leave each;
+// asked for eight, the compiler parks a few of them in lanes of a vector register - it has twenty to spare - and reads them back with
+// v_readlane: no scratch)
+template <int K> constexpr unsigned step_rw_min_waves() { return K == QUAD3D ? 8u : 1u; }
+template <int K, bool TL>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(step_rw_min_waves<K>()))) void k_step_rw(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs, const RewardArgs rw) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw);
 }
 
 // reset() of every env

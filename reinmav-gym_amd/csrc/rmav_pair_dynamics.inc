@@ -23,6 +23,8 @@
                 float ca[NA];
 #pragma unroll
                 for (int c = 0; c < NA; ++c) ca[c] = NORM ? act_clip(ar, act[c]) : act[c];
+                [[maybe_unused]] float c_rw = 0.0f;   // RW: the action cost of the agent step - the action is held, so once
+                if constexpr (RW) c_rw = reward_act_cost<K>(ca, rw);
                 bool live = true;
                 done = false;
                 r = 0.0f;
@@ -32,7 +34,10 @@
                         bool term;
                         Env<K>::step(s, ca, p, dist, term);
                         float rj = -dist;
-                        if (term) {
+                        if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
+                            rj = reward_rw<K>(s, c_rw, rw, term);
+                            if (term) sb = (sb < 0) ? 0 : sb + 1;
+                        } else if (term) {
                             rj = (sb < 0) ? 1.0f : 0.0f;
                             sb = (sb < 0) ? 0 : sb + 1;
                         }

@@ -236,8 +236,9 @@ __device__ __forceinline__ void state_frags(const float (&x)[16], typename PairO
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                           const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false, FS = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -248,8 +249,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair(const R
 template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, BOOT = false, NORM = false, FS = false;
+    constexpr bool TL = true, BOOT = false, NORM = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
@@ -261,8 +263,9 @@ template <int K, int FMT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                const BootArgs bt) {
-    constexpr bool TL = true, BOOT = true, NORM = false, FS = false;
+    constexpr bool TL = true, BOOT = true, NORM = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV && FMT == FMT_F16, "the (actor, critic) pair of time-limited handles");
@@ -276,8 +279,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_nrm(con
                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                               const BootArgs bt, const NormArgs nm, const ActRuleArgs ar) {
     constexpr int FMT = FMT_F16;
-    constexpr bool TL = BOOT, NORM = true, FS = false;
+    constexpr bool TL = BOOT, NORM = true, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_body.inc"
 }
@@ -288,8 +292,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_dr(cons
                                                                              const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                              const BootArgs bt, const NormArgs nm, const RangeArgs dr, const ActRuleArgs ar) {
     constexpr int FMT = FMT_F16;
-    constexpr bool TL = BOOT, NORM = true, FS = false;
+    constexpr bool TL = BOOT, NORM = true, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1
@@ -307,7 +312,26 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_fs(cons
     const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
     const FrameSkipArgs fs{ps.k};
     constexpr int FMT = FMT_F16;
-    constexpr bool TL = BOOT, NORM = true, FS = true;
+    constexpr bool TL = BOOT, NORM = true, FS = true, RW = false;
+    [[maybe_unused]] const RewardArgs rw{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with a tracking reward (rmav_set_reward; RewardArgs in rmav_kernels.hpp): k_rollout_pair_fs (k = 1 without a skip) whose
+// sub-steps are rewarded by reward_rw; the spec is read through the handle's device copy (PolicyRewardArgs).
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_rw(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyRewardArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    const RewardArgs &rw = *ps.rw;
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true, FS = true, RW = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1
@@ -426,8 +450,9 @@ __device__ __forceinline__ void shared_boot_tile1(const float *tile, int half, c
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                  const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false, FS = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const TimeLimitArgs tl{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -437,8 +462,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared(
 template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, BOOT = false, NORM = false, FS = false;
+    constexpr bool TL = true, BOOT = false, NORM = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
@@ -449,8 +475,9 @@ template <int K>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                       const BootArgs bt) {
-    constexpr bool TL = true, BOOT = true, NORM = false, FS = false;
+    constexpr bool TL = true, BOOT = true, NORM = false, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const NormArgs nm{};
     [[maybe_unused]] const ActRuleArgs ar{};
     static_assert(K != REINMAV, "ReinmavEnv ends an episode every step");
@@ -461,8 +488,9 @@ template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_nrm(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                      const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                      const BootArgs bt, const NormArgs nm, const ActRuleArgs ar) {
-    constexpr bool TL = BOOT, NORM = true, FS = false;
+    constexpr bool TL = BOOT, NORM = true, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_pair_shared_body.inc"
 }
@@ -471,8 +499,9 @@ template <int K, bool BOOT>
 __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                                                     const ParamsT<double> pc_shared, const TimeLimitArgs tl,
                                                                                     const BootArgs bt, const NormArgs nm, const RangeArgs dr, const ActRuleArgs ar) {
-    constexpr bool TL = BOOT, NORM = true, FS = false;
+    constexpr bool TL = BOOT, NORM = true, FS = false, RW = false;
     [[maybe_unused]] const FrameSkipArgs fs{};
+    [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1
@@ -487,7 +516,24 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
                                                                                     const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicySkipArgs ps) {
     const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
     const FrameSkipArgs fs{ps.k};
-    constexpr bool TL = BOOT, NORM = true, FS = true;
+    constexpr bool TL = BOOT, NORM = true, FS = true, RW = false;
+    [[maybe_unused]] const RewardArgs rw{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with a tracking reward: k_rollout_pair_shared_fs with reward_rw (see k_rollout_pair_rw).
+template <int K, bool BOOT>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_rw(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                                    const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyRewardArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    const RewardArgs &rw = *ps.rw;
+    constexpr bool TL = BOOT, NORM = true, FS = true, RW = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1

@@ -104,9 +104,12 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
                                                "not RMAV_REINMAV: there is no action-rule kernel for it");
         if (int rc = need_variants(precision, "a handle with a policy action rule (rmav_set_policy_action_rule)", "action-rule")) return rc;
     }
-    const bool skipped = h->frame_skip > 1;   // ... and so does a handle with a frame skip: its kernels are the ranged normalised ones with the sub-step loop
+    // ... and so does a handle with a frame skip or a tracking reward: its kernels are the ranged normalised ones with the sub-step loop
+    const bool skipped = h->frame_skip > 1 || h->reward_on;
     if (skipped) {
-        if (int rc = need_variants(precision, "a handle with a frame skip (rmav_set_frame_skip)", "frame-skip")) return rc;
+        if (h->reward_on) {
+            if (int rc = need_variants(precision, "a handle with a tracking reward (rmav_set_reward)", "tracking-reward")) return rc;
+        } else if (int rc = need_variants(precision, "a handle with a frame skip (rmav_set_frame_skip)", "frame-skip")) return rc;
         if (int rc = ensure_range_dev(h)) return rc;
     }
     if (h->range_mask || ruled || skipped) {

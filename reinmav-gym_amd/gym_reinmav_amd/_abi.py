@@ -60,6 +60,13 @@ class Params(C.Structure):
     ]
 
 
+class RewardSpec(C.Structure):
+    """``rmav_reward_spec``."""
+
+    _fields_ = [("goal", C.c_float * 3), ("alive", C.c_float), ("w_pos", C.c_float), ("w_vel", C.c_float), ("w_act", C.c_float),
+                ("act_ref", C.c_float * 4), ("terminal", C.c_float)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -137,6 +144,8 @@ PROTOTYPES = {
     "rmav_get_time_limit": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rmav_set_frame_skip": (C.c_int, [C.c_void_p, C.c_int32]),
     "rmav_get_frame_skip": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "rmav_set_reward": (C.c_int, [C.c_void_p, C.POINTER(RewardSpec)]),
+    "rmav_get_reward": (C.c_int, [C.c_void_p, C.POINTER(RewardSpec), C.POINTER(C.c_int32)]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

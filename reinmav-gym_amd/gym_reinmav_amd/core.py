@@ -70,22 +70,125 @@ def check_frame_skip(k) -> int:
     return int(k)
 
 
+def _finite_float(name, v) -> float:
+    if isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name} must be a real number, got {v!r}")
+    v = float(v)
+    if not np.isfinite(v) or abs(v) > float(np.finfo(np.float32).max):
+        raise ValueError(f"{name} must be finite (in fp32), got {v!r}")
+    return v
+
+
+def _finite_vector(name, v, lengths):
+    if v is None:
+        return None
+    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+        raise TypeError(f"{name} must be a sequence of {' or '.join(map(str, lengths))} numbers, got {v!r}")
+    if len(v) not in lengths:
+        raise ValueError(f"{name} must have {' or '.join(map(str, lengths))} components, got {len(v)}")
+    return tuple(_finite_float(f"{name}[{i}]", x) for i, x in enumerate(v))
+
+
+class TrackingReward:
+    """The reward of a handle with a goal (``rmav_set_reward``, include/rmav.h), evaluated inside the kernels for every dynamics step::
+
+        r = terminal                                                    if the step terminated
+        r = alive - w_pos |P - goal| - w_vel |V| - w_act |u - act_ref|^2   otherwise (also when the time limit truncated it)
+
+    ``P`` / ``V``: position / velocity of the body whose distance the reference rewards (the quadrotor; the load for
+    quadrotor3d-slungload); ``u``: the action the dynamics took (after ``clip_actions`` in a policy rollout).  ``goal=None`` = the env's
+    ``params.ref_pos`` (the controller's set-point); ``act_ref=None`` = the hover action of the kind, thrust ``mass |g_vec| /
+    thrust_scale`` and zero rates.  ``goal`` takes 3 components (2 suffice for a 2-D kind, which reads the first two), ``act_ref`` 4
+    (2 for a 2-action kind).  Types, lengths and finiteness are checked here, before the library is reached."""
+
+    FIELDS = ("goal", "alive", "w_pos", "w_vel", "w_act", "act_ref", "terminal")
+
+    def __init__(self, goal=None, alive=0.0, w_pos=1.0, w_vel=0.0, w_act=0.0, act_ref=None, terminal=0.0):
+        self.goal = _finite_vector("goal", goal, (2, 3))
+        self.act_ref = _finite_vector("act_ref", act_ref, (2, 4))
+        self.alive, self.w_pos, self.w_vel = _finite_float("alive", alive), _finite_float("w_pos", w_pos), _finite_float("w_vel", w_vel)
+        self.w_act, self.terminal = _finite_float("w_act", w_act), _finite_float("terminal", terminal)
+
+    @classmethod
+    def parse(cls, text: str) -> "TrackingReward":
+        """``"goal=0,0,2:alive=1:w_pos=1:w_vel=0.1:w_act=0.01:terminal=-10"`` (the form of ``examples/train_ppo2.py --reward``)."""
+        if not isinstance(text, str):
+            raise TypeError(f"a reward string is wanted, got {text!r}")
+        kw = {}
+        for item in filter(None, text.split(":")):
+            name, sep, val = item.partition("=")
+            if not sep or name not in cls.FIELDS or name in kw:
+                raise ValueError(f"--reward wants NAME=VALUE items separated by ':', NAME one of {cls.FIELDS}, each once; got {item!r}")
+            try:
+                nums = [float(x) for x in val.split(",")]
+            except ValueError:
+                raise ValueError(f"--reward: {item!r} is not a number or a comma-separated list of numbers") from None
+            kw[name] = tuple(nums) if name in ("goal", "act_ref") else nums[0] if len(nums) == 1 else tuple(nums)
+        return cls(**kw)
+
+    def check_kind(self, kind: int):
+        """Lengths against the kind, which the constructor does not know: a 2-component goal / action wants a 2-D / 2-action kind."""
+        dim = 2 if A.STATE_DIM[kind] in (5, 9) else 3
+        if kind == A.REINMAV:
+            raise ValueError("ReinmavEnv takes no tracking reward")
+        if self.goal is not None and len(self.goal) == 2 and dim != 2:
+            raise ValueError(f"goal has 2 components, {A.KIND_NAMES[kind]} wants 3")
+        if self.act_ref is not None and len(self.act_ref) == 2 and A.ACTION_DIM[kind] != 2:
+            raise ValueError(f"act_ref has 2 components, {A.KIND_NAMES[kind]} wants 4")
+
+    def spec(self, kind: int, params) -> "A.RewardSpec":
+        """``rmav_reward_spec`` for a handle of ``kind`` with ``params`` (the defaults resolved, fp32)."""
+        self.check_kind(kind)
+        goal = self.goal if self.goal is not None else tuple(float(x) for x in params.ref_pos)
+        if self.act_ref is not None:
+            act_ref = self.act_ref
+        else:
+            gnorm = float(np.sqrt(sum(float(x) ** 2 for x in params.g_vec)))
+            act_ref = (_finite_float("the hover thrust mass |g_vec| / thrust_scale", np.float64(params.mass) * gnorm / np.float64(params.thrust_scale)
+                                     if params.thrust_scale else float("nan")), 0.0, 0.0, 0.0)
+        goal = (tuple(goal) + (0.0, 0.0))[:3]
+        act_ref = (tuple(act_ref) + (0.0, 0.0))[:4]
+        return A.RewardSpec((C.c_float * 3)(*goal), self.alive, self.w_pos, self.w_vel, self.w_act, (C.c_float * 4)(*act_ref), self.terminal)
+
+    @classmethod
+    def from_spec(cls, s: "A.RewardSpec") -> "TrackingReward":
+        return cls(tuple(s.goal), s.alive, s.w_pos, s.w_vel, s.w_act, tuple(s.act_ref), s.terminal)
+
+    def __repr__(self):
+        return "TrackingReward(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS) + ")"
+
+
+def check_reward(reward, kind=None):
+    """``reward=`` as the constructors take it: None (the reference's reward) or a :class:`TrackingReward`; anything else is refused here."""
+    if reward is None:
+        return None
+    if not isinstance(reward, TrackingReward):
+        raise TypeError(f"reward must be None or a TrackingReward, got {reward!r}")
+    if kind is not None:
+        reward.check_kind(kind)
+    return reward
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
     def __init__(self, kind, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
-                 randomize: Optional[dict] = None, frame_skip: int = 1):
+                 randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
         ``randomize``: per-episode domain randomisation, ``{"mass": (lo, hi), "load_mass": ..., "tether_length": ...}``: every env
         draws the constant anew from ``[lo, hi)`` whenever its state is reset, inside the kernels (:meth:`set_env_param_range`).
 
-        ``frame_skip``: dynamics steps per action (gym MuJoCo's ``frame_skip``; :attr:`frame_skip`), held inside the kernels; 1 = none."""
+        ``frame_skip``: dynamics steps per action (gym MuJoCo's ``frame_skip``; :attr:`frame_skip`), held inside the kernels; 1 = none.
+
+        ``reward``: a :class:`TrackingReward` (goal, costs, alive bonus, terminal reward; :attr:`reward`), evaluated inside the kernels;
+        None = the reference's reward."""
         frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
+        reward = check_reward(reward, self.kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
         self.nS, self.nA = A.STATE_DIM[self.kind], A.ACTION_DIM[self.kind]
@@ -111,6 +214,8 @@ class BatchedQuadrotor:
             self.set_env_param_range(name, lo, hi)
         if frame_skip != 1:
             self.frame_skip = frame_skip
+        if reward is not None:
+            self.reward = reward
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -176,6 +281,21 @@ class BatchedQuadrotor:
     @frame_skip.setter
     def frame_skip(self, k: int):
         A.check(self._lib.rmav_set_frame_skip(self._h, check_frame_skip(k)))
+
+    @property
+    def reward(self) -> Optional[TrackingReward]:
+        """The :class:`TrackingReward` in force (``rmav_get_reward``; defaults resolved, values as the kernels hold them in fp32), or
+        None: the reference's reward.  Assignable at any time: ordered on the env's stream, launches enqueued afterwards see it."""
+        s, on = A.RewardSpec(), C.c_int32()
+        A.check(self._lib.rmav_get_reward(self._h, C.byref(s), C.byref(on)))
+        return TrackingReward.from_spec(s) if on.value else None
+
+    @reward.setter
+    def reward(self, reward: Optional[TrackingReward]):
+        if check_reward(reward, self.kind) is None:
+            A.check(self._lib.rmav_set_reward(self._h, None))
+        else:
+            A.check(self._lib.rmav_set_reward(self._h, C.byref(reward.spec(self.kind, self.params))))
 
     def set_policy_action_rule(self, deterministic: bool = False, clip=None):
         """What the in-kernel policy rollouts (``rmav_rollout_policy`` / ``_boot`` / ``_norm``: :class:`~gym_reinmav_amd.ppo.FusedPolicyCollector`)

@@ -535,6 +535,8 @@ class FusedPolicyCollector:
                 refuse("a policy with obs_norm", "normalised")
             if getattr(env, "frame_skip", 1) > 1:
                 refuse("an env with frame_skip", "frame-skip")
+            if getattr(env, "reward", None) is not None:
+                refuse("an env with reward=", "tracking-reward")
         self._rule = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
         if not has_variants and self._rule != (0, -math.inf, math.inf):
             refuse("deterministic= / clip_actions=", "action-rule")
