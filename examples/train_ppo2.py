@@ -45,6 +45,9 @@ def main():
                     help="tracking reward inside the kernels in place of the reference's -|pos|, e.g. "
                          "goal=0,0,2:alive=1:w_pos=1:w_vel=0.1:w_act=0.01:terminal=-10 (goal defaults to the controller's set-point, act_ref to "
                          "the hover action); not with --actor bf16")
+    ap.add_argument("--disturbance", default=None, metavar="SPEC",
+                    help="wind and gusts drawn and applied inside the step kernels, e.g. wind=-1:1,-1:1,0:0:gust=0.5,0.5,0.2:hold=25 (per-episode "
+                         "wind lo:hi per axis, gust amplitude per axis, agent steps a gust is held; m/s^2); not with --actor bf16")
     ap.add_argument("--randomize", action="append", default=[], metavar="NAME=LO:HI",
                     help="per-episode domain randomisation inside the kernels, e.g. mass=0.8:1.2 (mass | load_mass | tether_length; "
                          "repeatable); not with --actor bf16")
@@ -80,8 +83,12 @@ def main():
         reward = g.TrackingReward.parse(args.reward) if args.reward is not None else None
     except (TypeError, ValueError) as e:
         ap.error(str(e))
+    try:
+        disturbance = g.Disturbance.parse(args.disturbance) if args.disturbance is not None else None
+    except (TypeError, ValueError) as e:
+        ap.error(str(e))
     env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None,
-                             randomize=randomize or None, frame_skip=args.frame_skip, reward=reward)
+                             randomize=randomize or None, frame_skip=args.frame_skip, reward=reward, disturbance=disturbance)
     obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
     ret_norm = RunningReturnNorm(f"cuda:{env.device}") if args.normalize_reward else None   # ... and its ret=True half
     policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()
@@ -101,7 +108,7 @@ def main():
     if args.eval_every > 0:   # its own handle: the training envs' states, episode clocks and statistics are not disturbed
         eval_env = g.BatchedQuadrotor(kind, args.eval_envs, seed=args.seed, env_id_base=args.num_env,
                                       max_episode_steps=args.max_episode_steps or None, randomize=randomize or None,
-                                      frame_skip=args.frame_skip, reward=reward)
+                                      frame_skip=args.frame_skip, reward=reward, disturbance=disturbance)
     learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()

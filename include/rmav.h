@@ -71,6 +71,10 @@
  *   env constants (rmav_set_env_param_range): ONE block per env and reset, c2 = index of this env's reset (the c2 of the fresh state
  *           of that reset), c3 = (4<<24); word `which` (enum rmav_env_param) gives u = (x>>8) * 2^-24 and
  *           value = fma(hi - lo, u, lo) in fp32
+ *   wind (rmav_set_disturbance): ONE block per env and episode, c2 = the reset index of that episode (the env-constants stream's),
+ *           c3 = (5<<24); word i gives w_i = fma(wind_hi_i - wind_lo_i, u, wind_lo_i) in fp32
+ *   gust (rmav_set_disturbance): block index b = floor(t / gust_hold), t = the handle's global step counter (agent steps, as "action");
+ *           c2 = low 32 bits of b, c3 = (6<<24) | (bits 32..47 of b) << 8 ; word i gives q_i = fma(gust_i + gust_i, u, -gust_i)
  */
 #ifndef RMAV_H
 #define RMAV_H
@@ -229,6 +233,8 @@ int rmav_get_env_param_range(rmav_handle h, int which, float *lo, float *hi, int
  * (tests/test_gpu_parity.py::test_kernel_selection_variants_give_the_same_bits, ::test_single_step_variants_give_the_same_bits). */
 /* A handle with an episode time limit (rmav_set_time_limit) ignores the split and slice keys: its fused rollouts always run one
  * wavefront per 64 envs (the two-wavefront kernels have no time-limited variant). */
+/* A handle with a disturbance (rmav_set_disturbance) ignores RMAV_TUNE_STORE_POLICY as well: to bound the build its fused rollouts exist
+ * for ONE store policy (write-back).  Results never depend on the store policy. */
 enum rmav_tuning_key {
     RMAV_TUNE_SPLIT = 0,        /* fused rollouts: 0 = one wavefront per 64 envs, 1 = (integrator, memory) wavefront pairs */
     RMAV_TUNE_SLICE = 1,        /* batches beyond the pair kernel's capacity: 0 = one launch, 1 = one launch per balanced slice */
@@ -427,6 +433,48 @@ typedef struct rmav_reward_spec {
 } rmav_reward_spec;
 int rmav_set_reward(rmav_handle h, const rmav_reward_spec *spec);   /* NULL: back to the reference's reward */
 int rmav_get_reward(rmav_handle h, rmav_reward_spec *out, int32_t *enabled);   /* either pointer may be NULL */
+
+/* ---- wind and gust disturbances ---------------------------------------------------------------------------------------------------
+ * With a spec set every env of a quadrotor handle is pushed by an external acceleration d, added to rmav_params.g_vec per env and per
+ * agent step inside the step kernels (streams "wind" and "gust" of the RNG table above):
+ *     w_i = fma(wind_hi_i - wind_lo_i, u(W_i), wind_lo_i)     per episode; the span is one fp32 subtraction
+ *     q_i = fma(gust_i + gust_i, u(G_i), -gust_i)             per block of gust_hold agent steps of the handle's step counter
+ *     d_i = w_i + q_i                                          fp32, uncontracted, in this order
+ * and every use of g_vec_i in the dynamics reads g_vec_i + (R)d_i, R being the kind's arithmetic type (fp32 for the plain kinds, fp64 for
+ * the slung-load kinds, both bodies).  control() in all its forms - rmav_control, rmav_control_step, RMAV_ACT_CONTROLLER, the trailing
+ * control() of rmav_step_control - keeps the undisturbed g_vec: the controller does not know the wind.
+ *   - d is a pure function of (seed, global env id, the running episode's reset index, the step counter t, the spec): shard-invariant,
+ *     and a checkpoint is the spec alone.  rmav_seed, rmav_set_reset_counts and rmav_set_step_count move d exactly as they move the
+ *     streams they already move.  Under frame skip one d holds for all sub-steps of an agent step.
+ *   - the wind changes exactly when the reset index does: at rmav_reset and at every in-kernel auto-reset, by termination or truncation;
+ *     the step that ends an episode uses the old wind.
+ *   - nothing else depends on the spec: reward formulae, done thresholds, the reset, action, noise and constants streams, observations
+ *     (the disturbance is not observed).
+ *   - an all-zero spec gives d = +0, and g_vec + 0 has the bits of g_vec: such a handle stores the bits of one without a spec.
+ *   - rmav_disturbance_now: d of every env's NEXT step, [3][N] floats (row 2 is 0 for the 2-D kinds); RMAV_ERR_INVALID without a spec.
+ * Launches of such a handle run kernels of their own, as those of a handle with a tracking reward: fused rollouts use
+ * the one-wavefront kernels (the split, slice, step-lazy and step-store tuning keys do not apply; a chunk-major call is one launch per
+ * chunk; fused = 0 gives the bits of fused = 1).  The disturbed fused rollouts are built for ONE store policy: RMAV_TUNE_STORE_POLICY does not
+ * apply either, and results never depend on the store policy.  rmav_step_control is the step kernel's launch followed by rmav_control's
+ * (with a frame skip k > 1 it stays RMAV_ERR_INVALID).  rmav_rollout_policy / _boot / _norm run the three actors a frame skip runs
+ * (RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA, RMAV_POLICY_F16_SHARED); the other precisions return RMAV_ERR_INVALID.
+ * Validation: every value finite, wind_lo <= wind_hi, gust >= 0, gust_hold in [1, 1048576]; otherwise RMAV_ERR_INVALID.  RMAV_REINMAV takes
+ * no spec (RMAV_ERR_INVALID for a non-NULL one).  NULL switches the disturbance off: such a handle, like one that never set a spec, launches
+ * exactly the kernels it launched before.
+ * Ordering and capture as rmav_set_reward: the step kernels and the one-wavefront rollouts take the spec by value; the policy kernels read a
+ * device copy in the handle's arena, which rmav_set_disturbance rewrites in stream order with one small launch.  Launches enqueued after a
+ * set see the new spec, a captured graph keeps the values (and the step counter) it was captured with, and a set neither allocates nor
+ * synchronises.
+ * rmav_get_disturbance: the last spec set (zeros before the first), and whether it is in force; either pointer may be NULL.
+ * Callers detect the feature by the symbols; RMAV_VERSION is unchanged. */
+typedef struct rmav_disturbance_spec {
+    float wind_lo[3], wind_hi[3]; /* per-episode constant acceleration, component i ~ U[lo_i, hi_i], m/s^2; 2-D kinds read [0..1] */
+    float gust[3];                /* gust amplitude per axis, >= 0: component i ~ U[-gust_i, gust_i) */
+    int32_t gust_hold;            /* agent steps one gust value is held, 1 .. 1048576 */
+} rmav_disturbance_spec;          /* 40 bytes */
+int rmav_set_disturbance(rmav_handle h, const rmav_disturbance_spec *spec);   /* NULL: none (the default) */
+int rmav_get_disturbance(rmav_handle h, rmav_disturbance_spec *out, int32_t *enabled);   /* either pointer may be NULL */
+int rmav_disturbance_now(rmav_handle h, float *out, int mem);   /* [3][N] floats: d of every env's NEXT step; row 2 is 0 for 2-D kinds */
 
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that

@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->disturb_on) {   // a handle with a disturbance: k_rollout_ds, which takes the reward, the skip, the range and the time limit as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_disturb_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no disturbed kernel for action mode %d", MODE);
+        }
     } else if (h->reward_on) {   // a handle with a tracking reward: k_rollout_rw, which takes the skip, the range and the time limit as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_reward_rollout(h, MODE, ST, a)) return rc;
@@ -334,7 +340,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
     // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
     // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on)) {
+    // One with a disturbance (rmav_set_disturbance): k_rollout_ds.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -411,7 +418,11 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->reward_on) {   // a handle with a tracking reward: k_step_rw for every batch size; the control() form is k_control behind it
+    if (h->disturb_on) {   // a handle with a disturbance: k_step_ds for every batch size; the control() form is k_control (undisturbed) behind it
+        if (int rc = rmav_launch_disturb_step(h, a, bs, FinalArgs{})) return rc;
+        if (ctrl)
+            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
+    } else if (h->reward_on) {   // a handle with a tracking reward: k_step_rw for every batch size; the control() form is k_control behind it
         if (int rc = rmav_launch_reward_step(h, a, bs, FinalArgs{})) return rc;
         if (ctrl)
             if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
@@ -448,7 +459,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->reward_on) {
+    if (h->disturb_on) {
+        if (int rc = rmav_launch_disturb_step(h, a, bs, fa)) return rc;
+    } else if (h->reward_on) {
         if (int rc = rmav_launch_reward_step(h, a, bs, fa)) return rc;
     } else if (h->frame_skip > 1) {
         if (int rc = rmav_launch_skip_step(h, a, bs, fa)) return rc;
@@ -800,6 +813,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         const size_t o_lr = off; off += tr ? up(n * sizeof(float)) : 0;
         // (the device copy of a tracking reward's spec: here, so that rmav_set_reward never allocates - it may be captured into a graph)
         const size_t o_rw = off; off += (kind != RMAV_REINMAV) ? up(sizeof(RewardArgs)) : 0;
+        // (... and of a disturbance's spec, for the same reason)
+        const size_t o_ds = off; off += (kind != RMAV_REINMAV) ? up(sizeof(DisturbSpec)) : 0;
         if (hipMalloc(&h->arena, off) != hipSuccess) {
             (void)hipGetLastError();
             h->arena = nullptr;
@@ -811,7 +826,7 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         h->rec = (EnvRec *)(b + o_rec);
         h->totals = (Totals *)(b + o_tot);
         if (kind == RMAV_REINMAV) h->env_time = (double *)(b + o_time);
-        else h->reward_dev = (RewardArgs *)(b + o_rw);
+        else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds);
         if (tr) {
             h->ep_ret = (float *)(b + o_er);
             h->last_ret = (float *)(b + o_lr);
@@ -1093,8 +1108,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // One wavefront, one k_step launch, outputs in the pinned block: the kernel publishes its completion in a pinned word and
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
-    // (not rmav_step_control of a handle with a tracking reward: k_control runs behind k_step_rw, which would publish too early)
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && h->reward_on)) {
+    // (not rmav_step_control of a handle with a tracking reward or a disturbance: k_control runs behind k_step_rw / k_step_ds, which would publish too early)
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on))) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {
@@ -1429,6 +1444,52 @@ int rmav_get_reward(rmav_handle h, rmav_reward_spec *out, int32_t *enabled) {
     if (out) *out = h->reward;   // (the last spec set - zeros before the first - also while it is switched off)
     if (enabled) *enabled = h->reward_on;
     return RMAV_OK;
+}
+
+// Wind / gust disturbance: the spec on the handle, passed by value by every stepping launch (launch_rollout_kms, launch_step_k,
+// launch_step_final_k read disturb_on) and, for the policy kernels (rmav_policy_abi.hip), copied to the handle's arena by one small launch in
+// stream order.  No allocation, no synchronisation: ordering and capture as rmav_set_reward.
+int rmav_set_disturbance(rmav_handle h, const rmav_disturbance_spec *spec) {
+    CHECK_HANDLE(h);
+    if (!spec) {   // none: the launches of a handle that never had a spec
+        h->disturb_on = 0;
+        return RMAV_OK;
+    }
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv integrates its own rigid body: it takes no disturbance");
+    for (int i = 0; i < 3; ++i) {
+        const float lo = spec->wind_lo[i], hi = spec->wind_hi[i], g = spec->gust[i];
+        if (!(lo - lo == 0.0f) || !(hi - hi == 0.0f) || !(g - g == 0.0f))
+            return rmav_fail(RMAV_ERR_INVALID, "every value of a disturbance spec must be finite (axis %d is not)", i);
+        if (!(lo <= hi)) return rmav_fail(RMAV_ERR_INVALID, "wind_lo[%d] = %g exceeds wind_hi[%d] = %g", i, (double)lo, i, (double)hi);
+        if (!(hi - lo - (hi - lo) == 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "wind_hi[%d] - wind_lo[%d] overflows", i, i);
+        if (!(g >= 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "gust[%d] = %g is negative", i, (double)g);
+        if (!(g + g - (g + g) == 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "2 * gust[%d] overflows", i);
+    }
+    if (spec->gust_hold < 1 || spec->gust_hold > 1048576)
+        return rmav_fail(RMAV_ERR_INVALID, "gust_hold = %d is outside [1, 1048576]", (int)spec->gust_hold);
+    const rmav_disturbance_spec old = h->disturb;
+    h->disturb = *spec;
+    if (int rc = rmav_sync_disturb_dev(h)) {   // the policy kernels' copy, in stream order
+        h->disturb = old;
+        return rc;
+    }
+    h->disturb_on = 1;
+    return RMAV_OK;
+}
+
+int rmav_get_disturbance(rmav_handle h, rmav_disturbance_spec *out, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (out) *out = h->disturb;   // (the last spec set - zeros before the first - also while it is switched off)
+    if (enabled) *enabled = h->disturb_on;
+    return RMAV_OK;
+}
+
+int rmav_disturbance_now(rmav_handle h, float *out, int mem) {
+    CHECK_HANDLE(h);
+    if (mem != RMAV_HOST && mem != RMAV_DEVICE) return rmav_fail(RMAV_ERR_INVALID, "bad mem %d", mem);
+    if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
+    if (!h->disturb_on) return rmav_fail(RMAV_ERR_INVALID, "the handle has no disturbance (rmav_set_disturbance)");
+    return write_via_host(h, out, (size_t)3 * (size_t)h->n * sizeof(float), mem, [&](void *dst) { return rmav_launch_disturbance_now(h, (float *)dst); });
 }
 
 int rmav_set_time_limit(rmav_handle h, int32_t max_episode_steps) {

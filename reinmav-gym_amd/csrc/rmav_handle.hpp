@@ -1,7 +1,7 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus four that only launch kernels (rmav_policy_abi.hip,
-// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus five that only launch kernels (rmav_policy_abi.hip,
+// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -111,7 +111,26 @@ struct rmav_env_s {
     int32_t reward_on;
     rmav_reward_spec reward;
     rmav::RewardArgs *reward_dev;
+    // wind / gust disturbance (rmav_set_disturbance): the spec and whether one is set.  disturb_on routes every stepping launch to the
+    // *_ds kernels - before the reward, the skip, the range and the time limit, which those kernels take as well
+    int32_t disturb_on;
+    rmav_disturbance_spec disturb;
+    rmav::DisturbSpec *disturb_dev;   // the policy kernels' copy of the spec, in the arena next to reward_dev (k_set_disturbance rewrites it)
 };
+static_assert(sizeof(rmav_disturbance_spec) == 40, "nine floats and the hold");
+// what the *_ds kernels take for a launch whose first step has the step counter t0: the wind as (lo, hi - lo), the gust block and phase of t0
+inline rmav::DisturbArgs disturb_args(const rmav_env_s *h, uint64_t t0) {
+    rmav::DisturbArgs d{};
+    for (int i = 0; i < 3; ++i) {
+        d.v.lo[i] = h->disturb.wind_lo[i];
+        d.v.span[i] = h->disturb.wind_hi[i] - h->disturb.wind_lo[i];
+        d.v.gust[i] = h->disturb.gust[i];
+    }
+    d.v.hold = h->disturb.gust_hold;
+    d.b0 = t0 / (uint64_t)h->disturb.gust_hold;
+    d.phase0 = (int32_t)(t0 % (uint64_t)h->disturb.gust_hold);
+    return d;
+}
 static_assert(sizeof(rmav_reward_spec) == sizeof(rmav::RewardArgs) && offsetof(rmav_reward_spec, act_ref) == offsetof(rmav::RewardArgs, act_ref) &&
                   offsetof(rmav_reward_spec, terminal) == offsetof(rmav::RewardArgs, terminal),
               "RewardArgs is rmav_reward_spec, field for field");
@@ -130,6 +149,12 @@ inline rmav::PolicySkipArgs policy_skip_args(const rmav_env_s *h) {
 inline rmav::PolicyRewardArgs policy_reward_args(const rmav_env_s *h) {
     const rmav::ActRuleArgs r = act_rule_args(h);
     return rmav::PolicyRewardArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev};
+}
+// what the disturbed policy kernels take in PolicyRewardArgs' place (the launch's first step has the step counter t0)
+inline rmav::PolicyDisturbArgs policy_disturb_args(const rmav_env_s *h, uint64_t t0) {
+    const rmav::ActRuleArgs r = act_rule_args(h);
+    const rmav::DisturbArgs d = disturb_args(h, t0);
+    return rmav::PolicyDisturbArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev, h->disturb_dev, d.b0, d.phase0, 0};
 }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
@@ -329,3 +354,13 @@ RMAV_INTERNAL int rmav_launch_skip_step(rmav_handle h, const rmav::RolloutArgs &
 RMAV_INTERNAL int rmav_launch_reward_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
 RMAV_INTERNAL int rmav_launch_reward_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
 RMAV_INTERNAL int rmav_sync_reward_dev(rmav_handle h);
+
+// rmav_disturb_abi.hip: the launches of a handle with a disturbance (rmav_set_disturbance), shaped as the tracking-reward ones, whose
+// arguments they take as well (the reward as a template parameter of the kernels: on or off).  _rollout: ONE launch of
+// k_rollout_ds<K, mode, time limit?, reward?> (one store policy); _step: k_step_ds at bs threads per workgroup; _now: k_disturbance_now
+// into out [3][N] (device memory).  a.t0 is the step counter of the launch's first step.  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_disturb_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_disturb_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_disturbance_now(rmav_handle h, float *out_dev);
+// ... and k_set_disturbance: the handle's device copy of the spec (disturb_dev), rewritten in stream order; no allocation, no synchronisation
+RMAV_INTERNAL int rmav_sync_disturb_dev(rmav_handle h);

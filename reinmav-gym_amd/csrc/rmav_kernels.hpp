@@ -28,6 +28,7 @@
 #pragma once
 
 #include "rmav_math.hpp"
+#include "rmav_disturb.hpp"
 #include "rmav_policy.hpp"
 #include "rmav_policy_mfma.hpp"
 #include "rmav_policy_mfma32.hpp"
@@ -346,6 +347,17 @@ struct PolicyRewardArgs {
     int32_t k;
     const RewardArgs *rw;
 };
+// ... and the disturbed POLICY kernels (the *_ds policy families): PolicyRewardArgs - rw is read only by the RW = true kernels - with the
+// handle's device copy of the disturbance spec and the launch's place in the gust sequence (DisturbRef, rmav_disturb.hpp) behind it
+struct PolicyDisturbArgs {
+    float noise, lo, hi;
+    int32_t k;
+    const RewardArgs *rw;
+    const DisturbSpec *ds;
+    uint64_t b0;
+    int32_t phase0;
+    int32_t _pad;
+};
 // where the tracked body's position and velocity sit in the state, and their dimension
 template <int K> struct RewardBody;
 template <> struct RewardBody<QUAD2D>    { static constexpr int P = 0,  V = 3,  D = 2; };
@@ -506,7 +518,8 @@ __device__ __forceinline__ void wide_cols(const float *tile, rsrc_t r, uint32_t 
 template <int K, int MODE, int ST = ST_DEFAULT, bool FIXED = false>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                     const ParamsT<double> pc_shared) {
-    constexpr bool TL = false, BOOT = false, NORM = false, DR = false, FS = false, RW = false;
+    constexpr bool TL = false, BOOT = false, NORM = false, DR = false, FS = false, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
@@ -522,7 +535,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout(co
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl) {
-    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false, FS = false, RW = false;
+    constexpr bool TL = true, FIXED = false, BOOT = false, NORM = false, DR = false, FS = false, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
@@ -538,7 +552,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tl
 template <int K, int MODE, int ST = ST_DEFAULT>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_boot(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                          const ParamsT<double> pc_shared, const TimeLimitArgs tl, const BootArgs bt) {
-    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false, FS = false, RW = false;
+    constexpr bool TL = true, FIXED = false, BOOT = true, NORM = false, DR = false, FS = false, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
@@ -561,7 +576,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     // scalar registers) wherever the argument was placed (profiles/r09/obs_norm.md).
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false, FS = false, RW = false;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = false, FS = false, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const RangeArgs dr{};
@@ -574,7 +590,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_dr(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr) {
-    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = false, RW = false;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = false, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const ActRuleArgs ar{};
@@ -596,7 +613,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     const RangeArgs &dr = *drp;
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = false, RW = false;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = false, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
@@ -610,7 +628,8 @@ template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_fs(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
                                                        const FrameSkipArgs fs) {
-    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, RW = false;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const RewardArgs rw{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
@@ -630,7 +649,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     const RangeArgs &dr = *drp;
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, RW = false;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, RW = false, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
@@ -643,7 +663,8 @@ template <int K, int MODE, int ST, bool TL>
 __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_rw(const RolloutArgs a, const typename Env<K>::P p_shared,
                                                        const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
                                                        const FrameSkipArgs fs, const RewardArgs rw) {
-    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, RW = true;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, RW = true, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
     [[maybe_unused]] const ActRuleArgs ar{};
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
@@ -662,7 +683,44 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     const RangeArgs &dr = *drp;
     const NormArgs nm{a.act_in};
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
-    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, RW = true;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, RW = true, DS = false;
+    [[maybe_unused]] const DisturbArgs ds{};
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#include "rmav_rollout_body.inc"
+}
+
+// The one-wavefront kernels of a handle with a disturbance (rmav_set_disturbance; DisturbArgs in rmav_disturb.hpp): k_rollout_rw's body - k = 1
+// without a skip, mask = 0 without a range - whose lane constants carry gv + d.  The wind is drawn at the start of the launch and with
+// every spare reset state, the gust whenever the wave-uniform phase counter leaves a block; the fp64 controller's constants keep g_vec.
+// RW: the handle has a tracking reward as well (the reference's first-termination literal is no spec: a template parameter; rw is not
+// read without it).  One store policy: results never depend on it.
+template <int K, int MODE, bool TL, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_ds(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds) {
+    constexpr int ST = ST_DEFAULT;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, DS = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "disturbed launches run the one-wavefront kernels");
+#include "rmav_rollout_body.inc"
+}
+
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_rw - whose reward becomes the template parameter RW - with the lane
+// constants of k_rollout_ds; the specs are read through the handle's device copies (PolicyDisturbArgs).
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_ds(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicyDisturbArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
 #include "rmav_rollout_body.inc"
 }
@@ -738,11 +796,14 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // FIN: the launch also reports what the auto-reset destroys (fa; k_step_final).
 // DR: the handle has a parameter range (dr; k_step_dr): a finishing lane draws and stores the constants of its new episode.
 // RW: the handle has a tracking reward (rw; k_step_rw, on FS's loop - k = 1 without a skip): reward_rw in the literal's place.
-template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false>
+// DS: the handle has a disturbance (ds; k_step_ds): the lane's gravity is g_vec + d of this step; the controller's constants keep g_vec.
+template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false, bool DS = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
                                           const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
-                                          [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{}) {
+                                          [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{},
+                                          [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}) {
     static_assert(!RW || FS, "the tracking reward is evaluated in the sub-step loop");
+    static_assert(!DS || (FS && DR && !CTRL), "the disturbed step is cut from the most general body: the running reset index, eagerly; k_control behind it");
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
     static_assert(!(FS && LAZY), "the frame-skip loop runs the reward machine per sub-step: every lane's record, eagerly");
     static_assert(!(TL && LAZY), "a time limit needs every lane's episode start");
@@ -825,6 +886,14 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
         const double L = a.pe[2] ? (double)a.pe[2][li] : (double)pc_shared.L;
         override_params(pl, m, ml, L);
         override_params(pcl, m, ml, L);
+    }
+    // DS: the wind of the running episode (reset index rc - 1: rc names the NEXT fresh state), the gust of this step's block (ds.b0: the
+    // host has divided), added to the lane's gravity; one d for all sub-steps.  Lanes past the end are clones of env N-1 here too.
+    if constexpr (DS) {
+        float w[disturb_dim<K>()], q[disturb_dim<K>()];
+        wind_draw(ds.spec(), a.seed, a.env_base + (uint64_t)li, rc - 1u, w);
+        gust_draw(ds.spec(), a.seed, a.env_base + (uint64_t)li, ds.b0, q);
+        disturb_apply(pl, p_shared, w, q);
     }
 
     float dist = 0.0f;
@@ -1122,6 +1191,39 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(step_rw_
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, false, false, ST_DEFAULT, TL, true, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw);
+}
+
+// The single-step kernel of a handle with a disturbance (rmav_set_disturbance): k_step_rw's body and argument list with the spec behind it.
+// RW: the handle has a tracking reward as well (rw is not read without it).  No CTRL form: rmav_step_control launches k_control behind
+// it, with the undisturbed constants.
+template <int K, bool TL, bool RW>
+__global__ __launch_bounds__(kBlock) void k_step_ds(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds);
+}
+
+// rmav_disturbance_now: d of every env's NEXT step, out [3][n] (row 2 is 0 for the 2-D kinds).  ds.b0 is the block of the handle's step
+// counter; the running episode's reset index is the record's reset_cnt - 1.
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_disturbance_now(float *out, int64_t n, const EnvRec *rec, uint64_t seed, uint64_t env_base, const DisturbArgs ds) {
+    constexpr int D = disturb_dim<K>();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float w[D], q[D];
+    wind_draw(ds.spec(), seed, env_base + (uint64_t)i, rec[i].reset_cnt - 1u, w);
+    gust_draw(ds.spec(), seed, env_base + (uint64_t)i, ds.b0, q);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[(int64_t)c * n + i] = (c < D) ? w[c < D ? c : 0] + q[c < D ? c : 0] : 0.0f;
 }
 
 // reset() of every env

@@ -2,6 +2,7 @@
 // steps_beyond_done machine and the head of the time limit, in the step loop of both pair bodies.
 //   expects:  K, NA, the constexpr bools TL, NORM and FS, the kernel arguments ar (ActRuleArgs), - FS - fs (FrameSkipArgs) and - TL - tl (TimeLimitArgs); act[NA] (the
 //             action the policy drew), p, li, el
+//             - RMAV_PAIR_DS - pl, p_shared, ds_w, ds_q: pl.gv is rewritten to g_vec + d in front of the agent step
 //   defines:  dist, r (the step's reward), done (terminated or - TL - truncated)
 //   modifies: s (the state after the step), tenv (REINMAV), sb; stores one byte of tl.last_trunc where an episode ends (TL)
 //   leaves OPEN: the block of its last statement, `if constexpr (TL) {`, with `const bool trunc` (this lane's episode ran into the limit
@@ -17,6 +18,9 @@
             done = true;   // reinmav_env.py:110
             r = 90.0f;     // reinmav_env.py:111-116
         } else {
+#if RMAV_PAIR_DS   // the disturbance of this agent step (one d for all of its sub-steps): the lane's gravity is g_vec + (w + q)
+            disturb_apply(pl, p_shared, ds_w, ds_q);
+#endif
             if constexpr (FS) {
                 // frame skip (FrameSkipArgs, see k_rollout_fs): the clipped action is held for up to fs.k sub-steps, the reward machine runs
                 // behind each; closed HERE, in front of the time limit - between the same two barriers as the single step

@@ -5,7 +5,8 @@
 //             pc_shared, ar and - RMAV_PAIR_DR - dr; logstd, env_id, li, off, T, track, auto_reset
 //   defines:  the episode totals of this lane fin_n, fin_len, fin_ret; the running episode er (return), el (length); the env's record
 //             sb (steps_beyond_done), rc (reset counter); the env's constants pl and the reference p the dynamics take; tenv; the spare
-//             reset state spare[NS] with have_spare and - RMAV_PAIR_DR - the constants of the episode it starts, spare_pe[3]; pol_std[4]
+//             reset state spare[NS] with have_spare and - RMAV_PAIR_DR - the constants of the episode it starts, spare_pe[3]; pol_std[4];
+//             - RMAV_PAIR_DS (the *_ds wrappers; kernel argument ds: DisturbRef) - the wind ds_w, the gust ds_q, the gust block ds_b and the phase ds_ph
 //   modifies: nothing else (loads only: a.ep_ret, a.rec, a.pe, a.env_time)
 //   barriers: in front of the barrier that opens the step loop (B / P): it reads logstd, not the tiles
     unsigned int fin_n = 0, fin_len = 0;
@@ -55,6 +56,14 @@
 #endif
         have_spare = true;
     }
+#if RMAV_PAIR_DS   // the *_ds kernels: the wind of the running episode (reset index rc - 1: rc names the NEXT fresh state), the gust of the
+                   // running block and where the step stands in it (wave-uniform); a reset redraws the wind itself - no spare wind in registers
+    float ds_w[disturb_dim<K>()], ds_q[disturb_dim<K>()];
+    uint64_t ds_b = ds.b0;
+    int32_t ds_ph = ds.phase0;
+    wind_draw(ds.spec(), a.seed, env_id, rc - 1u, ds_w);
+    gust_draw(ds.spec(), a.seed, env_id, ds_b, ds_q);
+#endif
     float pol_std[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NA; ++c) pol_std[c] = NORM ? expf(logstd[c]) * ar.noise : expf(logstd[c]);   // the action rule: std_eff

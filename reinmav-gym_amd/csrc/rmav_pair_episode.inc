@@ -8,6 +8,7 @@
 //   modifies: er, el, fin_n, fin_len, fin_ret (an episode that ends also stores a.last_ret and the record's last_len); s, spare,
 //             have_spare, rc and - RMAV_PAIR_DR - spare_pe, pl, the handle's per-env arrays a.pe (a reset); the row: state AFTER the
 //             reset, reward, action and - unless BOOT, whose includer has written it with the truncation mark - the DONE word
+//             - RMAV_PAIR_DS - ds_w (a reset draws the new episode's wind), ds_ph, ds_b, ds_q (the next step's place in the gust sequence)
 //   barriers: in front of the barrier that ends step k (B(k) / Y(k)), which publishes the row; the includer places it
         if (track) {
             er += r;
@@ -43,10 +44,20 @@
 #if RMAV_PAIR_DR
                 range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl);   // the new episode's constants, re-derived and stored
 #endif
+#if RMAV_PAIR_DS
+                wind_draw(ds.spec(), a.seed, env_id, rc, ds_w);   // the new episode's wind (the step that ended the old one has used the old)
+#endif
                 have_spare = false;
                 rc += 1;
             }
         }
+#if RMAV_PAIR_DS   // the next agent step's place in the gust sequence; a new block draws its gust (wave-uniform: kernel arguments only)
+        if (++ds_ph >= ds.spec().hold) {
+            ds_ph = 0;
+            ++ds_b;
+            if (k + 1 < T) gust_draw(ds.spec(), a.seed, env_id, ds_b, ds_q);
+        }
+#endif
         float *row = otile + (k & 1) * PT::O_HALF;
 #pragma unroll
         for (int c = 0; c < NS; ++c) row[c * 64] = s[c];

@@ -32,7 +32,7 @@ inline BootArgs variant_boot(rmav_handle h, const BootArgs *bt) { return (h->tim
 constexpr size_t kNormBytes = sizeof(float) * kNormWords;   // the *_nrm kernels' tables, in LDS behind the weights
 
 // ---- the three actor families -------------------------------------------------------------------------------------------------------
-// A family names its kernels once - plain(), tl(), boot(), nrm<BOOT>, dr<BOOT>, fs<BOOT>, rw<BOOT>: the eleven slots (the last eight take the handle's
+// A family names its kernels once - plain(), tl(), boot(), nrm<BOOT>, dr<BOOT>, fs<BOOT>, rw<BOOT>, ds<BOOT, RW>: the fifteen slots (the last twelve take the handle's
 // action rule, act_rule_args: the identity unless rmav_set_policy_action_rule said otherwise) - and says what differs between the
 // families around them: envs behind one arrival word, the workgroup (pairs sharing one LDS copy of the weights, envs, threads), the LDS
 // bytes, and how the *_nrm / *_dr kernels take the tables and the range.  kVariants = false: the plain kernel is the only one.
@@ -73,6 +73,9 @@ template <int KIND, int MODE> struct OneWave {
     template <bool BOOT, typename Go> static void rw(Go go, const VariantArgs &v) {
         v.a.act_in = v.nm->tab, go(k_rollout_nrm_rw<K, BOOT>, v.tl, v.b, (const RangeArgs *)v.h->range_dev, policy_reward_args(v.h));
     }
+    template <bool BOOT, bool RW, typename Go> static void ds(Go go, const VariantArgs &v) {
+        v.a.act_in = v.nm->tab, go(k_rollout_nrm_ds<K, BOOT, RW>, v.tl, v.b, (const RangeArgs *)v.h->range_dev, policy_disturb_args(v.h, v.a.t0));
+    }
 };
 
 // The matrix-core actors as (actor, critic) wavefront pairs (rmav_policy_pair.hpp).  Pairs per workgroup: the pairs of a
@@ -101,6 +104,9 @@ template <int KIND, int FMT> struct Pair {   // (time-limited handles: RMAV_POLI
     template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) { go(k_rollout_pair_dr<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), act_rule_args(v.h)); }
     template <bool BOOT, typename Go> static void fs(Go go, const VariantArgs &v) { go(k_rollout_pair_fs<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), policy_skip_args(v.h)); }
     template <bool BOOT, typename Go> static void rw(Go go, const VariantArgs &v) { go(k_rollout_pair_rw<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), policy_reward_args(v.h)); }
+    template <bool BOOT, bool RW, typename Go> static void ds(Go go, const VariantArgs &v) {
+        go(k_rollout_pair_ds<K, BOOT, RW>, v.tl, v.b, *v.nm, range_args(v.h), policy_disturb_args(v.h, v.a.t0));
+    }
 };
 
 // RMAV_POLICY_F16_SHARED: one trunk, both wavefronts of a pair evaluate it for one 32-env column tile each (k_rollout_pair_shared)
@@ -117,6 +123,9 @@ template <int KIND> struct SharedPair {
     template <bool BOOT, typename Go> static void dr(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_dr<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), act_rule_args(v.h)); }
     template <bool BOOT, typename Go> static void fs(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_fs<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), policy_skip_args(v.h)); }
     template <bool BOOT, typename Go> static void rw(Go go, const VariantArgs &v) { go(k_rollout_pair_shared_rw<K, BOOT>, v.tl, v.b, *v.nm, range_args(v.h), policy_reward_args(v.h)); }
+    template <bool BOOT, bool RW, typename Go> static void ds(Go go, const VariantArgs &v) {
+        go(k_rollout_pair_shared_ds<K, BOOT, RW>, v.tl, v.b, *v.nm, range_args(v.h), policy_disturb_args(v.h, v.a.t0));
+    }
 };
 
 // ---- the one ladder: which of family F's kernels this launch runs, with which LDS size and trailing arguments ---------------------------
@@ -139,7 +148,12 @@ template <typename F> int launch_family(rmav_handle h, const RolloutArgs &a_in, 
         // a handle with a parameter range: the ranged *_nrm kernels (rmav_ppo_abi.hip hands every such call statistics and, with a limit, a boot_out)
         // a handle with a frame skip first: the *_fs kernels take the range (mask = 0 without one) and the rule as well
         // ... and one with a tracking reward in front of that: the *_rw kernels take the skip (k = 1 without one) as well
-        if (h->reward_on && v == V_NRM) F::template rw<false>(go(false), va);
+        // ... and one with a disturbance in front of that: the *_ds kernels take the reward as a template parameter
+        if (h->disturb_on && (v == V_NRM || v == V_NRM_BOOT)) {
+            if (v == V_NRM_BOOT) h->reward_on ? F::template ds<true, true>(go(true), va) : F::template ds<true, false>(go(true), va);
+            else h->reward_on ? F::template ds<false, true>(go(false), va) : F::template ds<false, false>(go(false), va);
+        } else if (h->disturb_on) return rmav_fail(RMAV_ERR_INVALID, "a handle with a disturbance runs the normalised kernels");
+        else if (h->reward_on && v == V_NRM) F::template rw<false>(go(false), va);
         else if (h->reward_on && v == V_NRM_BOOT) F::template rw<true>(go(true), va);
         else if (h->reward_on) return rmav_fail(RMAV_ERR_INVALID, "a handle with a tracking reward runs the normalised kernels");
         else if (h->frame_skip > 1 && v == V_NRM) F::template fs<false>(go(false), va);
@@ -160,9 +174,9 @@ template <typename F> int launch_family(rmav_handle h, const RolloutArgs &a_in, 
 
 template <int K> int launch_policy_k(rmav_handle h, int kmode, const RolloutArgs &a, const BootArgs *bt, const NormArgs *nm) {
     // (rmav_rollout_policy_boot has checked that the handle has a time limit and that kmode is one of the three actors with a *_boot kernel)
-    if ((nm || h->range_mask || has_act_rule(h) || h->frame_skip > 1 || h->reward_on) && (K == REINMAV || !policy_has_variants(kmode)))
+    if ((nm || h->range_mask || has_act_rule(h) || h->frame_skip > 1 || h->reward_on || h->disturb_on) && (K == REINMAV || !policy_has_variants(kmode)))
         return rmav_fail(RMAV_ERR_INVALID, "no %s kernel for policy mode %d",
-                         nm ? "normalised" : h->range_mask ? "ranged" : h->reward_on ? "tracking-reward" : h->frame_skip > 1 ? "frame-skip" : "action-rule", kmode);
+                         nm ? "normalised" : h->range_mask ? "ranged" : h->disturb_on ? "disturbed" : h->reward_on ? "tracking-reward" : h->frame_skip > 1 ? "frame-skip" : "action-rule", kmode);
     switch (kmode) {
     case RMAV_ACT_POLICY: return launch_family<OneWave<K, ACT_POLICY>>(h, a, nullptr, nullptr);
     case RMAV_ACT_POLICY_BF16:

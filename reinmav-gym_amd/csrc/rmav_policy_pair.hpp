@@ -34,6 +34,9 @@
 // fragments both include, rmav_pair_env_load.inc and rmav_pair_episode.inc) only where a *_dr wrapper sets it around its #include.  Not a
 // constexpr flag like TL / BOOT / NORM: even a dead local declaration in the bodies changed the register allocation of the bf16 pair kernels.
 #define RMAV_PAIR_DR 0
+// RMAV_PAIR_DS: likewise the wind / gust disturbance of the *_ds wrappers (rmav_set_disturbance): the per-lane wind and gust, the lane's gravity
+// g_vec + d in front of every agent step, the new wind at a reset, the wave-uniform place in the gust sequence.
+#define RMAV_PAIR_DS 0
 
 namespace rmav {
 
@@ -339,6 +342,29 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_rw(cons
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 0
 }
+// ... and of a handle with a disturbance (rmav_set_disturbance; rmav_disturb.hpp): k_rollout_pair_rw - whose reward becomes the template
+// parameter RW, as in k_rollout_ds - whose actor wavefront steps under g_vec + d; both specs are read through the handle's device copies.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_ds(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyDisturbArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
 
 // ---- one shared 2 x 64 trunk with a mean head and a value head (RMAV_POLICY_F16_SHARED) -------------------------------------------
 //
@@ -538,6 +564,28 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 1
 #include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with a disturbance: k_rollout_pair_shared_rw with the reward as a template parameter and wavefront A stepping under
+// g_vec + d (see k_rollout_pair_ds).
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_ds(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                                    const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyDisturbArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 0
 }

@@ -105,9 +105,12 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
         if (int rc = need_variants(precision, "a handle with a policy action rule (rmav_set_policy_action_rule)", "action-rule")) return rc;
     }
     // ... and so does a handle with a frame skip or a tracking reward: its kernels are the ranged normalised ones with the sub-step loop
-    const bool skipped = h->frame_skip > 1 || h->reward_on;
+    // ... and one with a disturbance: the *_ds kernels are those with g_vec + d
+    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on;
     if (skipped) {
-        if (h->reward_on) {
+        if (h->disturb_on) {
+            if (int rc = need_variants(precision, "a handle with a disturbance (rmav_set_disturbance)", "disturbed")) return rc;
+        } else if (h->reward_on) {
             if (int rc = need_variants(precision, "a handle with a tracking reward (rmav_set_reward)", "tracking-reward")) return rc;
         } else if (int rc = need_variants(precision, "a handle with a frame skip (rmav_set_frame_skip)", "frame-skip")) return rc;
         if (int rc = ensure_range_dev(h)) return rc;

@@ -464,6 +464,19 @@
         }
         const typename Env<K>::P &p = pl;
         const ParamsT<double> &pc = pcl;
+        // DS (k_rollout_ds): the wind of the running episode (reset index rc - 1: rc names the NEXT fresh state) and of the spare reset state,
+        // the gust of the running block, and where the step stands in it (wave-uniform).  pl.gv is rewritten in front of every step.
+        [[maybe_unused]] float ds_w[DS ? disturb_dim<K>() : 1], ds_q[DS ? disturb_dim<K>() : 1], spare_w[DS ? disturb_dim<K>() : 1];
+        [[maybe_unused]] uint64_t ds_b = 0;
+        [[maybe_unused]] int32_t ds_ph = 0;
+        if constexpr (DS) {
+            ds_b = ds.b0;
+            ds_ph = ds.phase0;
+            wind_draw(ds.spec(), a.seed, env_id, rc - 1u, ds_w);
+            gust_draw(ds.spec(), a.seed, env_id, ds_b, ds_q);
+#pragma unroll
+            for (int i = 0; i < disturb_dim<K>(); ++i) spare_w[i] = 0.0f;
+        }
         double tenv = 0.0;
         if constexpr (K == REINMAV) tenv = a.env_time[li];
 
@@ -497,6 +510,7 @@
                 reset_state<K>(a.seed, env_id, rc, spare);
             }
             if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);   // the spare constants with the spare state
+            if constexpr (DS) wind_draw(ds.spec(), a.seed, env_id, rc, spare_w);      // ... and the spare wind
             have_spare = true;
         }
 
@@ -698,6 +712,8 @@
                 done = true;   // reinmav_env.py:110
                 r = 90.0f;     // reinmav_env.py:111-116: 100 - 10, every step
             } else {
+                // the disturbance of this agent step (one d for all of its sub-steps): the lane's gravity is g_vec + (w + q)
+                if constexpr (DS) disturb_apply(pl, p_shared, ds_w, ds_q);
                 if constexpr (FS) {
                     // frame skip (FrameSkipArgs): the action - clipped ONCE, in front of the loop - is held for up to fs.k sub-steps, each
                     // an ordinary step with the reward / steps_beyond_done machine behind it; a lane leaves at its first termination,
@@ -912,6 +928,14 @@
             if (!SPLIT && done_out) {
                 __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(done ? 1 : 0), make_rsrc(done_out), li, 0, 0);
                 done_out += tn;
+            }
+            // DS: the next agent step's place in the gust sequence; a new block draws its gust (wave-uniform: kernel arguments only)
+            if constexpr (DS) {
+                if (++ds_ph >= ds.spec().hold) {
+                    ds_ph = 0;
+                    ++ds_b;
+                    if (k + 1 < a.n_steps) gust_draw(ds.spec(), a.seed, env_id, ds_b, ds_q);
+                }
             }
         }
         if constexpr (MODE == ACT_CONTROLLER_SPLIT || split_self_fetch(MODE)) __syncthreads();   // B(nc): the last step's outputs are in LDS

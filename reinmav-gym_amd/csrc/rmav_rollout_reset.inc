@@ -1,10 +1,10 @@
 // rmav_rollout_reset.inc - the auto-reset of rmav_rollout_body.inc: draw a spare reset state if a finishing lane has none, copy it,
 // re-derive a ranged handle's constants.  Included twice, behind each of the two forms of the episode bookkeeping (SKIP_QUIET and
 // predicated: see the comment above them) - the same statements, so a field added to the reset goes here once.
-//   expects:  K, NS, the constexpr bools SPARE_LDS and DR, the kernel arguments a, pc_shared and - DR - dr; done (after the time limit),
-//             auto_reset, env_id, li, off; the spare state in spare[] or - SPARE_LDS - behind lds_spare (this lane's words only)
+//   expects:  K, NS, the constexpr bools SPARE_LDS, DR and DS, the kernel arguments a, pc_shared and - DR - dr, - DS - ds; done (after the time
+//             limit), auto_reset, env_id, li, off; the spare state in spare[] or - SPARE_LDS - behind lds_spare (this lane's words only)
 //   defines:  nothing that outlives it
-//   modifies: s, have_spare, rc, the spare state and - DR - spare_pe, pl, pcl, the handle's per-env arrays a.pe
+//   modifies: s, have_spare, rc, the spare state and - DR - spare_pe, pl, pcl, the handle's per-env arrays a.pe, - DS - spare_w, ds_w
 //   barriers: none (the LDS spare is read back by the lane that wrote it)
                 if (K != REINMAV && auto_reset) {
                     const bool rst = done;
@@ -18,6 +18,7 @@
                                 else spare[c] = sp[c];
                             }
                             if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);
+                            if constexpr (DS) wind_draw(ds.spec(), a.seed, env_id, rc, spare_w);
                             have_spare = true;
                         }
                     }
@@ -28,6 +29,10 @@
                             else s[c] = spare[c];
                         }
                         if constexpr (DR) range_apply(dr, a.pe, pc_shared, li, off, spare_pe, pl, pcl);   // the new episode's constants, re-derived and stored
+                        if constexpr (DS) {   // the new episode's wind (the step that ended the old one has used the old)
+#pragma unroll
+                            for (int i = 0; i < disturb_dim<K>(); ++i) ds_w[i] = spare_w[i];
+                        }
                         have_spare = false;
                         rc += 1;
                     }

@@ -67,6 +67,12 @@ class RewardSpec(C.Structure):
                 ("act_ref", C.c_float * 4), ("terminal", C.c_float)]
 
 
+class DisturbanceSpec(C.Structure):
+    """``rmav_disturbance_spec``."""
+
+    _fields_ = [("wind_lo", C.c_float * 3), ("wind_hi", C.c_float * 3), ("gust", C.c_float * 3), ("gust_hold", C.c_int32)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -146,6 +152,9 @@ PROTOTYPES = {
     "rmav_get_frame_skip": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "rmav_set_reward": (C.c_int, [C.c_void_p, C.POINTER(RewardSpec)]),
     "rmav_get_reward": (C.c_int, [C.c_void_p, C.POINTER(RewardSpec), C.POINTER(C.c_int32)]),
+    "rmav_set_disturbance": (C.c_int, [C.c_void_p, C.POINTER(DisturbanceSpec)]),
+    "rmav_get_disturbance": (C.c_int, [C.c_void_p, C.POINTER(DisturbanceSpec), C.POINTER(C.c_int32)]),
+    "rmav_disturbance_now": (C.c_int, [C.c_void_p, _fp, C.c_int]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

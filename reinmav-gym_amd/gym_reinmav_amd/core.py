@@ -169,13 +169,127 @@ def check_reward(reward, kind=None):
     return reward
 
 
+class Disturbance:
+    """An external acceleration on every env of a handle (``rmav_set_disturbance``, include/rmav.h), drawn and added to gravity inside
+    the step kernels, per env and per agent step::
+
+        d = wind + gust        wind_i ~ U[lo_i, hi_i] once per episode, gust_i ~ U[-g_i, g_i) once per ``hold`` agent steps   (m/s^2)
+
+    ``wind``: one ``(lo, hi)`` pair per axis (3; 2 suffice for a 2-D kind, which reads the first two), or a scalar half-width ``w`` for
+    ``(-w, w)`` on every axis.  ``gust``: one amplitude per axis, or a scalar for all.  ``hold``: agent steps one gust value is held,
+    1 .. 1 048 576.  The controller does not know the disturbance, and it is not part of the observation.  Types, lengths, finiteness
+    and order are checked here, before the library is reached."""
+
+    FIELDS = ("wind", "gust", "hold")
+    MAX_HOLD = 1 << 20
+
+    def __init__(self, wind=0.0, gust=0.0, hold=1):
+        if isinstance(wind, (int, float, np.integer, np.floating)) and not isinstance(wind, (bool, np.bool_)):
+            w = _finite_float("wind", wind)
+            if w < 0:
+                raise ValueError(f"a scalar wind is a half-width and must be >= 0, got {wind!r}")
+            self.wind = ((-w if w else 0.0, w),) * 3
+        else:
+            if isinstance(wind, (str, bytes)) or not hasattr(wind, "__len__"):
+                raise TypeError(f"wind must be a half-width or a sequence of 2 or 3 (lo, hi) pairs, got {wind!r}")
+            if len(wind) not in (2, 3):
+                raise ValueError(f"wind must have 2 or 3 (lo, hi) pairs, got {len(wind)}")
+            pairs = []
+            for i, pr in enumerate(wind):
+                pr = _finite_vector(f"wind[{i}]", pr, (2,))
+                if pr is None or pr[0] > pr[1]:
+                    raise ValueError(f"wind[{i}] must be (lo, hi) with lo <= hi, got {pr!r}")
+                if abs(pr[1] - pr[0]) > float(np.finfo(np.float32).max):
+                    raise ValueError(f"wind[{i}]: hi - lo overflows fp32")
+                pairs.append(pr)
+            self.wind = tuple(pairs)
+        if isinstance(gust, (int, float, np.integer, np.floating)) and not isinstance(gust, (bool, np.bool_)):
+            self.gust = (_finite_float("gust", gust),) * 3
+        else:
+            self.gust = _finite_vector("gust", gust, (2, 3))
+            if self.gust is None:
+                raise TypeError("gust must be an amplitude or a sequence of 2 or 3 amplitudes, got None")
+        for i, gv in enumerate(self.gust):
+            if gv < 0 or 2.0 * gv > float(np.finfo(np.float32).max):
+                raise ValueError(f"gust[{i}] must be >= 0 and 2 * gust[{i}] finite in fp32, got {gv!r}")
+        if isinstance(hold, (bool, np.bool_)) or not isinstance(hold, (int, np.integer)):
+            raise TypeError(f"hold must be an integer, got {hold!r}")
+        if not 1 <= int(hold) <= self.MAX_HOLD:
+            raise ValueError(f"hold must be in [1, {self.MAX_HOLD}], got {hold!r}")
+        self.hold = int(hold)
+
+    @classmethod
+    def parse(cls, text: str) -> "Disturbance":
+        """``"wind=-1:1,-1:1,0:0:gust=0.5,0.5,0.2:hold=25"`` (the form of ``examples/train_ppo2.py --disturbance``): ``wind`` is one
+        ``lo:hi`` per axis (or one half-width), ``gust`` one amplitude per axis (or one for all)."""
+        if not isinstance(text, str):
+            raise TypeError(f"a disturbance string is wanted, got {text!r}")
+        import re
+
+        parts = re.split(r"(?:^|:)(\w+)=", text)
+        if parts[0].strip(":") or len(parts) < 3:
+            raise ValueError(f"--disturbance wants NAME=VALUE items separated by ':', NAME one of {cls.FIELDS}; got {text!r}")
+        kw = {}
+        for name, val in zip(parts[1::2], parts[2::2]):
+            if name not in cls.FIELDS or name in kw:
+                raise ValueError(f"--disturbance wants NAME=VALUE items, NAME one of {cls.FIELDS}, each once; got {name + '=' + val!r}")
+            try:
+                if name == "hold":
+                    kw[name] = int(val)
+                elif name == "gust":
+                    nums = [float(x) for x in val.split(",")]
+                    kw[name] = nums[0] if len(nums) == 1 else tuple(nums)
+                elif ":" not in val:
+                    kw[name] = float(val)
+                else:
+                    kw[name] = tuple(tuple(float(x) for x in pr.split(":")) for pr in val.split(","))
+            except ValueError:
+                raise ValueError(f"--disturbance: {name + '=' + val!r} does not parse as numbers") from None
+        return cls(**kw)
+
+    def check_kind(self, kind: int):
+        """Lengths against the kind, which the constructor does not know: 2 axes want a 2-D kind."""
+        if kind == A.REINMAV:
+            raise ValueError("ReinmavEnv takes no disturbance")
+        dim = 2 if A.STATE_DIM[kind] in (5, 9) else 3
+        if dim == 3 and (len(self.wind) == 2 or len(self.gust) == 2):
+            raise ValueError(f"wind / gust have 2 axes, {A.KIND_NAMES[kind]} wants 3")
+
+    def spec(self, kind: int) -> "A.DisturbanceSpec":
+        """``rmav_disturbance_spec`` for a handle of ``kind`` (a 2-D kind's third axis is 0)."""
+        self.check_kind(kind)
+        dim = 2 if A.STATE_DIM[kind] in (5, 9) else 3
+        wind = (tuple(self.wind[:dim]) + ((0.0, 0.0),))[:3]
+        gust = (tuple(self.gust[:dim]) + (0.0,))[:3]
+        return A.DisturbanceSpec((C.c_float * 3)(*(p[0] for p in wind)), (C.c_float * 3)(*(p[1] for p in wind)), (C.c_float * 3)(*gust), self.hold)
+
+    @classmethod
+    def from_spec(cls, s: "A.DisturbanceSpec") -> "Disturbance":
+        return cls(tuple(zip(s.wind_lo, s.wind_hi)), tuple(s.gust), int(s.gust_hold))
+
+    def __repr__(self):
+        return "Disturbance(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS) + ")"
+
+
+def check_disturbance(disturbance, kind=None):
+    """``disturbance=`` as the constructors take it: None (still air) or a :class:`Disturbance`; anything else is refused here."""
+    if disturbance is None:
+        return None
+    if not isinstance(disturbance, Disturbance):
+        raise TypeError(f"disturbance must be None or a Disturbance, got {disturbance!r}")
+    if kind is not None:
+        disturbance.check_kind(kind)
+    return disturbance
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
     def __init__(self, kind, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
-                 randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None):
+                 randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None,
+                 disturbance: Optional[Disturbance] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
@@ -185,10 +299,14 @@ class BatchedQuadrotor:
         ``frame_skip``: dynamics steps per action (gym MuJoCo's ``frame_skip``; :attr:`frame_skip`), held inside the kernels; 1 = none.
 
         ``reward``: a :class:`TrackingReward` (goal, costs, alive bonus, terminal reward; :attr:`reward`), evaluated inside the kernels;
-        None = the reference's reward."""
+        None = the reference's reward.
+
+        ``disturbance``: a :class:`Disturbance` (per-episode wind, held gusts; :attr:`disturbance`), drawn and applied inside the kernels;
+        None = still air."""
         frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         reward = check_reward(reward, self.kind)
+        disturbance = check_disturbance(disturbance, self.kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
         self.nS, self.nA = A.STATE_DIM[self.kind], A.ACTION_DIM[self.kind]
@@ -216,6 +334,8 @@ class BatchedQuadrotor:
             self.frame_skip = frame_skip
         if reward is not None:
             self.reward = reward
+        if disturbance is not None:
+            self.disturbance = disturbance
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -296,6 +416,29 @@ class BatchedQuadrotor:
             A.check(self._lib.rmav_set_reward(self._h, None))
         else:
             A.check(self._lib.rmav_set_reward(self._h, C.byref(reward.spec(self.kind, self.params))))
+
+    @property
+    def disturbance(self) -> Optional[Disturbance]:
+        """The :class:`Disturbance` in force (``rmav_get_disturbance``; values as the kernels hold them in fp32), or None: still air.
+        Assignable at any time (host state only): launches enqueued afterwards see it."""
+        s, on = A.DisturbanceSpec(), C.c_int32()
+        A.check(self._lib.rmav_get_disturbance(self._h, C.byref(s), C.byref(on)))
+        return Disturbance.from_spec(s) if on.value else None
+
+    @disturbance.setter
+    def disturbance(self, disturbance: Optional[Disturbance]):
+        if check_disturbance(disturbance, self.kind) is None:
+            A.check(self._lib.rmav_set_disturbance(self._h, None))
+        else:
+            A.check(self._lib.rmav_set_disturbance(self._h, C.byref(disturbance.spec(self.kind))))
+
+    def disturbance_now(self, out=None):
+        """The acceleration ``d`` every env's NEXT step adds to gravity (``rmav_disturbance_now``): a device tensor ``[3, N]`` (row 2 is
+        0 for a 2-D kind).  The env must have a :attr:`disturbance`."""
+        if out is None:
+            out = torch.empty((3, self.num_envs), dtype=torch.float32, device=f"cuda:{self.device}")
+        A.check(self._lib.rmav_disturbance_now(self._h, self._ptr(out), A.DEVICE))
+        return out
 
     def set_policy_action_rule(self, deterministic: bool = False, clip=None):
         """What the in-kernel policy rollouts (``rmav_rollout_policy`` / ``_boot`` / ``_norm``: :class:`~gym_reinmav_amd.ppo.FusedPolicyCollector`)

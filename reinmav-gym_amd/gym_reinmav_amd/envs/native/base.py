@@ -40,7 +40,7 @@ class NativeQuadrotorEnv(_EnvBase):
     _action_box = None    # (low, high, dtype)
     _reading_2d = None
 
-    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None, frame_skip: int = 1, reward=None):
+    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None, frame_skip: int = 1, reward=None, disturbance=None):
         kind = A.KIND_BY_NAME[self._kind]
         nS, nA = A.STATE_DIM[kind], A.ACTION_DIM[kind]
         lo, hi, dt = self._action_box
@@ -57,11 +57,12 @@ class NativeQuadrotorEnv(_EnvBase):
         # frame_skip (gym.make(id, frame_skip=k)): step() holds its action for k dynamics steps inside the kernel.  rmav_step_control has
         # no such kernel: step() is then rmav_step, and control() a launch of its own (rmav_control) on the state step() left.
         # reward (gym.make(id, reward=TrackingReward(...))): step() returns the tracking reward, computed inside the kernel.
+        # disturbance (gym.make(id, disturbance=Disturbance(...))): step() adds the wind and the gust to gravity; control() does not know them.
         self._limited = bool(max_episode_steps)
         self._batch = BatchedQuadrotor(kind, 1, device=device, seed=self._seed_value, auto_reset=False,
                                        track_episodes=self._limited, reading_2d=self._reading_2d,
                                        max_episode_steps=max_episode_steps, randomize=randomize, frame_skip=frame_skip,
-                                       reward=reward)
+                                       reward=reward, disturbance=disturbance)
         self._dim = 2 if nS in (5, 9) else 3
         self._has_load = nS in (9, 16)
         # Lean per-call path: preallocated host arrays and cached ctypes pointers, so a step() is one ABI call
@@ -148,6 +149,19 @@ class NativeQuadrotorEnv(_EnvBase):
     @reward.setter
     def reward(self, reward):
         self._batch.reward = reward
+
+    @property
+    def disturbance(self):
+        """The ``Disturbance`` in force or None (``BatchedQuadrotor.disturbance``); assignable."""
+        return self._batch.disturbance
+
+    @disturbance.setter
+    def disturbance(self, disturbance):
+        self._batch.disturbance = disturbance
+
+    def disturbance_now(self):
+        """The acceleration the next ``step`` adds to gravity, ``[3]`` floats (``BatchedQuadrotor.disturbance_now``)."""
+        return self._batch.disturbance_now()[:, 0].cpu().numpy()
 
     # -- public attributes of the reference ---------------------------------------------------------------
     @property

@@ -537,6 +537,8 @@ class FusedPolicyCollector:
                 refuse("an env with frame_skip", "frame-skip")
             if getattr(env, "reward", None) is not None:
                 refuse("an env with reward=", "tracking-reward")
+            if getattr(env, "disturbance", None) is not None:
+                refuse("an env with disturbance=", "disturbed")
         self._rule = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
         if not has_variants and self._rule != (0, -math.inf, math.inf):
             refuse("deterministic= / clip_actions=", "action-rule")

@@ -14,7 +14,7 @@ as added.  A typical use: `make asm` on the parent commit, copy build/ aside, `m
 
 One difference is reported apart: `s_mov_b32 s15, <k>` in front of a call is the LDS kernel id the backend passes to a non-inlined
 device function that reads LDS (the index of the calling kernel in the module's LDS lookup table), and it moves when kernels are
-added to the module; a function whose only differences are such immediates is listed as "kernel id only" and does not count as
+added to the module (an id above 64 is written `s_movk_i32 s15, 0x<k>`: the same size, the same register); a function whose only differences are such immediates is listed as "kernel id only" and does not count as
 changed."""
 import argparse
 import glob
@@ -23,7 +23,7 @@ import re
 import sys
 
 _LABEL = re.compile(r"\.L[A-Za-z_]*\d+(?:_\d+)*")
-_KERNEL_ID = re.compile(r"^s_mov_b32 s15, \d+$")
+_KERNEL_ID = re.compile(r"^(?:s_mov_b32 s15, \d+|s_movk_i32 s15, 0x[0-9a-f]+)$")   # (an id above 64 is no inline constant: s_movk_i32)
 
 
 def kernels(path):
