@@ -75,6 +75,10 @@
  *           c3 = (5<<24); word i gives w_i = fma(wind_hi_i - wind_lo_i, u, wind_lo_i) in fp32
  *   gust (rmav_set_disturbance): block index b = floor(t / gust_hold), t = the handle's global step counter (agent steps, as "action");
  *           c2 = low 32 bits of b, c3 = (6<<24) | (bits 32..47 of b) << 8 ; word i gives q_i = fma(gust_i + gust_i, u, -gust_i)
+ *   sensor (rmav_set_sensor_noise): block (b, j), j = c >> 2 in 0 .. 3 for observation component c; b = the handle's global step counter
+ *           AFTER the operation that produced the observation; c2 = low 32 bits of b, c3 = (7<<24) | (bits 32..47 of b) << 8 | j;
+ *           (r0,r1) and (r2,r3) go through Box-Muller exactly as "noise": u1 = ((r>>8)+1) * 2^-24, u2 = (r'>>8) * 2^-24,
+ *           rad = sqrtf(-2 logf(u1)), sincospif(2 u2), z = rad * (cos, sin); that gives z[4j .. 4j+3]
  */
 #ifndef RMAV_H
 #define RMAV_H
@@ -475,6 +479,50 @@ typedef struct rmav_disturbance_spec {
 int rmav_set_disturbance(rmav_handle h, const rmav_disturbance_spec *spec);   /* NULL: none (the default) */
 int rmav_get_disturbance(rmav_handle h, rmav_disturbance_spec *out, int32_t *enabled);   /* either pointer may be NULL */
 int rmav_disturbance_now(rmav_handle h, float *out, int mem);   /* [3][N] floats: d of every env's NEXT step; row 2 is 0 for 2-D kinds */
+
+/* ---- sensor noise: Gaussian observation noise drawn inside the kernels --------------------------------------------------------------
+ * With a spec set every OBSERVATION a quadrotor handle emits for an env is, per component c, in fp32 (stream "sensor" of the RNG table
+ * above):
+ *     o_c = fma(sigma_c, z_c, s_c)
+ * s being the true state the observation reports and z standard normal.  b, the block's step counter, is the handle's step counter (agent
+ * steps) AFTER the operation that produced the observation: a step that moves t -> t+1 emits observations with b = t+1, rmav_reset and
+ * rmav_observe use b = t.  An observation is therefore a pure function of (seed, global env id, state, step counter, spec): shard-invariant,
+ * stateless, and a checkpoint is the spec alone.  ONE rule ties every route together: what an operation emits for an env has the bits of
+ * rmav_observe called right after it.
+ *   - noisy: obs_out of rmav_reset / rmav_step / rmav_control_step / rmav_step_control / rmav_step_final and of rmav_rollout / _pitched /
+ *     _chunked in all three action modes, fused and unfused; final_obs_out of rmav_step_final (s = the pre-reset state, under the SAME z as
+ *     the post-reset observation of that step).
+ *   - not noisy: the dynamics, done, rewards (the tracking reward reads the true state), episode statistics, every other stream,
+ *     rmav_get_state, and control() in all its forms (the reference controller reads the state).  A handle with a spec and caller, random
+ *     or controller actions leaves every non-observation output and its state bit-identical to a twin without one.
+ *   - sigma_c = 0 gives o_c == s_c bit for bit, except that a -0.0 may come out as +0.0 (fma(0, z, -0.0) is +0.0 when 0 * z is +0.0).  An
+ *     all-zero spec stores the values of a handle without one.
+ *   - rmav_observe: the observation of every env's current state at b = t, nS*N floats, both mem values and both layouts.  On a handle
+ *     without a spec it has the bits of rmav_get_state.
+ * Launches of such a handle run kernels of their own, cut from the disturbed ones, whose launch rules they share: the
+ * one-wavefront fused rollouts with ONE store policy (the split, slice, step-lazy, step-store and store-policy tuning keys do not apply; a
+ * chunk-major call is one launch per chunk; fused = 0 gives the bits of fused = 1); a handle without a disturbance passes the all-zero
+ * disturbance, whose d = +0 leaves g_vec's bits.  rmav_step_control is the step kernel's launch followed by rmav_control's.
+ * rmav_rollout_policy / _boot / _norm run the three actors a disturbance runs (RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA,
+ * RMAV_POLICY_F16_SHARED): the input of every policy- and value-net evaluation - value_out[n_steps] and the bootstrap V(s_final) included,
+ * in front of the normaliser when there is one - and the stored obs_out are the noisy observation (what the actor reads at step k of a
+ * launch that started at t0 is rmav_observe at b = t0 + k, the row the previous step or launch stored); the dynamics run from the true
+ * state.  The other precisions return RMAV_ERR_INVALID with a message that names the feature.
+ * Validation: every sigma_c finite and >= 0, sigma_c == 0 for c >= nS; RMAV_REINMAV takes no spec; anything else is RMAV_ERR_INVALID and
+ * the spec in force stays.  NULL switches the feature off: such a handle, like one that never set a spec, launches exactly the kernels it
+ * launched before.
+ * Ordering and capture as rmav_set_reward: the step kernels, the one-wavefront rollouts and rmav_observe's kernel take the spec by value; the
+ * policy kernels read a device copy in the handle's arena, which rmav_set_sensor_noise rewrites in stream order with one small launch.
+ * Launches enqueued after a set see the new spec, a captured graph keeps the values (and the step counter) it was captured with, and a
+ * set neither allocates nor synchronises.
+ * rmav_get_sensor_noise: the last spec set (zeros before the first), and whether it is in force; either pointer may be NULL.
+ * Callers detect the feature by the symbols; RMAV_VERSION is unchanged. */
+typedef struct rmav_sensor_noise_spec {
+    float sigma[16];              /* standard deviation per observation component; only components < nS are used, the others must be 0 */
+} rmav_sensor_noise_spec;         /* 64 bytes */
+int rmav_set_sensor_noise(rmav_handle h, const rmav_sensor_noise_spec *spec);   /* NULL: none (the default) */
+int rmav_get_sensor_noise(rmav_handle h, rmav_sensor_noise_spec *out, int32_t *enabled);   /* either pointer may be NULL */
+int rmav_observe(rmav_handle h, float *obs_out, int mem, int layout);   /* nS*N floats: the observation of the current state at b = t */
 
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that

@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->sensor_on) {   // a handle with sensor noise: k_rollout_sn, which takes the disturbance (all-zero without one) and all it takes as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_sensor_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no sensor-noise kernel for action mode %d", MODE);
+        }
     } else if (h->disturb_on) {   // a handle with a disturbance: k_rollout_ds, which takes the reward, the skip, the range and the time limit as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_disturb_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
@@ -340,8 +346,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
     // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
     // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
-    // One with a disturbance (rmav_set_disturbance): k_rollout_ds.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on)) {
+    // One with a disturbance (rmav_set_disturbance): k_rollout_ds.  One with sensor noise (rmav_set_sensor_noise): k_rollout_sn.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -418,7 +424,11 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->disturb_on) {   // a handle with a disturbance: k_step_ds for every batch size; the control() form is k_control (undisturbed) behind it
+    if (h->sensor_on) {   // a handle with sensor noise: k_step_sn for every batch size; the control() form is k_control (of the true state) behind it
+        if (int rc = rmav_launch_sensor_step(h, a, bs, FinalArgs{})) return rc;
+        if (ctrl)
+            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
+    } else if (h->disturb_on) {   // a handle with a disturbance: k_step_ds for every batch size; the control() form is k_control (undisturbed) behind it
         if (int rc = rmav_launch_disturb_step(h, a, bs, FinalArgs{})) return rc;
         if (ctrl)
             if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
@@ -459,7 +469,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->disturb_on) {
+    if (h->sensor_on) {
+        if (int rc = rmav_launch_sensor_step(h, a, bs, fa)) return rc;
+    } else if (h->disturb_on) {
         if (int rc = rmav_launch_disturb_step(h, a, bs, fa)) return rc;
     } else if (h->reward_on) {
         if (int rc = rmav_launch_reward_step(h, a, bs, fa)) return rc;
@@ -815,6 +827,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         const size_t o_rw = off; off += (kind != RMAV_REINMAV) ? up(sizeof(RewardArgs)) : 0;
         // (... and of a disturbance's spec, for the same reason)
         const size_t o_ds = off; off += (kind != RMAV_REINMAV) ? up(sizeof(DisturbSpec)) : 0;
+        // (... and of a sensor-noise spec)
+        const size_t o_sn = off; off += (kind != RMAV_REINMAV) ? up(sizeof(SensorDev)) : 0;
         if (hipMalloc(&h->arena, off) != hipSuccess) {
             (void)hipGetLastError();
             h->arena = nullptr;
@@ -826,7 +840,7 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         h->rec = (EnvRec *)(b + o_rec);
         h->totals = (Totals *)(b + o_tot);
         if (kind == RMAV_REINMAV) h->env_time = (double *)(b + o_time);
-        else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds);
+        else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds), h->sensor_dev = (SensorDev *)(b + o_sn);
         if (tr) {
             h->ep_ret = (float *)(b + o_er);
             h->last_ret = (float *)(b + o_lr);
@@ -1021,8 +1035,12 @@ int rmav_sync(rmav_handle h) {
 int rmav_reset(rmav_handle h, float *obs_out, int mem, int layout) {
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
-    return write_via_host(h, obs_out, (size_t)h->n * kStateDim[h->kind] * sizeof(float), mem,
-                          [&](void *dst) { return launch_reset_tl(h, (float *)dst, layout); });
+    return write_via_host(h, obs_out, (size_t)h->n * kStateDim[h->kind] * sizeof(float), mem, [&](void *dst) {
+        if (!h->sensor_on || !dst) return launch_reset_tl(h, (float *)dst, layout);
+        // a handle with sensor noise: the reset, then the observation of the fresh states at the handle's step counter (k_observe)
+        if (int rc = launch_reset_tl(h, nullptr, layout)) return rc;
+        return rmav_launch_observe(h, (float *)dst, layout);
+    });
 }
 
 // rmav_rollout / rmav_step / rmav_step_control / rmav_control_step.  ctrl_out (nullable): control() of the state the
@@ -1108,8 +1126,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // One wavefront, one k_step launch, outputs in the pinned block: the kernel publishes its completion in a pinned word and
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
-    // (not rmav_step_control of a handle with a tracking reward or a disturbance: k_control runs behind k_step_rw / k_step_ds, which would publish too early)
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on))) {
+    // (not rmav_step_control of a handle with a tracking reward, a disturbance or sensor noise: k_control runs behind k_step_rw / k_step_ds / k_step_sn, which would publish too early)
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on))) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {
@@ -1490,6 +1508,49 @@ int rmav_disturbance_now(rmav_handle h, float *out, int mem) {
     if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
     if (!h->disturb_on) return rmav_fail(RMAV_ERR_INVALID, "the handle has no disturbance (rmav_set_disturbance)");
     return write_via_host(h, out, (size_t)3 * (size_t)h->n * sizeof(float), mem, [&](void *dst) { return rmav_launch_disturbance_now(h, (float *)dst); });
+}
+
+// Sensor noise: the spec on the handle, passed by value by every launch that emits an observation (launch_rollout_kms, launch_step_k,
+// launch_step_final_k and rmav_reset read sensor_on) and, for the policy kernel (rmav_sensor_policy_abi.hip), copied to the handle's arena by
+// one small launch in stream order.  No allocation, no synchronisation: ordering and capture as rmav_set_disturbance.
+int rmav_set_sensor_noise(rmav_handle h, const rmav_sensor_noise_spec *spec) {
+    CHECK_HANDLE(h);
+    if (!spec) {   // none: the launches of a handle that never had a spec
+        h->sensor_on = 0;
+        return RMAV_OK;
+    }
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no sensor noise");
+    const int nS = kStateDim[h->kind];
+    for (int c = 0; c < 16; ++c) {
+        const float g = spec->sigma[c];
+        if (!(g - g == 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "every sigma of a sensor-noise spec must be finite (component %d is not)", c);
+        if (!(g >= 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "sigma[%d] = %g is negative", c, (double)g);
+        if (c >= nS && g != 0.0f) return rmav_fail(RMAV_ERR_INVALID, "sigma[%d] = %g: the kind has %d observation components, the others must be 0", c, (double)g, nS);
+    }
+    const rmav_sensor_noise_spec old = h->sensor;
+    h->sensor = *spec;
+    if (int rc = rmav_sync_sensor_dev(h)) {   // the policy kernels' copy, in stream order
+        h->sensor = old;
+        return rc;
+    }
+    h->sensor_on = 1;
+    return RMAV_OK;
+}
+
+int rmav_get_sensor_noise(rmav_handle h, rmav_sensor_noise_spec *out, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (out) *out = h->sensor;   // (the last spec set - zeros before the first - also while it is switched off)
+    if (enabled) *enabled = h->sensor_on;
+    return RMAV_OK;
+}
+
+int rmav_observe(rmav_handle h, float *obs_out, int mem, int layout) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, layout)) return rc;
+    if (!obs_out) return rmav_fail(RMAV_ERR_INVALID, "obs_out is NULL");
+    if (!h->sensor_on) return rmav_get_state(h, obs_out, mem, layout);   // no spec: the state itself
+    return write_via_host(h, obs_out, (size_t)h->n * kStateDim[h->kind] * sizeof(float), mem,
+                          [&](void *dst) { return rmav_launch_observe(h, (float *)dst, layout); });
 }
 
 int rmav_set_time_limit(rmav_handle h, int32_t max_episode_steps) {

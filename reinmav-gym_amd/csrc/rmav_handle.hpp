@@ -1,7 +1,7 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus five that only launch kernels (rmav_policy_abi.hip,
-// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus seven that only launch kernels (rmav_policy_abi.hip,
+// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip, rmav_sensor_abi.hip, rmav_sensor_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -116,7 +116,20 @@ struct rmav_env_s {
     int32_t disturb_on;
     rmav_disturbance_spec disturb;
     rmav::DisturbSpec *disturb_dev;   // the policy kernels' copy of the spec, in the arena next to reward_dev (k_set_disturbance rewrites it)
+    // sensor noise (rmav_set_sensor_noise): the spec and whether one is set.  sensor_on routes every stepping launch to the *_sn kernels -
+    // before the disturbance, which those kernels take as well (the all-zero one without a spec) - and rmav_reset's observation to k_observe.
+    // The step kernels, the one-wavefront rollouts and k_observe take the spec by value; the policy kernels read sensor_dev.
+    int32_t sensor_on;
+    rmav_sensor_noise_spec sensor;
+    rmav::SensorDev *sensor_dev;   // the policy kernels' copy of the spec, in the arena next to disturb_dev (k_set_sensor_noise rewrites it)
 };
+static_assert(sizeof(rmav_sensor_noise_spec) == 64 && sizeof(rmav::SensorArgs) == 64, "sixteen floats");
+// what the *_sn kernels and k_observe take
+inline rmav::SensorArgs sensor_args(const rmav_env_s *h) {
+    rmav::SensorArgs s{};
+    for (int c = 0; c < 16; ++c) s.sigma[c] = h->sensor.sigma[c];
+    return s;
+}
 static_assert(sizeof(rmav_disturbance_spec) == 40, "nine floats and the hold");
 // what the *_ds kernels take for a launch whose first step has the step counter t0: the wind as (lo, hi - lo), the gust block and phase of t0
 inline rmav::DisturbArgs disturb_args(const rmav_env_s *h, uint64_t t0) {
@@ -129,6 +142,17 @@ inline rmav::DisturbArgs disturb_args(const rmav_env_s *h, uint64_t t0) {
     d.v.hold = h->disturb.gust_hold;
     d.b0 = t0 / (uint64_t)h->disturb.gust_hold;
     d.phase0 = (int32_t)(t0 % (uint64_t)h->disturb.gust_hold);
+    return d;
+}
+// what the *_sn kernels take in the disturbance's place: the handle's spec, or - without one - the all-zero spec (d = +0 leaves g_vec's bits)
+// at the longest hold, so that no launch redraws a gust inside its loop
+constexpr int32_t kCalmHold = 1048576;
+inline rmav::DisturbArgs disturb_or_calm(const rmav_env_s *h, uint64_t t0) {
+    if (h->disturb_on) return disturb_args(h, t0);
+    rmav::DisturbArgs d{};
+    d.v.hold = kCalmHold;
+    d.b0 = t0 / (uint64_t)kCalmHold;
+    d.phase0 = (int32_t)(t0 % (uint64_t)kCalmHold);
     return d;
 }
 static_assert(sizeof(rmav_reward_spec) == sizeof(rmav::RewardArgs) && offsetof(rmav_reward_spec, act_ref) == offsetof(rmav::RewardArgs, act_ref) &&
@@ -155,6 +179,13 @@ inline rmav::PolicyDisturbArgs policy_disturb_args(const rmav_env_s *h, uint64_t
     const rmav::ActRuleArgs r = act_rule_args(h);
     const rmav::DisturbArgs d = disturb_args(h, t0);
     return rmav::PolicyDisturbArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev, h->disturb_dev, d.b0, d.phase0, 0};
+}
+// what the noisy policy kernels take in PolicyDisturbArgs' place: the device copy of the disturbance spec, or the calm one beside the sigmas
+inline rmav::PolicySensorArgs policy_sensor_args(const rmav_env_s *h, uint64_t t0) {
+    const rmav::ActRuleArgs r = act_rule_args(h);
+    const rmav::DisturbArgs d = disturb_or_calm(h, t0);
+    return rmav::PolicySensorArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev, h->disturb_on ? h->disturb_dev : &h->sensor_dev->calm, d.b0, d.phase0, 0,
+                                  &h->sensor_dev->sn};
 }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
@@ -364,3 +395,16 @@ RMAV_INTERNAL int rmav_launch_disturb_step(rmav_handle h, const rmav::RolloutArg
 RMAV_INTERNAL int rmav_launch_disturbance_now(rmav_handle h, float *out_dev);
 // ... and k_set_disturbance: the handle's device copy of the spec (disturb_dev), rewritten in stream order; no allocation, no synchronisation
 RMAV_INTERNAL int rmav_sync_disturb_dev(rmav_handle h);
+
+// rmav_sensor_abi.hip: the launches of a handle with sensor noise (rmav_set_sensor_noise), shaped as the disturbed ones, whose arguments
+// they take as well (a handle without a disturbance: the all-zero spec).  _rollout: ONE launch of k_rollout_sn<K, mode, time limit?, reward?>
+// (one store policy); _step: k_step_sn at bs threads per workgroup; _observe: k_observe of the current state at the handle's step counter
+// into out (device memory, nS * N floats in `layout`).  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_sensor_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_sensor_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_observe(rmav_handle h, float *out_dev, int layout);
+// rmav_sensor_policy_abi.hip: the policy-in-kernel rollout of a handle with sensor noise - k_rollout_nrm_sn, the fp32 matrix-core actor (kmode
+// ACT_POLICY_F32M; any other is RMAV_ERR_INVALID) - with rmav_launch_policy_rollout's arguments; nm is required, bt on a time-limited handle.
+RMAV_INTERNAL int rmav_launch_sensor_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
+// ... and k_set_sensor_noise: the handle's device copy of the spec (sensor_dev), rewritten in stream order; no allocation, no synchronisation
+RMAV_INTERNAL int rmav_sync_sensor_dev(rmav_handle h);

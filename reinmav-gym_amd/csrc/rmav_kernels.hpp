@@ -29,9 +29,14 @@
 
 #include "rmav_math.hpp"
 #include "rmav_disturb.hpp"
+#include "rmav_sensor.hpp"
 #include "rmav_policy.hpp"
 #include "rmav_policy_mfma.hpp"
 #include "rmav_policy_mfma32.hpp"
+
+// RMAV_ROLLOUT_SN: the sensor noise of the *_sn wrappers (rmav_set_sensor_noise; rmav_sensor.hpp) is compiled into rmav_rollout_body.inc only
+// where a wrapper sets it around its #include, as RMAV_PAIR_DS in the pair bodies: every other kernel's text is what it was.
+#define RMAV_ROLLOUT_SN 0
 
 namespace rmav {
 
@@ -357,6 +362,23 @@ struct PolicyDisturbArgs {
     uint64_t b0;
     int32_t phase0;
     int32_t _pad;
+};
+// ... and the POLICY kernels of a handle with sensor noise (k_rollout_nrm_sn): PolicyDisturbArgs with the handle's device copy of the sensor
+// spec behind it.  SensorDev is that copy (rmav_env_s::sensor_dev, rewritten in stream order by k_set_sensor_noise): the sigmas and, for
+// a handle without a disturbance, the all-zero disturbance spec ds then points at - at the longest hold, so no launch redraws a gust.
+struct SensorDev {
+    SensorArgs sn;
+    DisturbSpec calm;
+};
+struct PolicySensorArgs {
+    float noise, lo, hi;
+    int32_t k;
+    const RewardArgs *rw;
+    const DisturbSpec *ds;
+    uint64_t b0;
+    int32_t phase0;
+    int32_t _pad;
+    const SensorArgs *sn;
 };
 // where the tracked body's position and velocity sit in the state, and their dimension
 template <int K> struct RewardBody;
@@ -725,6 +747,51 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 #include "rmav_rollout_body.inc"
 }
 
+// The one-wavefront kernels of a handle with sensor noise (rmav_set_sensor_noise; SensorArgs in rmav_sensor.hpp): k_rollout_ds's body and
+// argument list - a handle without a disturbance passes the all-zero spec, whose d = +0 leaves g_vec's bits - with the spec behind it.  Every
+// stored observation row is fma(sigma, z, s) of the state after the step and its reset, z of the step counter after the step; nothing
+// else reads the noise.  One store policy.
+template <int K, int MODE, bool TL, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_sn(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn) {
+    constexpr int ST = ST_DEFAULT;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, DS = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "noisy launches run the one-wavefront kernels");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_ds whose nets - the actor and the value net of every step, of the
+// bootstrap term and of value_out[n_steps] - read the noisy observation, in front of the normaliser, and whose stored obs rows hold it.
+// The dynamics, the reward and the state stored in place stay true.  The specs are read through the handle's device copies.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_sn(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicySensorArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
 // reset_state<K> for the lanes of a wavefront that need it, computed cooperatively (all 64 lanes must be active).
 // Philox4x32-10 is ~20 quarter-rate 32x32->64 multiplies per call and reset_state needs ceil(nS / 4) calls (the counter
 // word c3 selects the block of four components); executed by a whole wavefront for the one or two lanes whose env has
@@ -797,12 +864,16 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // DR: the handle has a parameter range (dr; k_step_dr): a finishing lane draws and stores the constants of its new episode.
 // RW: the handle has a tracking reward (rw; k_step_rw, on FS's loop - k = 1 without a skip): reward_rw in the literal's place.
 // DS: the handle has a disturbance (ds; k_step_ds): the lane's gravity is g_vec + d of this step; the controller's constants keep g_vec.
-template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false, bool DS = false>
+// SN: the handle has sensor noise (sn; k_step_sn): obs_out and final_obs are fma(sigma, z, s) with ONE z, that of the step counter after
+// this step (a.t0 + 1); the state stored in place stays the true one.
+template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false, bool DS = false,
+          bool SN = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
                                           const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
                                           [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{},
-                                          [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}) {
+                                          [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}, [[maybe_unused]] const SensorArgs &sn = SensorArgs{}) {
     static_assert(!RW || FS, "the tracking reward is evaluated in the sub-step loop");
+    static_assert(!SN || (DS && FIN), "the noisy step is cut from the disturbed body");
     static_assert(!DS || (FS && DR && !CTRL), "the disturbed step is cut from the most general body: the running reset index, eagerly; k_control behind it");
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
     static_assert(!(FS && LAZY), "the frame-skip loop runs the reward machine per sub-step: every lane's record, eagerly");
@@ -927,6 +998,11 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     } else {
         Env<K>::step(s, act, pl, dist, done);
     }
+    // SN: the noise of every observation this step emits (wave-uniform: skipped when the caller asked for none)
+    [[maybe_unused]] float sn_z[SN ? NS : 1];
+    if constexpr (SN) {
+        if (a.obs_out || fa.final_obs) sensor_draw<NS>(a.seed, a.env_base + (uint64_t)li, a.t0 + 1u, sn_z);
+    }
     // Where and how the step's outputs are stored (same values on both paths): reward, done, running return
     auto store_scalars = [&](float r_, bool done_, float er_) {
         if (a.rew_out) buf_st_aux<AUX>(make_rsrc(a.rew_out), off, 0, r_);
@@ -940,7 +1016,19 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
 #pragma unroll
         for (int c = 0; c < NS; ++c) buf_st_aux<AUX>(r_state, off, (uint32_t)c * col, s[c]);
         if (a.obs_out) {
-            if (aos) {
+            if constexpr (SN) {   // the observation of the state just stored: the z the terminal observation took
+                float o[NS];
+                sensor_apply(sn, sn_z, s, o);
+                if (aos) {
+                    float *dst = a.obs_out + (int64_t)li * NS;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) dst[c] = o[c];
+                } else {
+                    const rsrc_t ro = make_rsrc(a.obs_out);
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) buf_st_aux<AUX>(ro, off, (uint32_t)c * tcol, o[c]);
+                }
+            } else if (aos) {
                 float *dst = a.obs_out + (int64_t)li * NS;
 #pragma unroll
                 for (int c = 0; c < NS; ++c) dst[c] = s[c];
@@ -1010,7 +1098,19 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
         // flag of every lane
         if constexpr (FIN) {
             if (fa.final_obs && done) {
-                if (aos) {
+                if constexpr (SN) {   // the terminal observation: the pre-reset state under the step's z
+                    float o[NS];
+                    sensor_apply(sn, sn_z, s, o);
+                    if (aos) {
+                        float *dst = fa.final_obs + (int64_t)li * NS;
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) dst[c] = o[c];
+                    } else {
+                        const rsrc_t rf = make_rsrc(fa.final_obs);
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) buf_st_aux<AUX>(rf, off, (uint32_t)c * tcol, o[c]);
+                    }
+                } else if (aos) {
                     float *dst = fa.final_obs + (int64_t)li * NS;
 #pragma unroll
                     for (int c = 0; c < NS; ++c) dst[c] = s[c];
@@ -1224,6 +1324,44 @@ __global__ __launch_bounds__(kBlock) void k_disturbance_now(float *out, int64_t 
     gust_draw(ds.spec(), seed, env_base + (uint64_t)i, ds.b0, q);
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[(int64_t)c * n + i] = (c < D) ? w[c < D ? c : 0] + q[c < D ? c : 0] : 0.0f;
+}
+
+// The single-step kernel of a handle with sensor noise (rmav_set_sensor_noise): k_step_ds's body and argument list with the spec behind
+// it.  obs_out and final_obs are noisy (one z: that of the step counter after the step); the state stored in place is the true one.
+template <int K, bool TL, bool RW>
+__global__ __launch_bounds__(kBlock) void k_step_sn(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn);
+}
+
+// rmav_observe: the observation of every env's current state at the step counter b, out nS * n floats, feature-major or - aos - batch-major.
+// Every route that emits an observation stores the bits this kernel gives right after it.
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_observe(const float *state, float *out, int64_t n, uint64_t seed, uint64_t env_base, uint64_t b, uint32_t aos,
+                                                    const SensorArgs sn) {
+    constexpr int NS = Dims<K>::NS;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s[NS], z[NS], o[NS];
+#pragma unroll
+    for (int c = 0; c < NS; ++c) s[c] = state[(int64_t)c * n + i];
+    sensor_draw<NS>(seed, env_base + (uint64_t)i, b, z);
+    sensor_apply(sn, z, s, o);
+#pragma unroll
+    for (int c = 0; c < NS; ++c) {
+        if (aos) out[i * NS + c] = o[c];
+        else out[(int64_t)c * n + i] = o[c];
+    }
 }
 
 // reset() of every env

@@ -68,6 +68,13 @@
                 if (rew_out) rew_out += n;
                 if (done_out) done_out += n;
             }
+#if RMAV_PAIR_SN   // the observation of the launch's first state: the row the actor wavefront has left in half 1 in front of barrier B
+            else {
+                const float *row = otile + PT::O_HALF;
+#pragma unroll
+                for (int c = 0; c < NS; ++c) s[c] = row[c * 64];
+            }
+#endif
             float x[16];
             if constexpr (NORM) {
                 norm_state16<NS>(ntab, s, x);
@@ -122,6 +129,9 @@
 
     // ---- actor: policy net, action, dynamics, bookkeeping --------------------------------------------------------------
 #include "rmav_pair_env_load.inc"   // fin_*, er, el, sb, rc, pl / p, tenv, spare, have_spare, pol_std
+#if RMAV_PAIR_SN   // the observation of the launch's first state (step counter t0), where step "-1" would have left its row: half 1
+    sensor_store_row<NS>(sn, a.seed, env_id, a.t0, s, otile + PT::O_HALF);
+#endif
     __syncthreads();                                                  // B: Z(0) is in the tile
     for (int32_t k = 0; k < T; ++k) {
         float z[NA];
@@ -131,9 +141,19 @@
             for (int c = 0; c < NA; ++c) z[c] = zt[c * 64];
         }
         float x[16];
+#if RMAV_PAIR_SN   // the policy net reads the observation this lane stored as the previous row (its own words of the tile: program order)
+        if constexpr (NORM) {
+            float o[NS];
+            const float *prev = otile + ((k - 1) & 1) * PT::O_HALF;
+#pragma unroll
+            for (int c = 0; c < NS; ++c) o[c] = prev[c * 64];
+            norm_state16<NS>(ntab, o, x);
+        } else {
+#else
         if constexpr (NORM) {
             norm_state16<NS>(ntab, s, x);
         } else {
+#endif
 #pragma unroll
             for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
         }
@@ -153,8 +173,12 @@
                 using PB = PairBootTile<NS, NA>;
                 if (__ballot(trunc) != 0) {   // wave-uniform
                     float *fin = tile + PB::FIN + (k & 1) * PB::FIN_HALF + lane;
+#if RMAV_PAIR_SN   // the terminal OBSERVATION: the pre-reset state under the z of this step's row
+                    sensor_store_row<NS>(sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, fin);
+#else
 #pragma unroll
                     for (int c = 0; c < NS; ++c) fin[c * 64] = s[c];
+#endif
                 }
                 otile[(k & 1) * PT::O_HALF + PT::DONE] = trunc ? 2.0f : (done ? 1.0f : 0.0f);
             }

@@ -59,8 +59,14 @@
         }
 #endif
         float *row = otile + (k & 1) * PT::O_HALF;
+#if RMAV_PAIR_SN   // the *_sn wrappers (kernel argument sn: SensorArgs): the row holds the OBSERVATION of the state after the step and its reset,
+                   // under the z of the step counter after the step - computed once, by the lane that owns the env; both nets of step k + 1
+                   // and the trajectory store read it from the row.  s stays the true state.
+        sensor_store_row<NS>(sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, row);
+#else
 #pragma unroll
         for (int c = 0; c < NS; ++c) row[c * 64] = s[c];
+#endif
         row[PT::REW] = r;
         if constexpr (!BOOT) row[PT::DONE] = done ? 1.0f : 0.0f;
 #pragma unroll

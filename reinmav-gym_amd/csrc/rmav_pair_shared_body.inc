@@ -135,6 +135,13 @@
     const bool vvalid = h && (uint64_t)(gi - 32u) < (uint64_t)n;
     const uint32_t voff = (gi - 32u) * 4u;
     float *val_out = a.val_out;
+#if RMAV_PAIR_SN   // the *_sn wrappers: the net reads the OBSERVATION this lane stored as the previous row (its own words of the tile: program
+                   // order), not the true state in s; sn_half names that row's half
+    int sn_half = 1;
+#define RMAV_SOBS(c) (otile[sn_half * PT::O_HALF + (c) * 64])
+#else
+#define RMAV_SOBS(c) (s[c])
+#endif
     auto eval_tile0 = [&](float (&o4)[4]) {   // lane (n, h): components [8h, 8h + 8) of env n - its own for h = 0, lane n's for h = 1
         float x[8];
         [[maybe_unused]] const float *nt = nullptr;
@@ -145,13 +152,13 @@
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float lo = (j < NS) ? s[j] : 0.0f;
+            float lo = (j < NS) ? RMAV_SOBS(j) : 0.0f;
             float hi = 0.0f;
             if constexpr (NORM) {   // normalised by the lane that owns the env, before the exchange
                 if (j < NS) lo = norm1(nt, j, lo, nclip);
-                if (8 + j < NS) hi = xor32(norm1(nt, 8 + j, s[8 + j], nclip));
+                if (8 + j < NS) hi = xor32(norm1(nt, 8 + j, RMAV_SOBS(8 + j), nclip));
             } else {
-                if (8 + j < NS) hi = xor32(s[8 + j]);   // lanes 32..63 receive lane - 32's component 8 + j  (folded: NS is a constant)
+                if (8 + j < NS) hi = xor32(RMAV_SOBS(8 + j));   // lanes 32..63 receive lane - 32's component 8 + j  (folded: NS is a constant)
             }
             x[j] = h ? hi : lo;
         }
@@ -161,12 +168,19 @@
     };
     {   // the initial obs of the pair's envs, for B's first evaluation: the obs half step "-1" would have written
         float *row = otile + PT::O_HALF;
+#if RMAV_PAIR_SN   // ... the observation of the launch's first state, at the step counter t0
+        sensor_store_row<NS>(sn, a.seed, env_id, a.t0, s, row);
+#else
 #pragma unroll
         for (int c = 0; c < NS; ++c) row[c * 64] = s[c];
+#endif
     }
     __syncthreads();                                                      // P
     for (int32_t k = 0; k < T; ++k) {
         float o4[4];
+#if RMAV_PAIR_SN
+        sn_half = (k - 1) & 1;
+#endif
         eval_tile0(o4);
         __syncthreads();                                                  // X(k)
         float act[NA];
@@ -188,8 +202,14 @@
                 const uint64_t tm = __ballot(trunc);
                 if (tm != 0) {   // wave-uniform
                     float *fin = tile + SB::FIN + (k & 1) * SB::FIN_HALF + lane;
+#if RMAV_PAIR_SN   // the terminal OBSERVATION: the pre-reset state under the z of this step's row; both wavefronts evaluate the net on it
+                    sensor_store_row<NS>(sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, fin);
+#define RMAV_SFIN(c) (fin[(c) * 64])
+#else
 #pragma unroll
                     for (int c = 0; c < NS; ++c) fin[c * 64] = s[c];
+#define RMAV_SFIN(c) (s[c])
+#endif
                     float xf[8], u4[4];
                     [[maybe_unused]] const float *nt = nullptr;
                     [[maybe_unused]] float nclip = 0.0f;
@@ -199,13 +219,13 @@
                     }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
-                        float lo = (j < NS) ? s[j] : 0.0f;
+                        float lo = (j < NS) ? RMAV_SFIN(j) : 0.0f;
                         float hi = 0.0f;
                         if constexpr (NORM) {
                             if (j < NS) lo = norm1(nt, j, lo, nclip);
-                            if (8 + j < NS) hi = xor32(norm1(nt, 8 + j, s[8 + j], nclip));
+                            if (8 + j < NS) hi = xor32(norm1(nt, 8 + j, RMAV_SFIN(8 + j), nclip));
                         } else {
-                            if (8 + j < NS) hi = xor32(s[8 + j]);
+                            if (8 + j < NS) hi = xor32(RMAV_SFIN(8 + j));
                         }
                         xf[j] = h ? hi : lo;
                     }
@@ -221,6 +241,11 @@
     }
     {
         float o4[4];
+#if RMAV_PAIR_SN
+        sn_half = (T - 1) & 1;
+#endif
         eval_tile0(o4);                                                   // bootstrap values of envs 0..31
     }
+#undef RMAV_SOBS
+#undef RMAV_SFIN
 #include "rmav_pair_epilogue.inc"   // state and record write-back, episode totals, statistics-exchange snapshot

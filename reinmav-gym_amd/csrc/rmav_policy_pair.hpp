@@ -37,6 +37,9 @@
 // RMAV_PAIR_DS: likewise the wind / gust disturbance of the *_ds wrappers (rmav_set_disturbance): the per-lane wind and gust, the lane's gravity
 // g_vec + d in front of every agent step, the new wind at a reset, the wave-uniform place in the gust sequence.
 #define RMAV_PAIR_DS 0
+// RMAV_PAIR_SN: likewise the sensor noise of the *_sn wrappers (rmav_set_sensor_noise; rmav_sensor.hpp): the rows of the output tile hold the
+// noisy observation - computed once per step by the lane that owns the env -, both nets read it from there, the terminal area likewise.
+#define RMAV_PAIR_SN 0
 
 namespace rmav {
 
@@ -365,6 +368,34 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_ds(cons
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 0
 }
+// ... and of a handle with sensor noise (rmav_set_sensor_noise; rmav_sensor.hpp): k_rollout_pair_ds - a handle without a disturbance passes
+// the calm spec - whose output rows hold the noisy observation: the actor wavefront computes it once per step, both nets read it.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_sn(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicySensorArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 0
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
 
 // ---- one shared 2 x 64 trunk with a mean head and a value head (RMAV_POLICY_F16_SHARED) -------------------------------------------
 //
@@ -584,6 +615,32 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
 #undef RMAV_PAIR_DS
 #define RMAV_PAIR_DS 1
 #include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with sensor noise: k_rollout_pair_shared_ds whose output rows hold the noisy observation (see k_rollout_pair_sn).
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_sn(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicySensorArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 0
 #undef RMAV_PAIR_DS
 #define RMAV_PAIR_DS 0
 #undef RMAV_PAIR_DR

@@ -612,12 +612,25 @@
             __syncthreads();                                       // B0x (waits for the read above: lgkmcnt(0) precedes s_barrier)
         }
 
+#if RMAV_ROLLOUT_SN   // the *_sn wrappers: sn_o is the observation of s - what the nets read and the stored row holds.  Drawn ONCE per step, behind
+                      // the dynamics and the reset of step k for the step counter t0 + k + 1: stored as row k, read by the actor of step k + 1
+                      // and, after the last step, by the value net of value_out[n_steps]; the prologue draw at t0 serves step 0.
+#define RMAV_OBS sn_o
+        float sn_o[NS];
+        if constexpr (is_policy(MODE)) {
+            float sn_z[NS];
+            sensor_draw<NS>(a.seed, env_id, a.t0, sn_z);
+            sensor_apply(sn, sn_z, s, sn_o);
+        }
+#else
+#define RMAV_OBS s
+#endif
         for (int32_t k = 0; k < a.n_steps; ++k) {
             float act[NA];
             if constexpr (is_mfma_policy(MODE)) {
                 float x[16], mean[4], val0, z[4];
                 if constexpr (NORM) {
-                    norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, s, x);
+                    norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, RMAV_OBS, x);
                 } else {
 #pragma unroll
                     for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
@@ -793,9 +806,22 @@
                     float bv = 0.0f;
                     if (__ballot(trunc) != 0) {
                         float xf[16];
+#if RMAV_ROLLOUT_SN   // V of the terminal OBSERVATION: the pre-reset state under the z of this step's row (a second evaluation of the draw, on
+                      // about one step in max_steps - instead of NS registers of z held across the reset)
+                        if constexpr (NORM) {
+                            float sf[NS];
+                            {
+                                float sn_z[NS];
+                                sensor_draw<NS>(a.seed, env_id, a.t0 + (uint64_t)k + 1u, sn_z);
+                                sensor_apply(sn, sn_z, s, sf);
+                            }
+                            norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, sf, xf);
+                        } else {
+#else
                         if constexpr (NORM) {
                             norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, s, xf);
                         } else {
+#endif
 #pragma unroll
                             for (int c = 0; c < 16; ++c) xf[c] = (c < NS) ? s[c] : 0.0f;
                         }
@@ -894,6 +920,27 @@
                     for (int c = 0; c < NA; ++c) row[ST_::ACT + c * 64] = act[c];
                 }
                 if constexpr (split_feeds_actions(MODE)) __syncthreads();   // B(k + 1): O(k) handed over, A(k + 2) may be written
+#if RMAV_ROLLOUT_SN   // the *_sn wrappers (kernel argument sn: SensorArgs): the observation of the state after this step and its reset, under
+                      // the z of the step counter after the step; s itself - the dynamics, the reward, the state stored in place - stays true
+            } else if (is_policy(MODE) || obs_out) {   // (an actor reads the observation whether or not the caller stores it)
+                {
+                    float sn_z[NS];
+                    sensor_draw<NS>(a.seed, env_id, a.t0 + (uint64_t)k + 1u, sn_z);
+                    sensor_apply(sn, sn_z, s, sn_o);
+                }
+                if (obs_out) {
+                    if (aos) {
+                        float *dst = obs_out + (int64_t)li * NS;
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) dst[c] = sn_o[c];
+                    } else {
+                        const rsrc_t ro = make_rsrc(obs_out);
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) buf_st_aux<AUX>(ro, off, (uint32_t)c * tcol, sn_o[c]);
+                    }
+                    obs_out += (int64_t)NS * tn;
+                }
+#else
             } else if (obs_out) {
                 if (ST == ST_AOS_LDS && full_wave) {
                     // all 64 lanes are here (full_wave is wave-uniform); LDS executes one wavefront's
@@ -920,6 +967,7 @@
                     for (int c = 0; c < NS; ++c) buf_st_aux<AUX>(ro, off, (uint32_t)c * tcol, s[c]);
                 }
                 obs_out += (int64_t)NS * tn;
+#endif
             }
             if (!SPLIT && rew_out) {
                 buf_st_aux<AUX>(make_rsrc(rew_out), off, 0, r);
@@ -943,7 +991,7 @@
         if constexpr (is_mfma_policy(MODE)) {   // bootstrap value of the state the rollout ends in
             float x[16], mean[4], val0;
             if constexpr (NORM) {
-                norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, s, x);
+                norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, RMAV_OBS, x);
             } else {
 #pragma unroll
                 for (int c = 0; c < 16; ++c) x[c] = (c < NS) ? s[c] : 0.0f;
@@ -1033,3 +1081,4 @@
         if ((threadIdx.x & 63u) == 0 && valid)
             __hip_atomic_store(a.xarrive + (HALF ? (ge >> 5) : (ge >> 6)), a.xseq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+#undef RMAV_OBS

@@ -73,6 +73,12 @@ class DisturbanceSpec(C.Structure):
     _fields_ = [("wind_lo", C.c_float * 3), ("wind_hi", C.c_float * 3), ("gust", C.c_float * 3), ("gust_hold", C.c_int32)]
 
 
+class SensorNoiseSpec(C.Structure):
+    """``rmav_sensor_noise_spec``."""
+
+    _fields_ = [("sigma", C.c_float * 16)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -155,6 +161,9 @@ PROTOTYPES = {
     "rmav_set_disturbance": (C.c_int, [C.c_void_p, C.POINTER(DisturbanceSpec)]),
     "rmav_get_disturbance": (C.c_int, [C.c_void_p, C.POINTER(DisturbanceSpec), C.POINTER(C.c_int32)]),
     "rmav_disturbance_now": (C.c_int, [C.c_void_p, _fp, C.c_int]),
+    "rmav_set_sensor_noise": (C.c_int, [C.c_void_p, C.POINTER(SensorNoiseSpec)]),
+    "rmav_get_sensor_noise": (C.c_int, [C.c_void_p, C.POINTER(SensorNoiseSpec), C.POINTER(C.c_int32)]),
+    "rmav_observe": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

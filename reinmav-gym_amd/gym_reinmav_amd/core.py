@@ -282,6 +282,75 @@ def check_disturbance(disturbance, kind=None):
     return disturbance
 
 
+class SensorNoise:
+    """Gaussian noise on every observation a handle emits (``rmav_set_sensor_noise``, include/rmav.h), drawn inside the kernels::
+
+        o_c = fma(sigma_c, z_c, s_c)        z standard normal per (seed, env id, step counter, component)
+
+    ``sigma``: one standard deviation for every component, or a sequence of ``nS`` (one per observation component), each finite and
+    ``>= 0``.  The dynamics, the rewards, ``done``, the controller and ``get_state`` read the true state.  Types, lengths and finiteness
+    are checked here, before the library is reached."""
+
+    MAX_DIM = 16
+
+    def __init__(self, sigma=0.0):
+        if isinstance(sigma, (int, float, np.integer, np.floating)) and not isinstance(sigma, (bool, np.bool_)):
+            self.sigma = _finite_float("sigma", sigma)
+            sig = (self.sigma,)
+        else:
+            if isinstance(sigma, (str, bytes)) or not hasattr(sigma, "__len__"):
+                raise TypeError(f"sigma must be a standard deviation or a sequence of nS of them, got {sigma!r}")
+            if not 1 <= len(sigma) <= self.MAX_DIM:
+                raise ValueError(f"sigma must have nS (1 .. {self.MAX_DIM}) components, got {len(sigma)}")
+            self.sigma = sig = tuple(_finite_float(f"sigma[{i}]", x) for i, x in enumerate(sigma))
+        for i, v in enumerate(sig):
+            if v < 0:
+                raise ValueError(f"sigma[{i}] must be >= 0, got {v!r}")
+
+    @classmethod
+    def parse(cls, text: str) -> "SensorNoise":
+        """``"0.01"`` (every component) or ``"0.01,0.01,..."`` (one per component): the form of ``examples/train_ppo2.py --sensor-noise``."""
+        if not isinstance(text, str):
+            raise TypeError(f"a sensor-noise string is wanted, got {text!r}")
+        try:
+            nums = [float(x) for x in text.split(",")]
+        except ValueError:
+            raise ValueError(f"--sensor-noise wants SIGMA or SIGMA,SIGMA,... (one per observation component); got {text!r}") from None
+        return cls(nums[0] if len(nums) == 1 else tuple(nums))
+
+    def check_kind(self, kind: int):
+        """The length against the kind, which the constructor does not know."""
+        if kind == A.REINMAV:
+            raise ValueError("ReinmavEnv takes no sensor noise")
+        if not isinstance(self.sigma, float) and len(self.sigma) != A.STATE_DIM[kind]:
+            raise ValueError(f"sigma has {len(self.sigma)} components, {A.KIND_NAMES[kind]} observes {A.STATE_DIM[kind]}")
+
+    def spec(self, kind: int) -> "A.SensorNoiseSpec":
+        """``rmav_sensor_noise_spec`` for a handle of ``kind`` (components past ``nS`` are 0)."""
+        self.check_kind(kind)
+        nS = A.STATE_DIM[kind]
+        sig = (self.sigma,) * nS if isinstance(self.sigma, float) else self.sigma
+        return A.SensorNoiseSpec((C.c_float * 16)(*(tuple(sig) + (0.0,) * (16 - nS))))
+
+    @classmethod
+    def from_spec(cls, s: "A.SensorNoiseSpec", kind: int) -> "SensorNoise":
+        return cls(tuple(s.sigma[:A.STATE_DIM[kind]]))
+
+    def __repr__(self):
+        return f"SensorNoise(sigma={self.sigma!r})"
+
+
+def check_sensor_noise(sensor_noise, kind=None):
+    """``sensor_noise=`` as the constructors take it: None (exact observations) or a :class:`SensorNoise`; anything else is refused here."""
+    if sensor_noise is None:
+        return None
+    if not isinstance(sensor_noise, SensorNoise):
+        raise TypeError(f"sensor_noise must be None or a SensorNoise, got {sensor_noise!r}")
+    if kind is not None:
+        sensor_noise.check_kind(kind)
+    return sensor_noise
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
@@ -289,7 +358,7 @@ class BatchedQuadrotor:
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
                  randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None,
-                 disturbance: Optional[Disturbance] = None):
+                 disturbance: Optional[Disturbance] = None, sensor_noise: Optional[SensorNoise] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
@@ -302,11 +371,15 @@ class BatchedQuadrotor:
         None = the reference's reward.
 
         ``disturbance``: a :class:`Disturbance` (per-episode wind, held gusts; :attr:`disturbance`), drawn and applied inside the kernels;
-        None = still air."""
+        None = still air.
+
+        ``sensor_noise``: a :class:`SensorNoise` (Gaussian noise on every observation; :attr:`sensor_noise`), drawn inside the kernels;
+        None = exact observations."""
         frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         reward = check_reward(reward, self.kind)
         disturbance = check_disturbance(disturbance, self.kind)
+        sensor_noise = check_sensor_noise(sensor_noise, self.kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
         self.nS, self.nA = A.STATE_DIM[self.kind], A.ACTION_DIM[self.kind]
@@ -336,6 +409,8 @@ class BatchedQuadrotor:
             self.reward = reward
         if disturbance is not None:
             self.disturbance = disturbance
+        if sensor_noise is not None:
+            self.sensor_noise = sensor_noise
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -438,6 +513,32 @@ class BatchedQuadrotor:
         if out is None:
             out = torch.empty((3, self.num_envs), dtype=torch.float32, device=f"cuda:{self.device}")
         A.check(self._lib.rmav_disturbance_now(self._h, self._ptr(out), A.DEVICE))
+        return out
+
+    @property
+    def sensor_noise(self) -> Optional[SensorNoise]:
+        """The :class:`SensorNoise` in force (``rmav_get_sensor_noise``; values as the kernels hold them in fp32, one per component), or
+        None: exact observations.  Assignable at any time (host state only): launches enqueued afterwards see it."""
+        s, on = A.SensorNoiseSpec(), C.c_int32()
+        A.check(self._lib.rmav_get_sensor_noise(self._h, C.byref(s), C.byref(on)))
+        return SensorNoise.from_spec(s, self.kind) if on.value else None
+
+    @sensor_noise.setter
+    def sensor_noise(self, sensor_noise: Optional[SensorNoise]):
+        if check_sensor_noise(sensor_noise, self.kind) is None:
+            A.check(self._lib.rmav_set_sensor_noise(self._h, None))
+        else:
+            A.check(self._lib.rmav_set_sensor_noise(self._h, C.byref(sensor_noise.spec(self.kind))))
+
+    def observe(self, out=None, layout: str = "aos", device_out: bool = False):
+        """The observation of every env's current state (``rmav_observe``): what the last operation emitted, bit for bit; on an env
+        without :attr:`sensor_noise`, :meth:`get_state`.  ``out``: a preallocated array or device tensor of the layout's shape."""
+        if out is None:
+            out = self._new(self._shape(self.nS, layout), np.float32, device_out)
+            mem = A.DEVICE if device_out else A.HOST
+        else:
+            out, mem = self._in(out, self._shape(self.nS, layout)) if _is_tensor(out) else (out, A.HOST)
+        A.check(self._lib.rmav_observe(self._h, self._ptr(out), mem, _layout(layout)))
         return out
 
     def set_policy_action_rule(self, deterministic: bool = False, clip=None):

@@ -139,6 +139,11 @@ class RolloutCollector:
         One more policy forward per step, no host synchronisation: ``graph=True`` still captures (the env's ``step_count`` then stays
         where it was at the capture: the replayed launches carry their episode clock with them, see ``_capture``)."""
         assert env.auto_reset, "rollouts need VecEnv semantics (auto-reset)"
+        if graph and getattr(env, "sensor_noise", None) is not None:
+            # (a captured launch keeps the step counter it was captured with - include/rmav.h - and the sensor noise is a function of it:
+            # every replay would draw the same noise per env and step of the rollout)
+            raise ValueError("graph=True on an env with sensor_noise= would replay one noise pattern: every captured launch keeps its step "
+                             "counter; collect without a graph")
         self.env, self.policy, self.T = env, policy, int(nsteps)
         det, lo, hi = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
         self.deterministic = bool(det)
@@ -161,7 +166,7 @@ class RolloutCollector:
         self.rew = torch.empty((T, N), **f32)
         self.done = torch.empty((T, N), dtype=torch.uint8, device=dev)
         self._act_env = torch.empty((nA, N), **f32) if self.clip is not None else None   # what the env is stepped with
-        self.obs[0].copy_(env.get_state(layout="soa", device_out=True))
+        self.obs[0].copy_(env.observe(layout="soa", device_out=True))   # (get_state's bits on an env without sensor noise)
         self._graph = None
         if graph:
             self._capture()
@@ -196,7 +201,7 @@ class RolloutCollector:
         env = self.env
         side = torch.cuda.Stream(device=env.device)
         side.wait_stream(torch.cuda.current_stream(env.device))
-        state = env.get_state(layout="soa", device_out=True)
+        state = env.observe(layout="soa", device_out=True)   # the observation the first action is computed from
         t0 = env.step_count
         with torch.cuda.stream(side):
             # warm-up (allocator, lazy inits of the torch ops) on a scratch env of the same shape, so that the
@@ -539,6 +544,8 @@ class FusedPolicyCollector:
                 refuse("an env with reward=", "tracking-reward")
             if getattr(env, "disturbance", None) is not None:
                 refuse("an env with disturbance=", "disturbed")
+        if not has_variants and getattr(env, "sensor_noise", None) is not None:
+            refuse("an env with sensor_noise=", "sensor-noise")
         self._rule = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
         if not has_variants and self._rule != (0, -math.inf, math.inf):
             refuse("deterministic= / clip_actions=", "action-rule")
@@ -567,7 +574,7 @@ class FusedPolicyCollector:
         self._packer = _PolicyPacker(policy, env.nS, actor)
         assert self._packer.n_out == n_w, (self._packer.n_out, n_w)
         if store_trajectory:
-            self.obs[0].copy_(env.get_state(layout="soa", device_out=True))
+            self.obs[0].copy_(env.observe(layout="soa", device_out=True))   # (get_state's bits on an env without sensor noise)
         # The weight repack before every rollout: one gather launch behind the C ABI (rmav_pack_policy).  As ~8 dependent torch
         # launches (cat, gather, bf16 conversion, cat, copy) it cost ~38 us of a 0.21 ms rollout at 65 536 envs x 32 steps; a
         # hipGraph of those launches replayed no faster (the dependent-launch floor, not the host, is what they cost).

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Compare the instruction streams of the kernels of two `make asm` outputs: every listing build/<unit>.gfx950.s of each directory,
 by symbol over their union - a kernel that moved to another translation unit is neither missing nor added.  A symbol that two listings
-of one directory define is an error (the internal-linkage `_ZN4rmavL...` helpers excepted: every unit that includes their header has a
-copy, which is compared with the copy of the unit of the same name; a copy less is reported, not counted as missing).
+of one directory define is an error, with two exceptions: the internal-linkage `_ZN4rmavL...` helpers, and functions no listing exports
+(non-inlined device function templates such as `mlp_mfma32`, which every unit whose kernels call them instantiates).  Every unit has a
+copy of such a function, which is compared with the copy of the unit of the same name; a copy less is reported, not counted as missing.
 
     python tools/isa_compare.py OLD_DIR NEW_DIR
 
@@ -50,19 +51,31 @@ def kernels(path):
     return out
 
 
-def _local(symbol):
-    return symbol.startswith("_ZN4rmavL")   # internal linkage: every unit that includes its header has a copy of its own
+def _local(symbol, shared=()):
+    """internal linkage (every unit that includes its header has a copy of its own), or a function that several units of one directory
+    define and none exports - a non-inlined device function template such as mlp_mfma32: keyed by (unit, symbol), compared unit to unit"""
+    return symbol.startswith("_ZN4rmavL") or symbol in shared
 
 
 def directory(path):
-    """{symbol: (unit, body)} over every listing of a build directory; an internal-linkage helper is keyed by (unit, symbol)"""
-    out = {}
+    """{symbol: (unit, body)} over every listing of a build directory; a per-unit function (see _local) is keyed by (unit, symbol)"""
+    per_unit = {}
     for f in sorted(glob.glob(os.path.join(path, "*.gfx950.s"))):
-        unit = os.path.basename(f)[:-len(".gfx950.s")]
-        for k, body in kernels(f).items():
-            if not _local(k) and k in out:
+        per_unit[os.path.basename(f)[:-len(".gfx950.s")]] = (kernels(f), open(f).read())
+    # functions that more than one unit defines and none exports (no .globl / .weak NAME: the backend has internalised every copy, as it
+    # does with a device function that only the unit's own kernels call); an exported symbol - every kernel - defined twice stays an error
+    count, exported = {}, set()
+    for unit, (ks, txt) in per_unit.items():
+        exported |= set(re.findall(r"^\s*\.(?:globl|weak)\s+(\w+)\s*$", txt, flags=re.M))
+        for k in ks:
+            count[k] = count.get(k, 0) + 1
+    shared = {k for k, c in count.items() if c > 1 and k not in exported}
+    out = {}
+    for unit, (ks, _) in per_unit.items():
+        for k, body in ks.items():
+            if not _local(k, shared) and k in out:
                 sys.exit(f"ERROR {path}: {k} is defined in {out[k][0]} and in {unit}")
-            out[(unit, k) if _local(k) else k] = (unit, body)
+            out[(unit, k) if _local(k, shared) else k] = (unit, body)
     if not out:
         sys.exit(f"ERROR {path}: no *.gfx950.s listing with a function in it")
     return out
@@ -78,6 +91,9 @@ def main():
     name = lambda key: key[1] if isinstance(key, tuple) else key
     new_names = {name(key) for key in new}
     for key, (unit, body) in sorted(old.items(), key=str):
+        if key not in new:   # keyed per unit on one side only: a function that a second unit defines on the other side
+            alt = (unit, name(key)) if not isinstance(key, tuple) else name(key)
+            key = alt if alt in new else key
         if key not in new:
             # a unit's copy of an internal-linkage helper that another unit still defines is a copy less, not a kernel less
             if isinstance(key, tuple) and name(key) in new_names:
