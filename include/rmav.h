@@ -524,6 +524,54 @@ int rmav_set_sensor_noise(rmav_handle h, const rmav_sensor_noise_spec *spec);   
 int rmav_get_sensor_noise(rmav_handle h, rmav_sensor_noise_spec *out, int32_t *enabled);   /* either pointer may be NULL */
 int rmav_observe(rmav_handle h, float *obs_out, int mem, int layout);   /* nS*N floats: the observation of the current state at b = t */
 
+/* ---- actuator lag: a first-order motor model between the commanded action and the dynamics -----------------------------------------
+ * With a spec set every env of a quadrotor handle carries an actuator state m[nA] in fp32, and the dynamics read m, not the commanded
+ * action u.  Per ordinary dynamics step (every sub-step of a frame skip), per component c:
+ *     m_c = fma(alpha_c, u_c, beta_c * m_c)      fp32; the product beta_c * m_c is rounded on its own, then one fma
+ *     (s, dist, term) = step(s, m)
+ * alpha_c = 1 - exp(-dt / tau_c) and beta_c = exp(-dt / tau_c): the host computes both in fp64 from the spec's tau_c (seconds) and the
+ * rmav_params.dt in force when the launch is enqueued, rounds each to fp32 once and passes them to the kernels as values;
+ * rmav_set_params with a new dt re-derives them for later launches.  tau_c = 0 gives alpha = 1, beta = 0 and m_c = fma(1, u_c, 0 * m_c)
+ * = u_c: a handle whose every tau is 0 stores the bits of a handle without a spec (a -0.0 action may act as +0.0, as sigma = 0 of the
+ * sensor noise).  No random stream is involved: the RNG table above is unchanged.
+ *   - u is the action handed to the dynamics without the feature: the caller's or the random action, the controller's in all its forms
+ *     (RMAV_ACT_CONTROLLER, rmav_control_step), and for the policy rollouts the action after the action rule's clip.  For the 2-D kinds the
+ *     filter acts on the raw action; thrust_scale and clamp_thrust stay inside the step and act on m.
+ *   - nothing else reads m: stored actions, logp and the tracking reward's action cost c (still once per agent step) read u; rmav_control
+ *     returns the command; m is not observed (rmav_state_dim and the observation rows are unchanged).
+ *   - episodes: m_c = init_c for every env at the moment the feature is switched on, at rmav_reset, and at every in-kernel auto-reset by
+ *     termination or truncation.  The step that ends an episode runs with the old m - inside a frame skip m stops advancing with the
+ *     sub-step that terminates - and the first step of the next episode filters from init.  Without RMAV_F_AUTO_RESET only rmav_reset
+ *     re-initialises.  A set on a handle whose spec is in force changes tau and init and keeps the running m.
+ *   - state: m lives in a [nA][N] device array of the handle, like the per-env constants: loaded at the head of every launch, held in
+ *     registers through a fused rollout and stored at its end; the single-step kernels update it in place.  A checkpoint is the spec plus
+ *     rmav_get_actuator_state / rmav_set_actuator_state (nA*N floats, both mem values, both layouts); rmav_seed, rmav_set_state,
+ *     rmav_set_reset_counts and rmav_set_step_count do not touch it.  Because m is in memory and alpha / beta are launch values, a
+ *     captured graph advances m correctly at replay and keeps the alpha / beta it was captured with.
+ * Launches of such a handle run kernels of their own, cut from the noisy ones, whose launch rules they share: the
+ * one-wavefront fused rollouts with ONE store policy (fused = 0 gives the bits of fused = 1; a chunk-major call is one launch per chunk); a
+ * handle without sensor noise skips the noise draw, one without a disturbance passes the all-zero one.  rmav_step_control is the step
+ * kernel's launch followed by rmav_control's (refused with a frame skip above 1, as ever).  rmav_rollout_policy / _boot / _norm run the
+ * three actors the sensor noise runs (RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA, RMAV_POLICY_F16_SHARED); the other precisions return
+ * RMAV_ERR_INVALID with a message that names the feature.
+ * Validation: every tau_c finite and >= 0, every init_c finite, components >= nA zero; RMAV_REINMAV takes no spec; anything else is
+ * RMAV_ERR_INVALID and the spec in force stays.  NULL switches the feature off and frees nothing observable: such a handle, like one that
+ * never set a spec, launches exactly the kernels it launched before.
+ * Ordering and capture as rmav_set_sensor_noise: the step kernels and the one-wavefront rollouts take alpha / beta / init by value; the
+ * policy kernels read a device copy in the handle's arena, which rmav_set_actuator (and rmav_set_params) rewrites in stream order with one
+ * small launch.  The first rmav_set_actuator on a handle allocates the [nA][N] array; every set that switches the feature on fills it
+ * with init in stream order; later sets neither allocate nor synchronise.
+ * rmav_get_actuator: the last spec set (zeros before the first), and whether it is in force; either pointer may be NULL.
+ * Callers detect the feature by the symbols; RMAV_VERSION is unchanged. */
+typedef struct rmav_actuator_spec {
+    float tau[4];                 /* time constant per action component, seconds; 0 = no lag; 2-action kinds read [0..1], the others must be 0 */
+    float init[4];                /* m at the start of every episode */
+} rmav_actuator_spec;             /* 32 bytes */
+int rmav_set_actuator(rmav_handle h, const rmav_actuator_spec *spec);   /* NULL: none (the default) */
+int rmav_get_actuator(rmav_handle h, rmav_actuator_spec *out, int32_t *enabled);   /* either pointer may be NULL */
+int rmav_get_actuator_state(rmav_handle h, float *out, int mem, int layout);   /* nA*N floats; RMAV_ERR_INVALID without a spec */
+int rmav_set_actuator_state(rmav_handle h, const float *in, int mem, int layout);   /* RMAV_ERR_INVALID without a spec */
+
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that
  * bootstraps a truncated episode (target r + gamma V(s_final): a truncated episode is not a failure) needs the state the dynamics

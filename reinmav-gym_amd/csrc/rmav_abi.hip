@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->actuator_on) {   // a handle with actuator lag: k_rollout_al, which takes the sensor noise (switched off without a spec) and all it takes as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_actuator_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no actuator-lag kernel for action mode %d", MODE);
+        }
     } else if (h->sensor_on) {   // a handle with sensor noise: k_rollout_sn, which takes the disturbance (all-zero without one) and all it takes as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_sensor_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
@@ -347,7 +353,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
     // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
     // One with a disturbance (rmav_set_disturbance): k_rollout_ds.  One with sensor noise (rmav_set_sensor_noise): k_rollout_sn.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on)) {
+    // One with actuator lag (rmav_set_actuator): k_rollout_al.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -424,7 +431,11 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->sensor_on) {   // a handle with sensor noise: k_step_sn for every batch size; the control() form is k_control (of the true state) behind it
+    if (h->actuator_on) {   // a handle with actuator lag: k_step_al for every batch size; the control() form is k_control (the command) behind it
+        if (int rc = rmav_launch_actuator_step(h, a, bs, FinalArgs{})) return rc;
+        if (ctrl)
+            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
+    } else if (h->sensor_on) {   // a handle with sensor noise: k_step_sn for every batch size; the control() form is k_control (of the true state) behind it
         if (int rc = rmav_launch_sensor_step(h, a, bs, FinalArgs{})) return rc;
         if (ctrl)
             if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
@@ -469,7 +480,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->sensor_on) {
+    if (h->actuator_on) {
+        if (int rc = rmav_launch_actuator_step(h, a, bs, fa)) return rc;
+    } else if (h->sensor_on) {
         if (int rc = rmav_launch_sensor_step(h, a, bs, fa)) return rc;
     } else if (h->disturb_on) {
         if (int rc = rmav_launch_disturb_step(h, a, bs, fa)) return rc;
@@ -674,6 +687,7 @@ void free_all(rmav_handle h) {
     if (h->range_dev) (void)hipFree(h->range_dev);
     if (h->ident_norm) (void)hipFree(h->ident_norm);
     if (h->boot_scratch) (void)hipFree(h->boot_scratch);
+    if (h->actuator_m) (void)hipFree(h->actuator_m);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     h->magic = 0;
     delete h;
@@ -829,6 +843,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         const size_t o_ds = off; off += (kind != RMAV_REINMAV) ? up(sizeof(DisturbSpec)) : 0;
         // (... and of a sensor-noise spec)
         const size_t o_sn = off; off += (kind != RMAV_REINMAV) ? up(sizeof(SensorDev)) : 0;
+        // (... and of an actuator spec's coefficients)
+        const size_t o_al = off; off += (kind != RMAV_REINMAV) ? up(sizeof(ActuatorDev)) : 0;
         if (hipMalloc(&h->arena, off) != hipSuccess) {
             (void)hipGetLastError();
             h->arena = nullptr;
@@ -840,7 +856,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         h->rec = (EnvRec *)(b + o_rec);
         h->totals = (Totals *)(b + o_tot);
         if (kind == RMAV_REINMAV) h->env_time = (double *)(b + o_time);
-        else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds), h->sensor_dev = (SensorDev *)(b + o_sn);
+        else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds), h->sensor_dev = (SensorDev *)(b + o_sn),
+                 h->actuator_dev = (ActuatorDev *)(b + o_al);
         if (tr) {
             h->ep_ret = (float *)(b + o_er);
             h->last_ret = (float *)(b + o_lr);
@@ -925,7 +942,15 @@ int rmav_set_params(rmav_handle h, const rmav_params *in) {
     if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
     if (!in) return rmav_fail(RMAV_ERR_INVALID, "in is NULL");
     if (int rc = check_params(*in)) return rc;
+    const rmav_params old = h->params;
     h->params = *in;
+    if (h->actuator_on && in->dt != old.dt) {   // actuator lag: alpha and beta follow the new dt (the policy kernels' copy, in stream order)
+        DeviceGuard guard(h->device);
+        if (int rc = rmav_sync_actuator_dev(h)) {
+            h->params = old;
+            return rc;
+        }
+    }
     return RMAV_OK;
 }
 
@@ -1035,6 +1060,8 @@ int rmav_sync(rmav_handle h) {
 int rmav_reset(rmav_handle h, float *obs_out, int mem, int layout) {
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
+    if (h->actuator_on)   // actuator lag: every env's m = init, in stream order in front of whatever steps next
+        if (int rc = rmav_launch_actuator_fill(h)) return rc;
     return write_via_host(h, obs_out, (size_t)h->n * kStateDim[h->kind] * sizeof(float), mem, [&](void *dst) {
         if (!h->sensor_on || !dst) return launch_reset_tl(h, (float *)dst, layout);
         // a handle with sensor noise: the reset, then the observation of the fresh states at the handle's step counter (k_observe)
@@ -1126,8 +1153,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // One wavefront, one k_step launch, outputs in the pinned block: the kernel publishes its completion in a pinned word and
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
-    // (not rmav_step_control of a handle with a tracking reward, a disturbance or sensor noise: k_control runs behind k_step_rw / k_step_ds / k_step_sn, which would publish too early)
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on))) {
+    // (not rmav_step_control of a handle with a tracking reward, a disturbance, sensor noise or actuator lag: k_control runs behind k_step_rw / k_step_ds / k_step_sn / k_step_al, which would publish too early)
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on))) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {
@@ -1551,6 +1578,95 @@ int rmav_observe(rmav_handle h, float *obs_out, int mem, int layout) {
     if (!h->sensor_on) return rmav_get_state(h, obs_out, mem, layout);   // no spec: the state itself
     return write_via_host(h, obs_out, (size_t)h->n * kStateDim[h->kind] * sizeof(float), mem,
                           [&](void *dst) { return rmav_launch_observe(h, (float *)dst, layout); });
+}
+
+// Actuator lag: the spec on the handle and the per-env filter state m [nA][N] behind it.  Every stepping launch reads actuator_on
+// (launch_rollout_kms, launch_step_k, launch_step_final_k; rmav_ppo_abi.hip) and derives alpha / beta from the spec and params.dt when it is
+// enqueued; the policy kernels read the device copy in the arena, which every set rewrites in stream order with one small launch.  The FIRST set
+// on a handle allocates m; every set that switches the feature on fills it with init in stream order; a set on a handle whose spec is in
+// force keeps the running m.  Later sets neither allocate nor synchronise.
+int rmav_set_actuator(rmav_handle h, const rmav_actuator_spec *spec) {
+    CHECK_HANDLE(h);
+    if (!spec) {   // none: the launches of a handle that never had a spec (m stays allocated, unread)
+        h->actuator_on = 0;
+        return RMAV_OK;
+    }
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no actuator lag");
+    const int nA = kActionDim[h->kind];
+    for (int c = 0; c < 4; ++c) {
+        const float tau = spec->tau[c], m0 = spec->init[c];
+        if (!(tau - tau == 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "every tau of an actuator spec must be finite (component %d is not)", c);
+        if (!(tau >= 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "actuator tau[%d] = %g is negative", c, (double)tau);
+        if (!(m0 - m0 == 0.0f)) return rmav_fail(RMAV_ERR_INVALID, "every init of an actuator spec must be finite (component %d is not)", c);
+        if (c >= nA && (tau != 0.0f || m0 != 0.0f))
+            return rmav_fail(RMAV_ERR_INVALID, "actuator tau[%d] = %g, init[%d] = %g: the kind has %d action components, the others must be 0", c, (double)tau, c,
+                             (double)m0, nA);
+    }
+    if (!h->actuator_m) {
+        const hipError_t e = hipMalloc((void **)&h->actuator_m, (size_t)nA * (size_t)h->n * sizeof(float));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            h->actuator_m = nullptr;
+            return rmav_fail(RMAV_ERR_HIP, "the actuator state of %lld envs: %s", (long long)h->n, hipGetErrorString(e));
+        }
+    }
+    const rmav_actuator_spec old = h->actuator;
+    h->actuator = *spec;
+    int rc = rmav_sync_actuator_dev(h);   // the policy kernels' copy, in stream order
+    if (!rc && !h->actuator_on) rc = rmav_launch_actuator_fill(h);   // switched on: m = init for every env
+    if (rc) {
+        h->actuator = old;
+        if (h->actuator_on) (void)rmav_sync_actuator_dev(h);
+        return rc;
+    }
+    h->actuator_on = 1;
+    return RMAV_OK;
+}
+
+int rmav_get_actuator(rmav_handle h, rmav_actuator_spec *out, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (out) *out = h->actuator;   // (the last spec set - zeros before the first - also while it is switched off)
+    if (enabled) *enabled = h->actuator_on;
+    return RMAV_OK;
+}
+
+// m as rmav_get_state / rmav_set_state move the state: [nA][N] feature-major as it is stored, or batch-major through the layout kernels
+int rmav_get_actuator_state(rmav_handle h, float *out, int mem, int layout) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, layout)) return rc;
+    if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
+    if (!h->actuator_on) return rmav_fail(RMAV_ERR_INVALID, "the handle has no actuator spec (rmav_set_actuator): there is no actuator state");
+    const int nA = kActionDim[h->kind];
+    const size_t cnt = (size_t)h->n * nA;
+    if (layout == RMAV_SOA) return copy_out(h, (const float *)h->actuator_m, out, cnt, mem);
+    float *dst = out;
+    if (mem != RMAV_DEVICE) {
+        if (int rc = ensure_scratch(h, cnt * sizeof(float))) return rc;
+        dst = (float *)h->scratch;
+    }
+    hipLaunchKernelGGL(k_soa_to_aos, grid_for(h), dim3(block_size(h)), 0, h->stream, h->actuator_m, dst, h->n, nA);
+    HIP_TRY(hipGetLastError());
+    return mem == RMAV_DEVICE ? (int)RMAV_OK : copy_out(h, (const float *)dst, out, cnt, RMAV_HOST);
+}
+
+int rmav_set_actuator_state(rmav_handle h, const float *in, int mem, int layout) {
+    CHECK_HANDLE(h);
+    if (int rc = check_mem_layout(mem, layout)) return rc;
+    if (!in) return rmav_fail(RMAV_ERR_INVALID, "in is NULL");
+    if (!h->actuator_on) return rmav_fail(RMAV_ERR_INVALID, "the handle has no actuator spec (rmav_set_actuator): there is no actuator state to set");
+    const int nA = kActionDim[h->kind];
+    const size_t cnt = (size_t)h->n * nA;
+    if (layout == RMAV_SOA) return copy_in(h, h->actuator_m, in, cnt, mem);
+    const float *src = in;
+    if (mem == RMAV_HOST) {
+        if (int rc = ensure_scratch(h, cnt * sizeof(float))) return rc;
+        HIP_TRY(hipMemcpyAsync(h->scratch, in, cnt * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        src = (const float *)h->scratch;
+    }
+    hipLaunchKernelGGL(k_aos_to_soa, grid_for(h), dim3(block_size(h)), 0, h->stream, src, h->actuator_m, h->n, nA);
+    HIP_TRY(hipGetLastError());
+    if (mem == RMAV_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
+    return RMAV_OK;
 }
 
 int rmav_set_time_limit(rmav_handle h, int32_t max_episode_steps) {

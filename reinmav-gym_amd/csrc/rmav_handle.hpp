@@ -1,7 +1,8 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus seven that only launch kernels (rmav_policy_abi.hip,
-// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip, rmav_sensor_abi.hip, rmav_sensor_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus nine that only launch kernels (rmav_policy_abi.hip,
+// rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip, rmav_sensor_abi.hip, rmav_sensor_policy_abi.hip,
+// rmav_actuator_abi.hip, rmav_actuator_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -122,7 +123,27 @@ struct rmav_env_s {
     int32_t sensor_on;
     rmav_sensor_noise_spec sensor;
     rmav::SensorDev *sensor_dev;   // the policy kernels' copy of the spec, in the arena next to disturb_dev (k_set_sensor_noise rewrites it)
+    // actuator lag (rmav_set_actuator): the spec, whether one is set, and the per-env filter state m [nA][N] (allocated and filled with init
+    // by the first set; kept, unread, while the feature is off).  actuator_on routes every stepping launch to the *_al kernels - before the
+    // sensor noise, which those kernels take as well (switched off by a wave-uniform flag without a spec).  The step kernels and the
+    // one-wavefront rollouts take alpha / beta / init by value, derived from the spec and params.dt at the launch; the policy kernels read
+    // actuator_dev, which every set - and rmav_set_params - rewrites in stream order.
+    int32_t actuator_on;
+    rmav_actuator_spec actuator;
+    float *actuator_m;
+    rmav::ActuatorDev *actuator_dev;   // in the arena next to sensor_dev (k_set_actuator rewrites it)
 };
+static_assert(sizeof(rmav_actuator_spec) == 32, "eight floats");
+// alpha, beta (from the spec's tau and the dt in force) and init, as the *_al kernels take them
+inline rmav::ActuatorCoef actuator_coef(const rmav_env_s *h) {
+    rmav::ActuatorCoef c{};
+    for (int i = 0; i < 4; ++i) {
+        rmav::actuator_coeffs((double)h->actuator.tau[i], (double)h->params.dt, c.alpha[i], c.beta[i]);
+        c.init[i] = h->actuator.init[i];
+    }
+    return c;
+}
+inline rmav::ActuatorArgs actuator_args(const rmav_env_s *h) { return rmav::ActuatorArgs{actuator_coef(h), h->actuator_m, h->sensor_on ? 1u : 0u, 0u}; }
 static_assert(sizeof(rmav_sensor_noise_spec) == 64 && sizeof(rmav::SensorArgs) == 64, "sixteen floats");
 // what the *_sn kernels and k_observe take
 inline rmav::SensorArgs sensor_args(const rmav_env_s *h) {
@@ -186,6 +207,14 @@ inline rmav::PolicySensorArgs policy_sensor_args(const rmav_env_s *h, uint64_t t
     const rmav::DisturbArgs d = disturb_or_calm(h, t0);
     return rmav::PolicySensorArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev, h->disturb_on ? h->disturb_dev : &h->sensor_dev->calm, d.b0, d.phase0, 0,
                                   &h->sensor_dev->sn};
+}
+// what the lagged policy kernels take in PolicySensorArgs' place: the calm disturbance spec of a handle without one sits in actuator_dev
+// (k_set_actuator writes it; sensor_dev's copy exists only once a sensor-noise spec was set); sn is read only with sn_on
+inline rmav::PolicyActuatorArgs policy_actuator_args(const rmav_env_s *h, uint64_t t0) {
+    const rmav::ActRuleArgs r = act_rule_args(h);
+    const rmav::DisturbArgs d = disturb_or_calm(h, t0);
+    return rmav::PolicyActuatorArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev, h->disturb_on ? h->disturb_dev : &h->actuator_dev->calm, d.b0, d.phase0,
+                                    h->sensor_on ? 1u : 0u, &h->sensor_dev->sn, &h->actuator_dev->c, h->actuator_m};
 }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
@@ -408,3 +437,16 @@ RMAV_INTERNAL int rmav_launch_observe(rmav_handle h, float *out_dev, int layout)
 RMAV_INTERNAL int rmav_launch_sensor_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
 // ... and k_set_sensor_noise: the handle's device copy of the spec (sensor_dev), rewritten in stream order; no allocation, no synchronisation
 RMAV_INTERNAL int rmav_sync_sensor_dev(rmav_handle h);
+
+// rmav_actuator_abi.hip: the launches of a handle with actuator lag (rmav_set_actuator), shaped as the noisy ones, whose arguments they take
+// as well (a handle without sensor noise: sn_on = 0; without a disturbance: the all-zero spec).  _rollout: ONE launch of
+// k_rollout_al<K, mode, time limit?, reward?> (one store policy); _step: k_step_al at bs threads per workgroup; _fill: k_actuator_fill, which
+// sets every env's m to the spec's init, in stream order; _sync: k_set_actuator, the handle's device copy of the coefficients (actuator_dev)
+// rewritten in stream order - no allocation, no synchronisation.  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_actuator_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_actuator_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_actuator_fill(rmav_handle h);
+RMAV_INTERNAL int rmav_sync_actuator_dev(rmav_handle h);
+// rmav_actuator_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_al, k_rollout_pair_al, k_rollout_pair_shared_al -
+// with rmav_launch_sensor_policy_rollout's arguments.
+RMAV_INTERNAL int rmav_launch_actuator_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);

@@ -30,6 +30,7 @@
 #include "rmav_math.hpp"
 #include "rmav_disturb.hpp"
 #include "rmav_sensor.hpp"
+#include "rmav_actuator.hpp"
 #include "rmav_policy.hpp"
 #include "rmav_policy_mfma.hpp"
 #include "rmav_policy_mfma32.hpp"
@@ -37,6 +38,10 @@
 // RMAV_ROLLOUT_SN: the sensor noise of the *_sn wrappers (rmav_set_sensor_noise; rmav_sensor.hpp) is compiled into rmav_rollout_body.inc only
 // where a wrapper sets it around its #include, as RMAV_PAIR_DS in the pair bodies: every other kernel's text is what it was.
 #define RMAV_ROLLOUT_SN 0
+// RMAV_ROLLOUT_AL: likewise the actuator lag of the *_al wrappers (rmav_set_actuator; rmav_actuator.hpp), which are cut from the *_sn bodies:
+// the filter state m beside the state, the filter in front of every dynamics sub-step, m = init at a reset, and the noise draw behind ONE
+// wave-uniform branch per site (al.sn_on: a handle with lag and no sensor noise does not pay it).
+#define RMAV_ROLLOUT_AL 0
 
 namespace rmav {
 
@@ -380,6 +385,58 @@ struct PolicySensorArgs {
     int32_t _pad;
     const SensorArgs *sn;
 };
+// ... and the POLICY kernels of a handle with actuator lag (the *_al policy families): PolicySensorArgs with the handle's device copy of the
+// filter's coefficients behind it, the handle's array of m and whether the handle has sensor noise.  ActuatorDev is that copy
+// (rmav_env_s::actuator_dev, rewritten in stream order by k_set_actuator): alpha, beta, init and - for a handle without a disturbance - the calm
+// disturbance spec ds then points at.
+struct ActuatorDev {
+    ActuatorCoef c;
+    DisturbSpec calm;
+};
+struct PolicyActuatorArgs {
+    float noise, lo, hi;
+    int32_t k;
+    const RewardArgs *rw;
+    const DisturbSpec *ds;
+    uint64_t b0;
+    int32_t phase0;
+    uint32_t sn_on;
+    const SensorArgs *sn;
+    const ActuatorCoef *al;
+    float *m;
+};
+// the observation row of the *_al kernels: the noisy one, or - a handle without sensor noise, wave-uniform - the state itself
+template <int NS>
+__device__ __forceinline__ void actuator_obs(uint32_t sn_on, const SensorArgs &sn, uint64_t seed, uint64_t env_id, uint64_t b, const float (&s)[NS], float (&o)[NS]) {
+    if (sn_on) {
+        float z[NS];
+        sensor_draw<NS>(seed, env_id, b, z);
+        sensor_apply(sn, z, s, o);
+    } else {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) o[c] = s[c];
+    }
+}
+// ... under a z already drawn (the single-step kernel: one z for the terminal and the post-reset observation)
+template <int NS>
+__device__ __forceinline__ void step_obs_al(uint32_t sn_on, const SensorArgs &sn, const float (&z)[NS], const float (&s)[NS], float (&o)[NS]) {
+    if (sn_on) {
+        sensor_apply(sn, z, s, o);
+    } else {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) o[c] = s[c];
+    }
+}
+// ... into the words dst[c * 64] of a pair kernel's LDS row (sensor_store_row or the plain copy)
+template <int NS>
+__device__ __forceinline__ void actuator_obs_row(uint32_t sn_on, const SensorArgs &sn, uint64_t seed, uint64_t env_id, uint64_t b, const float (&s)[NS], float *dst) {
+    if (sn_on) {
+        sensor_store_row<NS>(sn, seed, env_id, b, s, dst);
+    } else {
+#pragma unroll
+        for (int c = 0; c < NS; ++c) dst[c * 64] = s[c];
+    }
+}
 // where the tracked body's position and velocity sit in the state, and their dimension
 template <int K> struct RewardBody;
 template <> struct RewardBody<QUAD2D>    { static constexpr int P = 0,  V = 3,  D = 2; };
@@ -792,6 +849,68 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 #define RMAV_ROLLOUT_SN 0
 }
 
+// The one-wavefront kernels of a handle with actuator lag (rmav_set_actuator; ActuatorArgs in rmav_actuator.hpp): k_rollout_sn's body and
+// argument list with the filter behind it.  m is loaded at the head of the launch, advanced in front of every dynamics sub-step (which reads
+// it in the action's place), set to init where the state is reset and stored with the state.  A handle without sensor noise passes
+// al.sn_on = 0, which skips the draw with one scalar branch per site; one without a disturbance the all-zero spec.  One store policy.
+template <int K, int MODE, bool TL, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_al(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn,
+                                                       const ActuatorArgs al) {
+    constexpr int ST = ST_DEFAULT;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, DS = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    const ActuatorCoef &alc = al.c;
+    const float *const al_init = al.c.init;
+    float *const al_m = al.m;
+    const uint32_t al_sn = al.sn_on;
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "lagged launches run the one-wavefront kernels");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 0
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_sn whose dynamics read the filtered action.  The filter takes the action
+// after the rule's clip; the stored action and its log-probability stay what the policy drew.  The coefficients are read through the
+// handle's device copy.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_al(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicyActuatorArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    const ActuatorCoef &alc = *ps.al;   // (read at their uses, as the other specs of this kernel: held in registers they cost the kind-0 kernels a wave of occupancy)
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 0
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
 // reset_state<K> for the lanes of a wavefront that need it, computed cooperatively (all 64 lanes must be active).
 // Philox4x32-10 is ~20 quarter-rate 32x32->64 multiplies per call and reset_state needs ceil(nS / 4) calls (the counter
 // word c3 selects the block of four components); executed by a whole wavefront for the one or two lanes whose env has
@@ -866,13 +985,17 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // DS: the handle has a disturbance (ds; k_step_ds): the lane's gravity is g_vec + d of this step; the controller's constants keep g_vec.
 // SN: the handle has sensor noise (sn; k_step_sn): obs_out and final_obs are fma(sigma, z, s) with ONE z, that of the step counter after
 // this step (a.t0 + 1); the state stored in place stays the true one.
+// AL: the handle has actuator lag (al; k_step_al): the filter state m is loaded beside the state, advanced in front of every dynamics
+// sub-step - which reads m, not the action -, set to init where the env is reset and stored in place; al.sn_on = 0 skips the noise draw.
 template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false, bool DS = false,
-          bool SN = false>
+          bool SN = false, bool AL = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
                                           const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
                                           [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{},
-                                          [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}, [[maybe_unused]] const SensorArgs &sn = SensorArgs{}) {
+                                          [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}, [[maybe_unused]] const SensorArgs &sn = SensorArgs{},
+                                          [[maybe_unused]] const ActuatorArgs &al = ActuatorArgs{}) {
     static_assert(!RW || FS, "the tracking reward is evaluated in the sub-step loop");
+    static_assert(!AL || SN, "the lagged step is cut from the noisy body");
     static_assert(!SN || (DS && FIN), "the noisy step is cut from the disturbed body");
     static_assert(!DS || (FS && DR && !CTRL), "the disturbed step is cut from the most general body: the running reset index, eagerly; k_control behind it");
     static_assert(K != REINMAV, "ReinmavEnv steps go through k_rollout");
@@ -929,6 +1052,12 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
 #pragma unroll
         for (int c = 0; c < NA; ++c) act[c] = LAZY ? buf_ld_nt(r, off, (uint32_t)c * tcol) : buf_ld(r, off, (uint32_t)c * tcol);   // big batches: read-once, non-temporal (1 048 576 envs -2 %)
     }
+    [[maybe_unused]] float am[AL ? NA : 1];   // AL: the filter state of this env
+    if constexpr (AL) {
+        const rsrc_t r_m = make_rsrc(al.m);
+#pragma unroll
+        for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);
+    }
     float er = 0.0f;
     if (track) er = buf_ld(make_rsrc(a.ep_ret), off, 0);
     // needed only by lanes whose env terminates in this step: steps_beyond_done (the terminal reward), the reset counter
@@ -980,7 +1109,12 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
         do {
             if (live) {
                 bool term;
-                Env<K>::step(s, act, pl, dist, term);
+                if constexpr (AL) {   // the filter advances in front of every dynamics sub-step, which reads m; c_rw keeps the command
+                    actuator_step<NA>(al.c, am, act);
+                    Env<K>::step(s, am, pl, dist, term);
+                } else {
+                    Env<K>::step(s, act, pl, dist, term);
+                }
                 float rj = -dist;
                 if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
                     rj = reward_rw<K>(s, c_rw, rw, term);
@@ -1000,7 +1134,9 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     }
     // SN: the noise of every observation this step emits (wave-uniform: skipped when the caller asked for none)
     [[maybe_unused]] float sn_z[SN ? NS : 1];
-    if constexpr (SN) {
+    if constexpr (AL) {   // (a handle with lag and no sensor noise skips the draw and stores the state itself: al.sn_on is wave-uniform)
+        if ((a.obs_out || fa.final_obs) && al.sn_on) sensor_draw<NS>(a.seed, a.env_base + (uint64_t)li, a.t0 + 1u, sn_z);
+    } else if constexpr (SN) {
         if (a.obs_out || fa.final_obs) sensor_draw<NS>(a.seed, a.env_base + (uint64_t)li, a.t0 + 1u, sn_z);
     }
     // Where and how the step's outputs are stored (same values on both paths): reward, done, running return
@@ -1018,7 +1154,8 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
         if (a.obs_out) {
             if constexpr (SN) {   // the observation of the state just stored: the z the terminal observation took
                 float o[NS];
-                sensor_apply(sn, sn_z, s, o);
+                if constexpr (AL) step_obs_al(al.sn_on, sn, sn_z, s, o);
+                    else sensor_apply(sn, sn_z, s, o);
                 if (aos) {
                     float *dst = a.obs_out + (int64_t)li * NS;
 #pragma unroll
@@ -1100,7 +1237,8 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
             if (fa.final_obs && done) {
                 if constexpr (SN) {   // the terminal observation: the pre-reset state under the step's z
                     float o[NS];
-                    sensor_apply(sn, sn_z, s, o);
+                    if constexpr (AL) step_obs_al(al.sn_on, sn, sn_z, s, o);
+                    else sensor_apply(sn, sn_z, s, o);
                     if (aos) {
                         float *dst = fa.final_obs + (int64_t)li * NS;
 #pragma unroll
@@ -1135,6 +1273,13 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
         }
     }
     if (valid) store_state();
+    if constexpr (AL) {   // the filter state in place: init where the env was reset (the step that ended the episode ran with the old m)
+        if (valid) {
+            const rsrc_t r_m = make_rsrc(al.m);
+#pragma unroll
+            for (int c = 0; c < NA; ++c) buf_st_aux<AUX>(r_m, off, (uint32_t)c * col, (auto_reset && done) ? al.c.init[c] : am[c]);
+        }
+    }
     if constexpr (CTRL) {   // control() of the state this launch leaves behind
         float a2[NA];
         env_control<K>(s, pcl, a2);
@@ -1342,6 +1487,25 @@ __global__ __launch_bounds__(kBlock) void k_step_sn(float *state_pl, int64_t n_p
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn);
+}
+
+// The single-step kernel of a handle with actuator lag (rmav_set_actuator): k_step_sn's body and argument list with the filter behind it.
+// m is updated in place: advanced once per dynamics sub-step, init where the env was reset.
+template <int K, bool TL, bool RW>
+__global__ __launch_bounds__(kBlock) void k_step_al(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn,
+                                                    const ActuatorArgs al) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn, al);
 }
 
 // rmav_observe: the observation of every env's current state at the step counter b, out nS * n floats, feature-major or - aos - batch-major.

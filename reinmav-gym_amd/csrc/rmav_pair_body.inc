@@ -129,7 +129,9 @@
 
     // ---- actor: policy net, action, dynamics, bookkeeping --------------------------------------------------------------
 #include "rmav_pair_env_load.inc"   // fin_*, er, el, sb, rc, pl / p, tenv, spare, have_spare, pol_std
-#if RMAV_PAIR_SN   // the observation of the launch's first state (step counter t0), where step "-1" would have left its row: half 1
+#if RMAV_PAIR_AL   // (the *_al wrappers: the noisy row or - al_sn = 0, wave-uniform - the state itself)
+    actuator_obs_row<NS>(al_sn, sn, a.seed, env_id, a.t0, s, otile + PT::O_HALF);
+#elif RMAV_PAIR_SN   // the observation of the launch's first state (step counter t0), where step "-1" would have left its row: half 1
     sensor_store_row<NS>(sn, a.seed, env_id, a.t0, s, otile + PT::O_HALF);
 #endif
     __syncthreads();                                                  // B: Z(0) is in the tile
@@ -173,7 +175,9 @@
                 using PB = PairBootTile<NS, NA>;
                 if (__ballot(trunc) != 0) {   // wave-uniform
                     float *fin = tile + PB::FIN + (k & 1) * PB::FIN_HALF + lane;
-#if RMAV_PAIR_SN   // the terminal OBSERVATION: the pre-reset state under the z of this step's row
+#if RMAV_PAIR_AL
+                    actuator_obs_row<NS>(al_sn, sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, fin);
+#elif RMAV_PAIR_SN   // the terminal OBSERVATION: the pre-reset state under the z of this step's row
                     sensor_store_row<NS>(sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, fin);
 #else
 #pragma unroll

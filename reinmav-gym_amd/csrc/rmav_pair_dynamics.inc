@@ -36,7 +36,12 @@
                 do {
                     if (live) {
                         bool term;
+#if RMAV_PAIR_AL   // actuator lag: the filter advances in front of every dynamics sub-step, which reads m; c_rw and the stored action keep the command
+                        actuator_step<NA>(alc, am, ca);
+                        Env<K>::step(s, am, p, dist, term);
+#else
                         Env<K>::step(s, ca, p, dist, term);
+#endif
                         float rj = -dist;
                         if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
                             rj = reward_rw<K>(s, c_rw, rw, term);

@@ -64,6 +64,15 @@
     wind_draw(ds.spec(), a.seed, env_id, rc - 1u, ds_w);
     gust_draw(ds.spec(), a.seed, env_id, ds_b, ds_q);
 #endif
+#if RMAV_PAIR_AL   // the *_al kernels (alc: ActuatorCoef, al_m: the handle's [nA][N] array): the filter state of this env, which belongs to the
+                   // wavefront that integrates - in registers through the launch, stored by rmav_pair_epilogue.inc
+    float am[NA];
+    {
+        const rsrc_t r_m = make_rsrc(al_m);
+#pragma unroll
+        for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);
+    }
+#endif
     float pol_std[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NA; ++c) pol_std[c] = NORM ? expf(logstd[c]) * ar.noise : expf(logstd[c]);   // the action rule: std_eff

@@ -8,6 +8,13 @@
 //   barriers: behind the last barrier of the step loop; none follows (the helper wavefront has returned or is draining the last row)
 #pragma unroll
     for (int c = 0; c < NS; ++c) buf_st(r_state, off, (uint32_t)c * col, s[c]);
+#if RMAV_PAIR_AL   // the filter state, with the state (vector stores; clone lanes store the bits of the lane they copy, as for the state)
+    {
+        const rsrc_t r_m = make_rsrc(al_m);
+#pragma unroll
+        for (int c = 0; c < NA; ++c) buf_st(r_m, off, (uint32_t)c * col, am[c]);
+    }
+#endif
     if constexpr (K == REINMAV) a.env_time[li] = tenv;
     if (track) {
         buf_st(make_rsrc(a.ep_ret), off, 0, er);

@@ -47,6 +47,10 @@
 #if RMAV_PAIR_DS
                 wind_draw(ds.spec(), a.seed, env_id, rc, ds_w);   // the new episode's wind (the step that ended the old one has used the old)
 #endif
+#if RMAV_PAIR_AL   // the new episode's actuator state (the step that ended the old one ran with the old m)
+#pragma unroll
+                for (int c = 0; c < NA; ++c) am[c] = al_init[c];
+#endif
                 have_spare = false;
                 rc += 1;
             }
@@ -59,7 +63,9 @@
         }
 #endif
         float *row = otile + (k & 1) * PT::O_HALF;
-#if RMAV_PAIR_SN   // the *_sn wrappers (kernel argument sn: SensorArgs): the row holds the OBSERVATION of the state after the step and its reset,
+#if RMAV_PAIR_AL   // the *_al wrappers: the noisy row as below, or - a handle without sensor noise (al_sn = 0, wave-uniform) - the state itself
+        actuator_obs_row<NS>(al_sn, sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, row);
+#elif RMAV_PAIR_SN   // the *_sn wrappers (kernel argument sn: SensorArgs): the row holds the OBSERVATION of the state after the step and its reset,
                    // under the z of the step counter after the step - computed once, by the lane that owns the env; both nets of step k + 1
                    // and the trajectory store read it from the row.  s stays the true state.
         sensor_store_row<NS>(sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, row);

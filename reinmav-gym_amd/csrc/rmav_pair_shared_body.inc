@@ -168,7 +168,9 @@
     };
     {   // the initial obs of the pair's envs, for B's first evaluation: the obs half step "-1" would have written
         float *row = otile + PT::O_HALF;
-#if RMAV_PAIR_SN   // ... the observation of the launch's first state, at the step counter t0
+#if RMAV_PAIR_AL   // (the *_al wrappers: the noisy row or - al_sn = 0, wave-uniform - the state itself)
+        actuator_obs_row<NS>(al_sn, sn, a.seed, env_id, a.t0, s, row);
+#elif RMAV_PAIR_SN   // ... the observation of the launch's first state, at the step counter t0
         sensor_store_row<NS>(sn, a.seed, env_id, a.t0, s, row);
 #else
 #pragma unroll
@@ -202,7 +204,10 @@
                 const uint64_t tm = __ballot(trunc);
                 if (tm != 0) {   // wave-uniform
                     float *fin = tile + SB::FIN + (k & 1) * SB::FIN_HALF + lane;
-#if RMAV_PAIR_SN   // the terminal OBSERVATION: the pre-reset state under the z of this step's row; both wavefronts evaluate the net on it
+#if RMAV_PAIR_AL
+                    actuator_obs_row<NS>(al_sn, sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, fin);
+#define RMAV_SFIN(c) (fin[(c) * 64])
+#elif RMAV_PAIR_SN   // the terminal OBSERVATION: the pre-reset state under the z of this step's row; both wavefronts evaluate the net on it
                     sensor_store_row<NS>(sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, fin);
 #define RMAV_SFIN(c) (fin[(c) * 64])
 #else

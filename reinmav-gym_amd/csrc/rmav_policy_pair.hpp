@@ -40,6 +40,10 @@
 // RMAV_PAIR_SN: likewise the sensor noise of the *_sn wrappers (rmav_set_sensor_noise; rmav_sensor.hpp): the rows of the output tile hold the
 // noisy observation - computed once per step by the lane that owns the env -, both nets read it from there, the terminal area likewise.
 #define RMAV_PAIR_SN 0
+// RMAV_PAIR_AL: likewise the actuator lag of the *_al wrappers (rmav_set_actuator; rmav_actuator.hpp), which are cut from the *_sn bodies: the
+// filter state m of the wavefront that integrates, the filter in front of every dynamics sub-step, m = init at a reset, and the noisy rows
+// behind one wave-uniform branch per site (al_sn: a handle with lag and no sensor noise stores the state itself).
+#define RMAV_PAIR_AL 0
 
 namespace rmav {
 
@@ -396,6 +400,44 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_sn(cons
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 0
 }
+// ... and of a handle with actuator lag (rmav_set_actuator; rmav_actuator.hpp): k_rollout_pair_sn whose actor wavefront - the one that
+// integrates - carries the filter state m and feeds the dynamics with it; the action it hands to the critic for storing stays the command.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_al(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyActuatorArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    ActuatorCoef alc;   // alpha and beta once per launch, into registers (every sub-step reads them); init is read where an env is reset
+#pragma unroll
+    for (int c = 0; c < Dims<K>::NA; ++c) alc.alpha[c] = ps.al->alpha[c], alc.beta[c] = ps.al->beta[c];
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 1
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 0
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 0
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
 
 // ---- one shared 2 x 64 trunk with a mean head and a value head (RMAV_POLICY_F16_SHARED) -------------------------------------------
 //
@@ -647,5 +689,41 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
 #define RMAV_PAIR_DR 0
 }
 
+// ... and of a handle with actuator lag: k_rollout_pair_shared_sn whose wavefront A carries the filter state (see k_rollout_pair_al).
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_al(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyActuatorArgs ps) {
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    ActuatorCoef alc;   // alpha and beta once per launch, into registers (every sub-step reads them); init is read where an env is reset
+#pragma unroll
+    for (int c = 0; c < Dims<K>::NA; ++c) alc.alpha[c] = ps.al->alpha[c], alc.beta[c] = ps.al->beta[c];
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 1
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 0
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 0
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
 
 }  // namespace rmav

@@ -107,9 +107,12 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
     // ... and so does a handle with a frame skip or a tracking reward: its kernels are the ranged normalised ones with the sub-step loop
     // ... and one with a disturbance: the *_ds kernels are those with g_vec + d
     // ... and one with sensor noise: k_rollout_nrm_sn is the disturbed kernel whose nets read the noisy observation
-    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on;
+    // ... and one with actuator lag: the *_al kernels are the noisy ones with the filter between the clipped action and the dynamics
+    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on;
     if (skipped) {
-        if (h->sensor_on) {
+        if (h->actuator_on) {
+            if (int rc = need_variants(precision, "a handle with actuator lag (rmav_set_actuator)", "actuator-lag")) return rc;
+        } else if (h->sensor_on) {
             if (int rc = need_variants(precision, "a handle with sensor noise (rmav_set_sensor_noise)", "sensor-noise")) return rc;
         } else if (h->disturb_on) {
             if (int rc = need_variants(precision, "a handle with a disturbance (rmav_set_disturbance)", "disturbed")) return rc;
@@ -132,7 +135,9 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
             bt = &bt_r;
         }
     }
-    if (h->sensor_on) {
+    if (h->actuator_on) {
+        if (int rc = rmav_launch_actuator_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
+    } else if (h->sensor_on) {
         if (int rc = rmav_launch_sensor_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
     } else if (int rc = rmav_launch_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
     h->t += (uint64_t)n_steps;

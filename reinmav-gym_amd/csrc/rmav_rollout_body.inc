@@ -477,6 +477,15 @@
 #pragma unroll
             for (int i = 0; i < disturb_dim<K>(); ++i) spare_w[i] = 0.0f;
         }
+#if RMAV_ROLLOUT_AL   // the *_al wrappers (alc: ActuatorCoef, al_m: the handle's [nA][N] array, al_sn: the handle has sensor noise): the filter state
+                      // of this env rides in registers for the whole launch - loaded here, stored with the state behind the step loop
+        float am[NA];
+        {
+            const rsrc_t r_m = make_rsrc(al_m);
+#pragma unroll
+            for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);
+        }
+#endif
         double tenv = 0.0;
         if constexpr (K == REINMAV) tenv = a.env_time[li];
 
@@ -618,9 +627,13 @@
 #define RMAV_OBS sn_o
         float sn_o[NS];
         if constexpr (is_policy(MODE)) {
+#if RMAV_ROLLOUT_AL   // (... or, on a handle without sensor noise, the state itself: one wave-uniform branch per site)
+            actuator_obs<NS>(al_sn, sn, a.seed, env_id, a.t0, s, sn_o);
+#else
             float sn_z[NS];
             sensor_draw<NS>(a.seed, env_id, a.t0, sn_z);
             sensor_apply(sn, sn_z, s, sn_o);
+#endif
         }
 #else
 #define RMAV_OBS s
@@ -743,7 +756,12 @@
                     do {
                         if (live) {
                             bool term;
+#if RMAV_ROLLOUT_AL   // actuator lag: the filter advances in front of every dynamics sub-step, which reads m; c_rw and the stored action keep the command
+                            actuator_step<NA>(alc, am, ca);
+                            Env<K>::step(s, am, p, dist, term);
+#else
                             Env<K>::step(s, ca, p, dist, term);
+#endif
                             float rj = -dist;
                             if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
                                 rj = reward_rw<K>(s, c_rw, rw, term);
@@ -810,11 +828,15 @@
                       // about one step in max_steps - instead of NS registers of z held across the reset)
                         if constexpr (NORM) {
                             float sf[NS];
+#if RMAV_ROLLOUT_AL
+                            actuator_obs<NS>(al_sn, sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, sf);
+#else
                             {
                                 float sn_z[NS];
                                 sensor_draw<NS>(a.seed, env_id, a.t0 + (uint64_t)k + 1u, sn_z);
                                 sensor_apply(sn, sn_z, s, sf);
                             }
+#endif
                             norm_state16<NS>(lds_w + Mfma32Layout::TOTAL, sf, xf);
                         } else {
 #else
@@ -923,11 +945,15 @@
 #if RMAV_ROLLOUT_SN   // the *_sn wrappers (kernel argument sn: SensorArgs): the observation of the state after this step and its reset, under
                       // the z of the step counter after the step; s itself - the dynamics, the reward, the state stored in place - stays true
             } else if (is_policy(MODE) || obs_out) {   // (an actor reads the observation whether or not the caller stores it)
+#if RMAV_ROLLOUT_AL
+                actuator_obs<NS>(al_sn, sn, a.seed, env_id, a.t0 + (uint64_t)k + 1u, s, sn_o);
+#else
                 {
                     float sn_z[NS];
                     sensor_draw<NS>(a.seed, env_id, a.t0 + (uint64_t)k + 1u, sn_z);
                     sensor_apply(sn, sn_z, s, sn_o);
                 }
+#endif
                 if (obs_out) {
                     if (aos) {
                         float *dst = obs_out + (int64_t)li * NS;
@@ -1010,6 +1036,18 @@
         }
 #pragma unroll
         for (int c = 0; c < NS; ++c) buf_st(r_state, off, (uint32_t)c * col, s[c]);
+#if RMAV_ROLLOUT_AL   // the filter state, with the state (vector stores; clone lanes store the bits of the lane they copy, as for the state).  The
+                      // actor through the plain pointer: with a third buffer descriptor here one quadrotor2d-slungload kernel kept a 48-byte
+                      // stack frame; the others through a descriptor: the 64-bit address costs quadrotor3d-slungload a wave of occupancy
+        if constexpr (is_policy(MODE)) {
+#pragma unroll
+            for (int c = 0; c < NA; ++c) al_m[(int64_t)c * n + li] = am[c];
+        } else {
+            const rsrc_t r_m = make_rsrc(al_m);
+#pragma unroll
+            for (int c = 0; c < NA; ++c) buf_st(r_m, off, (uint32_t)c * col, am[c]);
+        }
+#endif
         if constexpr (MODE == ACT_BUFFER_CTRL && K != REINMAV) {   // control() of the state this launch leaves behind
             float a2[NA];
             env_control<K>(s, pc, a2);

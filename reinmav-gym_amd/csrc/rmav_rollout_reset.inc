@@ -33,6 +33,10 @@
 #pragma unroll
                             for (int i = 0; i < disturb_dim<K>(); ++i) ds_w[i] = spare_w[i];
                         }
+#if RMAV_ROLLOUT_AL   // the new episode's actuator state (the step that ended the old one ran with the old m)
+#pragma unroll
+                        for (int c = 0; c < Dims<K>::NA; ++c) am[c] = al_init[c];
+#endif
                         have_spare = false;
                         rc += 1;
                     }

@@ -79,6 +79,12 @@ class SensorNoiseSpec(C.Structure):
     _fields_ = [("sigma", C.c_float * 16)]
 
 
+class ActuatorSpec(C.Structure):
+    """``rmav_actuator_spec``."""
+
+    _fields_ = [("tau", C.c_float * 4), ("init", C.c_float * 4)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -164,6 +170,10 @@ PROTOTYPES = {
     "rmav_set_sensor_noise": (C.c_int, [C.c_void_p, C.POINTER(SensorNoiseSpec)]),
     "rmav_get_sensor_noise": (C.c_int, [C.c_void_p, C.POINTER(SensorNoiseSpec), C.POINTER(C.c_int32)]),
     "rmav_observe": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
+    "rmav_set_actuator": (C.c_int, [C.c_void_p, C.POINTER(ActuatorSpec)]),
+    "rmav_get_actuator": (C.c_int, [C.c_void_p, C.POINTER(ActuatorSpec), C.POINTER(C.c_int32)]),
+    "rmav_get_actuator_state": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
+    "rmav_set_actuator_state": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

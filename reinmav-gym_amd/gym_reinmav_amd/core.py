@@ -351,6 +351,75 @@ def check_sensor_noise(sensor_noise, kind=None):
     return sensor_noise
 
 
+class Actuator:
+    """Actuator lag: a first-order motor model between the commanded action and the dynamics (``rmav_set_actuator``, include/rmav.h), run
+    inside the kernels in front of every dynamics step (every sub-step of a ``frame_skip``)::
+
+        m_c = fma(alpha_c, u_c, beta_c * m_c)        alpha_c = 1 - exp(-dt / tau_c), beta_c = exp(-dt / tau_c)
+
+    The dynamics read ``m``; stored actions, log-probabilities, the tracking reward's action cost and ``control()`` keep the command ``u``.
+    ``tau``: one time constant in seconds for every action component, or a sequence of ``nA`` (one per component), each finite and
+    ``>= 0`` (0 = no lag).  ``init``: ``m`` at the start of every episode, ``nA`` components; ``None`` = the hover action of the kind, the
+    one ``TrackingReward(act_ref=None)`` uses.  Types, lengths and finiteness are checked here, before the library is reached."""
+
+    def __init__(self, tau, init=None):
+        if isinstance(tau, (int, float, np.integer, np.floating)) and not isinstance(tau, (bool, np.bool_)):
+            self.tau = _finite_float("tau", tau)
+            taus = (self.tau,)
+        else:
+            self.tau = taus = _finite_vector("tau", tau, (2, 4))
+            if taus is None:
+                raise TypeError("tau must be a time constant in seconds or a sequence of nA of them, got None")
+        for i, v in enumerate(taus):
+            if v < 0:
+                raise ValueError(f"tau[{i}] must be >= 0, got {v!r}")
+        self.init = _finite_vector("init", init, (2, 4))
+
+    def check_kind(self, kind: int):
+        """The lengths against the kind, which the constructor does not know."""
+        if kind == A.REINMAV:
+            raise ValueError("ReinmavEnv takes no actuator lag")
+        nA = A.ACTION_DIM[kind]
+        if not isinstance(self.tau, float) and len(self.tau) != nA:
+            raise ValueError(f"tau has {len(self.tau)} components, {A.KIND_NAMES[kind]} takes {nA} actions")
+        if self.init is not None and len(self.init) != nA:
+            raise ValueError(f"init has {len(self.init)} components, {A.KIND_NAMES[kind]} takes {nA} actions")
+
+    def spec(self, kind: int, params) -> "A.ActuatorSpec":
+        """``rmav_actuator_spec`` for a handle of ``kind`` with ``params`` (the default ``init`` resolved, fp32; components past ``nA`` are 0)."""
+        self.check_kind(kind)
+        nA = A.ACTION_DIM[kind]
+        tau = (self.tau,) * nA if isinstance(self.tau, float) else self.tau
+        if self.init is not None:
+            init = self.init
+        else:   # the hover action: TrackingReward.spec's act_ref
+            gnorm = float(np.sqrt(sum(float(x) ** 2 for x in params.g_vec)))
+            init = (_finite_float("the hover thrust mass |g_vec| / thrust_scale", np.float64(params.mass) * gnorm / np.float64(params.thrust_scale)
+                                  if params.thrust_scale else float("nan")),) + (0.0,) * (nA - 1)
+        pad = (0.0,) * (4 - nA)
+        return A.ActuatorSpec((C.c_float * 4)(*(tuple(tau) + pad)), (C.c_float * 4)(*(tuple(init) + pad)))
+
+    @classmethod
+    def from_spec(cls, s: "A.ActuatorSpec", kind: int) -> "Actuator":
+        nA = A.ACTION_DIM[kind]
+        return cls(tuple(s.tau[:nA]), tuple(s.init[:nA]))
+
+    def __repr__(self):
+        return f"Actuator(tau={self.tau!r}, init={self.init!r})"
+
+
+def check_actuator(actuator, kind=None):
+    """``actuator=`` as the constructors take it: None (the action reaches the dynamics unchanged) or an :class:`Actuator`; anything else is
+    refused here."""
+    if actuator is None:
+        return None
+    if not isinstance(actuator, Actuator):
+        raise TypeError(f"actuator must be None or an Actuator, got {actuator!r}")
+    if kind is not None:
+        actuator.check_kind(kind)
+    return actuator
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
@@ -358,7 +427,8 @@ class BatchedQuadrotor:
                  auto_reset: bool = True, track_episodes: bool = True, params: Optional[A.Params] = None,
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
                  randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None,
-                 disturbance: Optional[Disturbance] = None, sensor_noise: Optional[SensorNoise] = None):
+                 disturbance: Optional[Disturbance] = None, sensor_noise: Optional[SensorNoise] = None,
+                 actuator: Optional[Actuator] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
@@ -374,12 +444,16 @@ class BatchedQuadrotor:
         None = still air.
 
         ``sensor_noise``: a :class:`SensorNoise` (Gaussian noise on every observation; :attr:`sensor_noise`), drawn inside the kernels;
-        None = exact observations."""
+        None = exact observations.
+
+        ``actuator``: an :class:`Actuator` (first-order lag between the action and the dynamics; :attr:`actuator`), run inside the kernels;
+        None = the action reaches the dynamics unchanged."""
         frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         reward = check_reward(reward, self.kind)
         disturbance = check_disturbance(disturbance, self.kind)
         sensor_noise = check_sensor_noise(sensor_noise, self.kind)
+        actuator = check_actuator(actuator, self.kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
         self.nS, self.nA = A.STATE_DIM[self.kind], A.ACTION_DIM[self.kind]
@@ -411,6 +485,8 @@ class BatchedQuadrotor:
             self.disturbance = disturbance
         if sensor_noise is not None:
             self.sensor_noise = sensor_noise
+        if actuator is not None:
+            self.actuator = actuator
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -540,6 +616,34 @@ class BatchedQuadrotor:
             out, mem = self._in(out, self._shape(self.nS, layout)) if _is_tensor(out) else (out, A.HOST)
         A.check(self._lib.rmav_observe(self._h, self._ptr(out), mem, _layout(layout)))
         return out
+
+    @property
+    def actuator(self) -> Optional[Actuator]:
+        """The :class:`Actuator` in force (``rmav_get_actuator``; the default ``init`` resolved, values as the kernels hold them in fp32), or
+        None: no lag.  Assignable at any time: switching it on sets every env's actuator state to ``init``, in stream order; assigning to an
+        env that has one changes ``tau`` and ``init`` and keeps the running state."""
+        s, on = A.ActuatorSpec(), C.c_int32()
+        A.check(self._lib.rmav_get_actuator(self._h, C.byref(s), C.byref(on)))
+        return Actuator.from_spec(s, self.kind) if on.value else None
+
+    @actuator.setter
+    def actuator(self, actuator: Optional[Actuator]):
+        if check_actuator(actuator, self.kind) is None:
+            A.check(self._lib.rmav_set_actuator(self._h, None))
+        else:
+            A.check(self._lib.rmav_set_actuator(self._h, C.byref(actuator.spec(self.kind, self.params))))
+
+    def actuator_state(self, layout: str = "aos", device_out: bool = False):
+        """The actuator state ``m`` of every env (``rmav_get_actuator_state``), ``nA`` values per env: with :attr:`actuator` the part of a
+        checkpoint that ``get_state`` does not hold.  An env without an actuator has none (``RmavError``)."""
+        m = self._new(self._shape(self.nA, layout), np.float32, device_out)
+        A.check(self._lib.rmav_get_actuator_state(self._h, self._ptr(m), A.DEVICE if device_out else A.HOST, _layout(layout)))
+        return m
+
+    def set_actuator_state(self, m, layout: str = "aos"):
+        """Restore what :meth:`actuator_state` returned (``rmav_set_actuator_state``): a NumPy array or a CUDA tensor of the layout's shape."""
+        m, mem = self._in(m, self._shape(self.nA, layout))
+        A.check(self._lib.rmav_set_actuator_state(self._h, self._ptr(m), mem, _layout(layout)))
 
     def set_policy_action_rule(self, deterministic: bool = False, clip=None):
         """What the in-kernel policy rollouts (``rmav_rollout_policy`` / ``_boot`` / ``_norm``: :class:`~gym_reinmav_amd.ppo.FusedPolicyCollector`)
