@@ -62,7 +62,8 @@
  * sharded over GPUs):
  *   reset : c2 = index of this env's reset (0 for the first),  c3 = (1<<24) | j ; block j supplies
  *           state components 4j..4j+3 as  2*u - 1,  u = (x>>8) * 2^-24          (U[-1,1), as
- *           quadrotor3d.py:184 draws every state component)
+ *           quadrotor3d.py:184 draws every state component).  A handle with a start-state spec (rmav_set_start_state) maps each of
+ *           these values into its component's range, s_c = fma(h_c, v_c, m_c): same counters, same words, no stream of its own.
  *   action: block index b = the handle's global step counter t (4-action kinds) or t >> 1 (2-action kinds, which use
  *           draws 2 (t & 1) and 2 (t & 1) + 1 of the block, i.e. one Philox call per two steps);
  *           c2 = low 32 bits of b, c3 = (2<<24) | (bits 32..47 of b) << 8 ; component i = fma(act_hi-act_lo, u_i, act_lo)
@@ -571,6 +572,46 @@ int rmav_set_actuator(rmav_handle h, const rmav_actuator_spec *spec);   /* NULL:
 int rmav_get_actuator(rmav_handle h, rmav_actuator_spec *out, int32_t *enabled);   /* either pointer may be NULL */
 int rmav_get_actuator_state(rmav_handle h, float *out, int mem, int layout);   /* nA*N floats; RMAV_ERR_INVALID without a spec */
 int rmav_set_actuator_state(rmav_handle h, const float *in, int mem, int layout);   /* RMAV_ERR_INVALID without a spec */
+
+/* ---- start-state ranges: the per-component distribution of every fresh state --------------------------------------------------------
+ * The reference's reset() draws EACH state component as U[-1, 1): a random attitude and up to 1 m/s on every axis.  With a spec set every
+ * fresh state a quadrotor handle draws is, per component c, in fp32:
+ *     v_c = the value the "reset" stream of the RNG table gives today (same counters, same words; v_c = fma(2^-23, x >> 8, -1))
+ *     s_c = fma(h_c, v_c, m_c),   h_c = (hi_c - lo_c) / 2,   m_c = (hi_c + lo_c) / 2
+ * The host computes h_c and m_c in fp64 from the spec's fp32 values, rounds each to fp32 once and passes them to the kernels as values.
+ * No random stream is added.  A start state is a pure function of (seed, global env id, reset index, spec): shard-invariant, and a
+ * checkpoint is the spec alone.  lo_c == hi_c pins component c to that value; the map is the fma of the ROUNDED h and m, not a clamp, so where
+ * the midpoint is not representable a state can leave [lo_c, hi_c] by that rounding (half an ulp of the larger bound).  The identity spec (lo = -1, hi = 1 below nS) gives h = 1,
+ * m = 0 and fma(1, v, 0) = v: such a handle stores, in every route, the bits of a handle without a spec.
+ *   - applies everywhere a fresh state is drawn: at rmav_reset, at every in-kernel auto-reset by termination or by time-limit truncation,
+ *     in the spare state a fused launch draws up front (n_steps >= 8) and in the on-demand draw of a second termination inside one launch.
+ *   - applies nowhere else: the dynamics, rewards, done, steps_beyond_done, reset counts and every other stream (action, policy noise, env
+ *     constants, wind, gust, sensor) are unchanged functions of their inputs; rmav_step_final's final_obs_out is the pre-reset state, as
+ *     ever; rmav_set_state, rmav_seed, rmav_set_reset_counts and rmav_set_step_count do not consult the spec.  With sensor noise the
+ *     observation a reset emits is the noisy observation of the mapped state.
+ *   - rmav_set_start_state is host state plus the device copy below: it draws NOTHING and does not touch the running episodes, which were
+ *     drawn under whatever was in force when they began (rmav_create has drawn reset 0 with the reference's rule: call rmav_reset behind the
+ *     set to start every env under the spec, at reset index 1).
+ * Launches of such a handle run kernels of their own, cut from the lagged ones, whose launch rules they share: the
+ * one-wavefront fused rollouts with ONE store policy (fused = 0 gives the bits of fused = 1; a chunk-major call is one launch per chunk);
+ * rmav_reset runs k_reset_ss.  A handle without actuator lag passes a wave-uniform flag that GATES the filter: the kernels then neither
+ * load nor store a filter state and hand the command itself to the dynamics - a -0.0 action keeps its sign, no handle-owned m exists, and
+ * rmav_get_actuator_state stays refused.  One without sensor noise skips the draw, one without a disturbance passes the all-zero one.
+ * rmav_rollout_policy / _boot / _norm run the three actors the actuator lag runs (RMAV_POLICY_FP32_MFMA, RMAV_POLICY_F16_MFMA,
+ * RMAV_POLICY_F16_SHARED); the other precisions return RMAV_ERR_INVALID with a message that names the feature.
+ * Validation: every value finite, lo_c <= hi_c, components >= nS zero; RMAV_REINMAV takes no spec (its reset() is a no-op); anything else
+ * is RMAV_ERR_INVALID and the spec in force stays.  NULL switches the feature off: such a handle, like one that never set a spec, launches
+ * exactly the kernels it launched before.
+ * Ordering and capture as rmav_set_reward: the step kernels, the one-wavefront rollouts and k_reset_ss take h / m by value; the policy
+ * kernels read a device copy in the handle's arena, which rmav_set_start_state rewrites in stream order with one small launch.  It neither
+ * allocates nor synchronises.
+ * rmav_get_start_state: the last spec set (zeros before the first), and whether it is in force; either pointer may be NULL.
+ * Callers detect the feature by the symbols; RMAV_VERSION is unchanged. */
+typedef struct rmav_start_state_spec {
+    float lo[16], hi[16];         /* per state component; components >= nS must be 0 */
+} rmav_start_state_spec;          /* 128 bytes */
+int rmav_set_start_state(rmav_handle h, const rmav_start_state_spec *spec);   /* NULL: the reference's U[-1,1) (the default) */
+int rmav_get_start_state(rmav_handle h, rmav_start_state_spec *out, int32_t *enabled);   /* either pointer may be NULL */
 
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that

@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->start_on) {   // a handle with a start-state spec: k_rollout_ss, which takes the actuator lag (switched off without a spec) and all it takes as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_start_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no start-state kernel for action mode %d", MODE);
+        }
     } else if (h->actuator_on) {   // a handle with actuator lag: k_rollout_al, which takes the sensor noise (switched off without a spec) and all it takes as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_actuator_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
@@ -353,8 +359,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
     // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
     // One with a disturbance (rmav_set_disturbance): k_rollout_ds.  One with sensor noise (rmav_set_sensor_noise): k_rollout_sn.
-    // One with actuator lag (rmav_set_actuator): k_rollout_al.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on)) {
+    // One with actuator lag (rmav_set_actuator): k_rollout_al.  One with a start-state spec (rmav_set_start_state): k_rollout_ss.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -431,7 +437,11 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->actuator_on) {   // a handle with actuator lag: k_step_al for every batch size; the control() form is k_control (the command) behind it
+    if (h->start_on) {   // a handle with a start-state spec: k_step_ss for every batch size; the control() form is k_control behind it
+        if (int rc = rmav_launch_start_step(h, a, bs, FinalArgs{})) return rc;
+        if (ctrl)
+            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
+    } else if (h->actuator_on) {   // a handle with actuator lag: k_step_al for every batch size; the control() form is k_control (the command) behind it
         if (int rc = rmav_launch_actuator_step(h, a, bs, FinalArgs{})) return rc;
         if (ctrl)
             if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
@@ -480,7 +490,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->actuator_on) {
+    if (h->start_on) {
+        if (int rc = rmav_launch_start_step(h, a, bs, fa)) return rc;
+    } else if (h->actuator_on) {
         if (int rc = rmav_launch_actuator_step(h, a, bs, fa)) return rc;
     } else if (h->sensor_on) {
         if (int rc = rmav_launch_sensor_step(h, a, bs, fa)) return rc;
@@ -511,6 +523,7 @@ int launch_rollout(rmav_handle h, int mode, const RolloutArgs &a) {
 }
 
 int launch_reset(rmav_handle h, float *obs_dev, int layout) {
+    if (h->start_on) return rmav_launch_start_reset(h, obs_dev, layout);   // a handle with a start-state spec: k_reset_ss
     const uint32_t fl = (h->flags & F_TRACK) | (layout == RMAV_AOS ? F_AOS : 0u);
     return dispatch_kind<ALL_KINDS>(h->kind, [&](auto k) {
         hipLaunchKernelGGL((k_reset<decltype(k)::value>), grid_for(h), dim3(block_size(h)), 0, h->stream, h->state, h->n, h->rec, h->ep_ret,
@@ -845,6 +858,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         const size_t o_sn = off; off += (kind != RMAV_REINMAV) ? up(sizeof(SensorDev)) : 0;
         // (... and of an actuator spec's coefficients)
         const size_t o_al = off; off += (kind != RMAV_REINMAV) ? up(sizeof(ActuatorDev)) : 0;
+        // (... and of a start-state spec's)
+        const size_t o_ss = off; off += (kind != RMAV_REINMAV) ? up(sizeof(StartDev)) : 0;
         if (hipMalloc(&h->arena, off) != hipSuccess) {
             (void)hipGetLastError();
             h->arena = nullptr;
@@ -857,7 +872,7 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         h->totals = (Totals *)(b + o_tot);
         if (kind == RMAV_REINMAV) h->env_time = (double *)(b + o_time);
         else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds), h->sensor_dev = (SensorDev *)(b + o_sn),
-                 h->actuator_dev = (ActuatorDev *)(b + o_al);
+                 h->actuator_dev = (ActuatorDev *)(b + o_al), h->start_dev = (StartDev *)(b + o_ss);
         if (tr) {
             h->ep_ret = (float *)(b + o_er);
             h->last_ret = (float *)(b + o_lr);
@@ -1154,7 +1169,7 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
     // (not rmav_step_control of a handle with a tracking reward, a disturbance, sensor noise or actuator lag: k_control runs behind k_step_rw / k_step_ds / k_step_sn / k_step_al, which would publish too early)
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on))) {
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on))) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {
@@ -1666,6 +1681,44 @@ int rmav_set_actuator_state(rmav_handle h, const float *in, int mem, int layout)
     hipLaunchKernelGGL(k_aos_to_soa, grid_for(h), dim3(block_size(h)), 0, h->stream, src, h->actuator_m, h->n, nA);
     HIP_TRY(hipGetLastError());
     if (mem == RMAV_HOST) HIP_TRY(hipStreamSynchronize(h->stream));
+    return RMAV_OK;
+}
+
+// Start-state ranges: the spec on the handle.  Every stepping launch and rmav_reset read start_on (launch_rollout_kms, launch_step_k,
+// launch_step_final_k, launch_reset; rmav_ppo_abi.hip) and derive h / m from the spec when they are enqueued; the policy kernels read the
+// device copy in the arena, which every set rewrites in stream order with one small launch.  Nothing is drawn, allocated or synchronised.
+int rmav_set_start_state(rmav_handle h, const rmav_start_state_spec *spec) {
+    CHECK_HANDLE(h);
+    if (!spec) {   // none: the launches of a handle that never had a spec
+        h->start_on = 0;
+        return RMAV_OK;
+    }
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no start-state spec (its reset() is a no-op)");
+    const int nS = kStateDim[h->kind];
+    for (int c = 0; c < 16; ++c) {
+        const float lo = spec->lo[c], hi = spec->hi[c];
+        if (!(lo - lo == 0.0f) || !(hi - hi == 0.0f))
+            return rmav_fail(RMAV_ERR_INVALID, "every lo and hi of a start-state spec must be finite (component %d is not)", c);
+        if (!(lo <= hi)) return rmav_fail(RMAV_ERR_INVALID, "start-state lo[%d] = %g is above hi[%d] = %g", c, (double)lo, c, (double)hi);
+        if (c >= nS && (lo != 0.0f || hi != 0.0f))
+            return rmav_fail(RMAV_ERR_INVALID, "start-state lo[%d] = %g, hi[%d] = %g: the kind has %d state components, the others must be 0", c, (double)lo, c,
+                             (double)hi, nS);
+    }
+    const rmav_start_state_spec old = h->start;
+    h->start = *spec;
+    if (int rc = rmav_sync_start_dev(h)) {   // the policy kernels' copy, in stream order
+        h->start = old;
+        if (h->start_on) (void)rmav_sync_start_dev(h);
+        return rc;
+    }
+    h->start_on = 1;
+    return RMAV_OK;
+}
+
+int rmav_get_start_state(rmav_handle h, rmav_start_state_spec *out, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (out) *out = h->start;   // (the last spec set - zeros before the first - also while it is switched off)
+    if (enabled) *enabled = h->start_on;
     return RMAV_OK;
 }
 

@@ -1,8 +1,8 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus nine that only launch kernels (rmav_policy_abi.hip,
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus eleven that only launch kernels (rmav_policy_abi.hip,
 // rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip, rmav_sensor_abi.hip, rmav_sensor_policy_abi.hip,
-// rmav_actuator_abi.hip, rmav_actuator_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// rmav_actuator_abi.hip, rmav_actuator_policy_abi.hip, rmav_start_abi.hip, rmav_start_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -132,7 +132,22 @@ struct rmav_env_s {
     rmav_actuator_spec actuator;
     float *actuator_m;
     rmav::ActuatorDev *actuator_dev;   // in the arena next to sensor_dev (k_set_actuator rewrites it)
+    // start-state ranges (rmav_set_start_state): the spec and whether one is set.  start_on routes every stepping launch to the *_ss
+    // kernels - before the actuator lag, which those kernels take as well (switched off by a wave-uniform flag without a spec) - and
+    // rmav_reset to k_reset_ss.  The step kernels, the one-wavefront rollouts and k_reset_ss take h / m by value, derived from the spec at the
+    // launch; the policy kernels read start_dev, which every set rewrites in stream order.
+    int32_t start_on;
+    rmav_start_state_spec start;
+    rmav::StartDev *start_dev;   // in the arena next to actuator_dev (k_set_start_state rewrites it)
 };
+static_assert(sizeof(rmav_start_state_spec) == 128, "thirty-two floats");
+// h and m of every component (from the spec's lo and hi, in fp64, each rounded once), as the *_ss kernels take them
+inline rmav::StartCoef start_coef(const rmav_env_s *h) {
+    rmav::StartCoef c{};
+    for (int i = 0; i < 16; ++i) rmav::start_coeffs(h->start.lo[i], h->start.hi[i], c.h[i], c.m[i]);
+    return c;
+}
+inline rmav::StartArgs start_args(const rmav_env_s *h) { return rmav::StartArgs{start_coef(h), h->actuator_on ? 1u : 0u, 0u}; }
 static_assert(sizeof(rmav_actuator_spec) == 32, "eight floats");
 // alpha, beta (from the spec's tau and the dt in force) and init, as the *_al kernels take them
 inline rmav::ActuatorCoef actuator_coef(const rmav_env_s *h) {
@@ -215,6 +230,23 @@ inline rmav::PolicyActuatorArgs policy_actuator_args(const rmav_env_s *h, uint64
     const rmav::DisturbArgs d = disturb_or_calm(h, t0);
     return rmav::PolicyActuatorArgs{r.noise, r.lo, r.hi, h->frame_skip, h->reward_dev, h->disturb_on ? h->disturb_dev : &h->actuator_dev->calm, d.b0, d.phase0,
                                     h->sensor_on ? 1u : 0u, &h->sensor_dev->sn, &h->actuator_dev->c, h->actuator_m};
+}
+// what the *_ss kernels take in ActuatorArgs' place: the handle's, or - without actuator lag - zeros and no array (StartArgs::al_on = 0: unread)
+inline rmav::ActuatorArgs start_actuator_args(const rmav_env_s *h) {
+    if (h->actuator_on) return actuator_args(h);
+    return rmav::ActuatorArgs{rmav::ActuatorCoef{}, nullptr, h->sensor_on ? 1u : 0u, 0u};
+}
+// what the policy kernels of a handle with a start spec take: PolicyActuatorArgs - the calm disturbance spec of a handle without a disturbance
+// sits in actuator_dev if the handle has actuator lag (k_set_actuator wrote it), else in start_dev (k_set_start_state did); without actuator
+// lag al points at memory of the arena nobody wrote, whose values the kernels load and do not use, and m is NULL and untouched - then the
+// device copy of h / m
+inline rmav::PolicyStartArgs policy_start_args(const rmav_env_s *h, uint64_t t0) {
+    rmav::PolicyActuatorArgs pa = policy_actuator_args(h, t0);
+    if (!h->actuator_on) {
+        if (!h->disturb_on) pa.ds = &h->start_dev->calm;
+        pa.m = nullptr;
+    }
+    return rmav::PolicyStartArgs{pa, &h->start_dev->c, h->actuator_on ? 1u : 0u, 0u};
 }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
@@ -450,3 +482,15 @@ RMAV_INTERNAL int rmav_sync_actuator_dev(rmav_handle h);
 // rmav_actuator_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_al, k_rollout_pair_al, k_rollout_pair_shared_al -
 // with rmav_launch_sensor_policy_rollout's arguments.
 RMAV_INTERNAL int rmav_launch_actuator_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
+
+// rmav_start_abi.hip: the launches of a handle with a start-state spec (rmav_set_start_state), shaped as the lagged ones, whose arguments they
+// take as well (a handle without actuator lag: al_on = 0).  _rollout: ONE launch of k_rollout_ss<K, mode, time limit?, reward?> (one store
+// policy); _step: k_step_ss at bs threads per workgroup; _reset: k_reset_ss, launch_reset's arguments; _sync: k_set_start_state, the handle's
+// device copy of the coefficients (start_dev) rewritten in stream order - no allocation, no synchronisation.  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_start_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_start_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_start_reset(rmav_handle h, float *obs_dev, int layout);
+RMAV_INTERNAL int rmav_sync_start_dev(rmav_handle h);
+// rmav_start_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_ss, k_rollout_pair_ss, k_rollout_pair_shared_ss -
+// with rmav_launch_sensor_policy_rollout's arguments.
+RMAV_INTERNAL int rmav_launch_start_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);

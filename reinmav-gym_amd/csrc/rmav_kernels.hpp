@@ -31,6 +31,7 @@
 #include "rmav_disturb.hpp"
 #include "rmav_sensor.hpp"
 #include "rmav_actuator.hpp"
+#include "rmav_start.hpp"
 #include "rmav_policy.hpp"
 #include "rmav_policy_mfma.hpp"
 #include "rmav_policy_mfma32.hpp"
@@ -42,6 +43,11 @@
 // the filter state m beside the state, the filter in front of every dynamics sub-step, m = init at a reset, and the noise draw behind ONE
 // wave-uniform branch per site (al.sn_on: a handle with lag and no sensor noise does not pay it).
 #define RMAV_ROLLOUT_AL 0
+// RMAV_ROLLOUT_SS: likewise the start-state ranges of the *_ss wrappers (rmav_set_start_state; rmav_start.hpp), which are cut from the *_al
+// bodies: every fresh state - the launch-head spare and the on-demand draw of rmav_rollout_reset.inc - goes through start_apply, and the
+// filter, the loads and the stores of its state sit behind ONE wave-uniform flag (ss_al: a handle with a start spec and no actuator lag
+// hands the command itself to the dynamics).  In every other kernel that flag is the constant true.
+#define RMAV_ROLLOUT_SS 0
 
 namespace rmav {
 
@@ -404,6 +410,20 @@ struct PolicyActuatorArgs {
     const SensorArgs *sn;
     const ActuatorCoef *al;
     float *m;
+};
+// ... and the POLICY kernels of a handle with a start-state spec (the *_ss policy families): PolicyActuatorArgs with the handle's device copy
+// of the map's coefficients behind it and whether the handle has actuator lag.  StartDev is that copy (rmav_env_s::start_dev, rewritten in
+// stream order by k_set_start_state): h, m and - for a handle with neither a disturbance nor an actuator spec - the calm disturbance spec ds
+// then points at.
+struct StartDev {
+    StartCoef c;
+    DisturbSpec calm;
+};
+struct PolicyStartArgs {
+    PolicyActuatorArgs pa;
+    const StartCoef *ss;
+    uint32_t al_on;
+    uint32_t _pad;
 };
 // the observation row of the *_al kernels: the noisy one, or - a handle without sensor noise, wave-uniform - the state itself
 template <int NS>
@@ -911,6 +931,80 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 #define RMAV_ROLLOUT_SN 0
 }
 
+// The one-wavefront kernels of a handle with a start-state spec (rmav_set_start_state; StartArgs in rmav_start.hpp): k_rollout_al's body and
+// argument list with the map behind it.  Every fresh state the launch draws - the spare at its head, the on-demand draw of a second
+// termination - is fma(h, v, m) of what reset_state<K> draws; the coefficients are read where a state is drawn.  A handle without actuator
+// lag passes ss.al_on = 0 (no filter, no filter state), one without sensor noise al.sn_on = 0, one without a disturbance the all-zero spec.
+template <int K, int MODE, bool TL, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_ss(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn,
+                                                       const ActuatorArgs al, const StartArgs ss) {
+    constexpr int ST = ST_DEFAULT;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, DS = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    const ActuatorCoef &alc = al.c;
+    const float *const al_init = al.c.init;
+    float *const al_m = al.m;
+    const uint32_t al_sn = al.sn_on;
+    const StartCoef &ssc = ss.c;
+    const uint32_t ss_al = ss.al_on;
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "launches with a start spec run the one-wavefront kernels");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 1
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 0
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 0
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_al whose fresh states go through the map.  The coefficients are read
+// through the handle's device copy, where a state is drawn.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_ss(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicyStartArgs pss) {
+    const PolicyActuatorArgs &ps = pss.pa;
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    const ActuatorCoef &alc = *ps.al;
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    const StartCoef &ssc = *pss.ss;
+    const uint32_t ss_al = pss.al_on;
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 1
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 0
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 0
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
 // reset_state<K> for the lanes of a wavefront that need it, computed cooperatively (all 64 lanes must be active).
 // Philox4x32-10 is ~20 quarter-rate 32x32->64 multiplies per call and reset_state needs ceil(nS / 4) calls (the counter
 // word c3 selects the block of four components); executed by a whole wavefront for the one or two lanes whose env has
@@ -987,14 +1081,19 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // this step (a.t0 + 1); the state stored in place stays the true one.
 // AL: the handle has actuator lag (al; k_step_al): the filter state m is loaded beside the state, advanced in front of every dynamics
 // sub-step - which reads m, not the action -, set to init where the env is reset and stored in place; al.sn_on = 0 skips the noise draw.
+// SS: the handle has a start-state spec (ss; k_step_ss): a finishing lane maps what it picked up from reset_state_wave (start_apply);
+// ss.al_on = 0 skips the filter and the loads and stores of its state (al.m may be NULL).
 template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false, bool DS = false,
-          bool SN = false, bool AL = false>
+          bool SN = false, bool AL = false, bool SS = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
                                           const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
                                           [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{},
                                           [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}, [[maybe_unused]] const SensorArgs &sn = SensorArgs{},
-                                          [[maybe_unused]] const ActuatorArgs &al = ActuatorArgs{}) {
+                                          [[maybe_unused]] const ActuatorArgs &al = ActuatorArgs{}, [[maybe_unused]] const StartArgs &ss = StartArgs{}) {
     static_assert(!RW || FS, "the tracking reward is evaluated in the sub-step loop");
+    static_assert(!SS || AL, "the step of a handle with a start spec is cut from the lagged body");
+    // (wave-uniform; the constant true in every kernel but k_step_ss)
+    [[maybe_unused]] const bool al_live = !SS || ss.al_on != 0u;
     static_assert(!AL || SN, "the lagged step is cut from the noisy body");
     static_assert(!SN || (DS && FIN), "the noisy step is cut from the disturbed body");
     static_assert(!DS || (FS && DR && !CTRL), "the disturbed step is cut from the most general body: the running reset index, eagerly; k_control behind it");
@@ -1054,9 +1153,15 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     }
     [[maybe_unused]] float am[AL ? NA : 1];   // AL: the filter state of this env
     if constexpr (AL) {
-        const rsrc_t r_m = make_rsrc(al.m);
+        if constexpr (SS) {
 #pragma unroll
-        for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);
+            for (int c = 0; c < NA; ++c) am[c] = 0.0f;
+        }
+        if (al_live) {
+            const rsrc_t r_m = make_rsrc(al.m);
+#pragma unroll
+            for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);
+        }
     }
     float er = 0.0f;
     if (track) er = buf_ld(make_rsrc(a.ep_ret), off, 0);
@@ -1111,6 +1216,10 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
                 bool term;
                 if constexpr (AL) {   // the filter advances in front of every dynamics sub-step, which reads m; c_rw keeps the command
                     actuator_step<NA>(al.c, am, act);
+                    if constexpr (SS) {   // (without actuator lag: the command itself - a select, as in rmav_rollout_body.inc)
+#pragma unroll
+                        for (int c = 0; c < NA; ++c) am[c] = al_live ? am[c] : act[c];
+                    }
                     Env<K>::step(s, am, pl, dist, term);
                 } else {
                     Env<K>::step(s, act, pl, dist, term);
@@ -1263,6 +1372,9 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     }
     if (auto_reset)   // wave-uniform; every lane takes part
         reset_state_wave<K>(a.seed, a.env_base + (uint64_t)(gi - (threadIdx.x & 63u)), rc, done && valid, s);
+    if constexpr (SS) {   // the start-state spec: the finishing lane maps the v it picked up
+        if (auto_reset && done && valid) start_apply<NS>(ss.c, s);
+    }
     if constexpr (DR) {
         // the new episode's constants: the tag-4 block of the reset index its state was drawn with.  The step above used the old
         // ones; the control() below, on the fresh state, uses these.
@@ -1274,7 +1386,7 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
     }
     if (valid) store_state();
     if constexpr (AL) {   // the filter state in place: init where the env was reset (the step that ended the episode ran with the old m)
-        if (valid) {
+        if (valid && al_live) {
             const rsrc_t r_m = make_rsrc(al.m);
 #pragma unroll
             for (int c = 0; c < NA; ++c) buf_st_aux<AUX>(r_m, off, (uint32_t)c * col, (auto_reset && done) ? al.c.init[c] : am[c]);
@@ -1508,6 +1620,25 @@ __global__ __launch_bounds__(kBlock) void k_step_al(float *state_pl, int64_t n_p
     step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn, al);
 }
 
+// The single-step kernel of a handle with a start-state spec (rmav_set_start_state): k_step_al's body and argument list with the map behind
+// the cooperative reset draw.
+template <int K, bool TL, bool RW>
+__global__ __launch_bounds__(kBlock) void k_step_ss(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn,
+                                                    const ActuatorArgs al, const StartArgs ss) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn, al, ss);
+}
+
 // rmav_observe: the observation of every env's current state at the step counter b, out nS * n floats, feature-major or - aos - batch-major.
 // Every route that emits an observation stores the bits this kernel gives right after it.
 template <int K>
@@ -1553,6 +1684,38 @@ __global__ __launch_bounds__(kBlock) void k_reset(float *state, int64_t n, EnvRe
         q.ep_start = ep_clock;   // running length 0
     }
     rec[i] = q;                  // (steps_beyond_done is NOT cleared: quadrotor3d.py:182-185 does not)
+    if (obs_out) {
+        if (flags & F_AOS) {
+#pragma unroll
+            for (int c = 0; c < NS; ++c) obs_out[i * NS + c] = s[c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < NS; ++c) obs_out[(int64_t)c * n + i] = s[c];
+        }
+    }
+}
+
+// reset() of every env of a handle with a start-state spec (the four quadrotor kinds): k_reset whose fresh state goes through the map
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_reset_ss(float *state, int64_t n, EnvRec *rec, float *ep_ret, uint32_t ep_clock, float *obs_out, uint64_t seed,
+                                                     uint64_t env_base, uint32_t flags, const StartCoef ss) {
+    static_assert(K != REINMAV, "ReinmavEnv takes no start spec");
+    constexpr int NS = Dims<K>::NS;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s[NS];
+    EnvRec q = rec[i];
+    const uint32_t rc = q.reset_cnt;
+    reset_state<K>(seed, env_base + (uint64_t)i, rc, s);
+    start_apply<NS>(ss, s);
+#pragma unroll
+    for (int c = 0; c < NS; ++c) state[(int64_t)c * n + i] = s[c];
+    q.reset_cnt = rc + 1;
+    if (flags & F_TRACK) {
+        ep_ret[i] = 0.0f;
+        q.ep_start = ep_clock;   // running length 0
+    }
+    rec[i] = q;                  // (steps_beyond_done is NOT cleared, as in k_reset)
     if (obs_out) {
         if (flags & F_AOS) {
 #pragma unroll

@@ -38,6 +38,10 @@
                         bool term;
 #if RMAV_PAIR_AL   // actuator lag: the filter advances in front of every dynamics sub-step, which reads m; c_rw and the stored action keep the command
                         actuator_step<NA>(alc, am, ca);
+#if RMAV_PAIR_SS   // (a start spec without actuator lag: the command itself - a select, as in rmav_rollout_body.inc)
+#pragma unroll
+                        for (int c = 0; c < NA; ++c) am[c] = al_live ? am[c] : ca[c];
+#endif
                         Env<K>::step(s, am, p, dist, term);
 #else
                         Env<K>::step(s, ca, p, dist, term);

@@ -51,6 +51,9 @@
 #endif
     if (K != REINMAV && auto_reset && T >= 8) {
         reset_state<K>(a.seed, env_id, rc, spare);
+#if RMAV_PAIR_SS   // the spare is a START state: the draw under the handle's ranges (clone lanes compute the bits of the env they copy)
+        start_apply<NS>(ssc, spare);
+#endif
 #if RMAV_PAIR_DR
         range_draw(dr, a.seed, env_id, rc, spare_pe);
 #endif
@@ -67,7 +70,14 @@
 #if RMAV_PAIR_AL   // the *_al kernels (alc: ActuatorCoef, al_m: the handle's [nA][N] array): the filter state of this env, which belongs to the
                    // wavefront that integrates - in registers through the launch, stored by rmav_pair_epilogue.inc
     float am[NA];
-    {
+#if RMAV_PAIR_SS   // the *_ss kernels (ssc: StartCoef, ss_al: the handle has actuator lag, wave-uniform): without it no filter state exists
+    const bool al_live = ss_al != 0u;
+#pragma unroll
+    for (int c = 0; c < NA; ++c) am[c] = 0.0f;
+#else
+    constexpr bool al_live = true;
+#endif
+    if (al_live) {
         const rsrc_t r_m = make_rsrc(al_m);
 #pragma unroll
         for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);

@@ -9,7 +9,7 @@
 #pragma unroll
     for (int c = 0; c < NS; ++c) buf_st(r_state, off, (uint32_t)c * col, s[c]);
 #if RMAV_PAIR_AL   // the filter state, with the state (vector stores; clone lanes store the bits of the lane they copy, as for the state)
-    {
+    if (al_live) {
         const rsrc_t r_m = make_rsrc(al_m);
 #pragma unroll
         for (int c = 0; c < NA; ++c) buf_st(r_m, off, (uint32_t)c * col, am[c]);

@@ -32,6 +32,9 @@
             if (__ballot(done && !have_spare) != 0) {
                 if (!have_spare) {   // every lane that has used its spare up (see k_rollout)
                     reset_state<K>(a.seed, env_id, rc, spare);
+#if RMAV_PAIR_SS   // a START state: the draw under the handle's ranges
+                    start_apply<NS>(ssc, spare);
+#endif
 #if RMAV_PAIR_DR
                     range_draw(dr, a.seed, env_id, rc, spare_pe);
 #endif

@@ -108,9 +108,12 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
     // ... and one with a disturbance: the *_ds kernels are those with g_vec + d
     // ... and one with sensor noise: k_rollout_nrm_sn is the disturbed kernel whose nets read the noisy observation
     // ... and one with actuator lag: the *_al kernels are the noisy ones with the filter between the clipped action and the dynamics
-    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on;
+    // ... and one with a start-state spec: the *_ss kernels are the lagged ones whose fresh states go through the map
+    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on;
     if (skipped) {
-        if (h->actuator_on) {
+        if (h->start_on) {
+            if (int rc = need_variants(precision, "a handle with a start-state spec (rmav_set_start_state)", "start-state")) return rc;
+        } else if (h->actuator_on) {
             if (int rc = need_variants(precision, "a handle with actuator lag (rmav_set_actuator)", "actuator-lag")) return rc;
         } else if (h->sensor_on) {
             if (int rc = need_variants(precision, "a handle with sensor noise (rmav_set_sensor_noise)", "sensor-noise")) return rc;
@@ -135,7 +138,9 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
             bt = &bt_r;
         }
     }
-    if (h->actuator_on) {
+    if (h->start_on) {
+        if (int rc = rmav_launch_start_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
+    } else if (h->actuator_on) {
         if (int rc = rmav_launch_actuator_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
     } else if (h->sensor_on) {
         if (int rc = rmav_launch_sensor_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;

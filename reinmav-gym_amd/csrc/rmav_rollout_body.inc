@@ -480,7 +480,21 @@
 #if RMAV_ROLLOUT_AL   // the *_al wrappers (alc: ActuatorCoef, al_m: the handle's [nA][N] array, al_sn: the handle has sensor noise): the filter state
                       // of this env rides in registers for the whole launch - loaded here, stored with the state behind the step loop
         float am[NA];
-        {
+#if RMAV_ROLLOUT_SS   // the *_ss wrappers (ssc: StartCoef, ss_al: the handle has actuator lag, wave-uniform): without it no filter state exists
+        const bool al_live = ss_al != 0u;
+#pragma unroll
+        for (int c = 0; c < NA; ++c) am[c] = 0.0f;
+#else
+        constexpr bool al_live = true;
+#endif
+#if RMAV_ROLLOUT_SS   // (the actor through the plain pointer, as for its store behind the step loop: with the descriptor under the branch
+                      // one quadrotor2d-slungload kernel kept an unused 48-byte stack frame)
+        if (al_live && is_policy(MODE)) {
+#pragma unroll
+            for (int c = 0; c < NA; ++c) am[c] = al_m[(int64_t)c * n + li];
+        } else
+#endif
+        if (al_live) {
             const rsrc_t r_m = make_rsrc(al_m);
 #pragma unroll
             for (int c = 0; c < NA; ++c) am[c] = buf_ld(r_m, off, (uint32_t)c * col);
@@ -513,10 +527,16 @@
             if constexpr (SPARE_LDS) {
                 float sp[NS];
                 reset_state<K>(a.seed, env_id, rc, sp);
+#if RMAV_ROLLOUT_SS
+                start_apply<NS>(ssc, sp);
+#endif
 #pragma unroll
                 for (int c = 0; c < NS; ++c) lds_spare[c * 64] = sp[c];   // read back by this lane only: no barrier needed
             } else {
                 reset_state<K>(a.seed, env_id, rc, spare);
+#if RMAV_ROLLOUT_SS   // the spare is a START state: the draw under the handle's ranges (clone lanes compute the bits of the env they copy)
+                start_apply<NS>(ssc, spare);
+#endif
             }
             if constexpr (DR) range_draw(dr, a.seed, env_id, rc, spare_pe);   // the spare constants with the spare state
             if constexpr (DS) wind_draw(ds.spec(), a.seed, env_id, rc, spare_w);      // ... and the spare wind
@@ -758,6 +778,11 @@
                             bool term;
 #if RMAV_ROLLOUT_AL   // actuator lag: the filter advances in front of every dynamics sub-step, which reads m; c_rw and the stored action keep the command
                             actuator_step<NA>(alc, am, ca);
+#if RMAV_ROLLOUT_SS   // (a start spec without actuator lag: the command itself - a select, not a branch around the filter, which cost the
+                      // quadrotor3d-slungload buffer kernels six registers and a wave of occupancy)
+#pragma unroll
+                            for (int c = 0; c < NA; ++c) am[c] = al_live ? am[c] : ca[c];
+#endif
                             Env<K>::step(s, am, p, dist, term);
 #else
                             Env<K>::step(s, ca, p, dist, term);
@@ -1039,7 +1064,8 @@
 #if RMAV_ROLLOUT_AL   // the filter state, with the state (vector stores; clone lanes store the bits of the lane they copy, as for the state).  The
                       // actor through the plain pointer: with a third buffer descriptor here one quadrotor2d-slungload kernel kept a 48-byte
                       // stack frame; the others through a descriptor: the 64-bit address costs quadrotor3d-slungload a wave of occupancy
-        if constexpr (is_policy(MODE)) {
+        if (!al_live) {
+        } else if constexpr (is_policy(MODE)) {
 #pragma unroll
             for (int c = 0; c < NA; ++c) al_m[(int64_t)c * n + li] = am[c];
         } else {

@@ -12,6 +12,9 @@
                         if (!have_spare) {
                             float sp[NS];
                             reset_state<K>(a.seed, env_id, rc, sp);
+#if RMAV_ROLLOUT_SS   // a START state: the draw under the handle's ranges
+                            start_apply<NS>(ssc, sp);
+#endif
 #pragma unroll
                             for (int c = 0; c < NS; ++c) {
                                 if constexpr (SPARE_LDS) lds_spare[c * 64] = sp[c];

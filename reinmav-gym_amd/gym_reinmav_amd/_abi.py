@@ -85,6 +85,12 @@ class ActuatorSpec(C.Structure):
     _fields_ = [("tau", C.c_float * 4), ("init", C.c_float * 4)]
 
 
+class StartStateSpec(C.Structure):
+    """``rmav_start_state_spec``."""
+
+    _fields_ = [("lo", C.c_float * 16), ("hi", C.c_float * 16)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -174,6 +180,8 @@ PROTOTYPES = {
     "rmav_get_actuator": (C.c_int, [C.c_void_p, C.POINTER(ActuatorSpec), C.POINTER(C.c_int32)]),
     "rmav_get_actuator_state": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
     "rmav_set_actuator_state": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
+    "rmav_set_start_state": (C.c_int, [C.c_void_p, C.POINTER(StartStateSpec)]),
+    "rmav_get_start_state": (C.c_int, [C.c_void_p, C.POINTER(StartStateSpec), C.POINTER(C.c_int32)]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

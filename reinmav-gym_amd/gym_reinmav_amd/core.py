@@ -420,6 +420,125 @@ def check_actuator(actuator, kind=None):
     return actuator
 
 
+class StartState:
+    """Start-state ranges: the per-component distribution of every fresh state (``rmav_set_start_state``, include/rmav.h), applied inside the
+    kernels wherever a state is drawn - ``reset()`` and every in-kernel auto-reset::
+
+        s_c = fma(h_c, v_c, m_c)        h_c = (hi_c - lo_c) / 2, m_c = (hi_c + lo_c) / 2, v_c the reference's U[-1, 1) draw
+
+    ``lo``, ``hi``: each one value for every state component or a sequence of ``nS`` (one per component), finite, ``lo <= hi``;
+    ``lo == hi`` pins a component.  ``StartState(-1, 1)`` is the reference's distribution, bit for bit.  Types, lengths, finiteness and
+    the order are checked here, before the library is reached."""
+
+    MAX_DIM = 16
+
+    def __init__(self, lo, hi):
+        self.lo, self.hi = self._bound("lo", lo), self._bound("hi", hi)
+        los, his = self._pair()
+        for i, (a, b) in enumerate(zip(los, his)):
+            if a > b:
+                raise ValueError(f"lo[{i}] = {a!r} is above hi[{i}] = {b!r}")
+
+    @classmethod
+    def _bound(cls, name, v):
+        if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)):
+            return _finite_float(name, v)
+        if isinstance(v, np.ndarray):
+            v = v.tolist()
+        if v is None or isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+            raise TypeError(f"{name} must be a number or a sequence of nS of them, got {v!r}")
+        if not 1 <= len(v) <= cls.MAX_DIM:
+            raise ValueError(f"{name} must have nS (1 .. {cls.MAX_DIM}) components, got {len(v)}")
+        return tuple(_finite_float(f"{name}[{i}]", x) for i, x in enumerate(v))
+
+    def _pair(self, n=None):
+        """``lo`` and ``hi`` as two tuples of one length (``n`` if both are scalars)."""
+        lens = {len(x) for x in (self.lo, self.hi) if not isinstance(x, float)}
+        if len(lens) > 1:
+            raise ValueError(f"lo has {len(self.lo)} components and hi has {len(self.hi)}")
+        n = lens.pop() if lens else (n or 1)
+        return tuple((x,) * n if isinstance(x, float) else x for x in (self.lo, self.hi))
+
+    @classmethod
+    def around(cls, state, spread) -> "StartState":
+        """``lo = state - spread``, ``hi = state + spread``: ``state`` one value per component, ``spread`` (``>= 0``) a scalar or per component."""
+        st = cls._bound("state", state)
+        sp = cls._bound("spread", spread)
+        if isinstance(st, float):
+            raise TypeError("state must be a sequence of nS components")
+        sp = (sp,) * len(st) if isinstance(sp, float) else sp
+        if len(sp) != len(st):
+            raise ValueError(f"spread has {len(sp)} components and state has {len(st)}")
+        for i, v in enumerate(sp):
+            if v < 0:
+                raise ValueError(f"spread[{i}] must be >= 0, got {v!r}")
+        return cls(tuple(a - b for a, b in zip(st, sp)), tuple(a + b for a, b in zip(st, sp)))
+
+    @classmethod
+    def parse(cls, text: str) -> "StartState":
+        """``"lo:hi"`` (every component) or ``"lo:hi,lo:hi,..."`` (one pair per component): the form of ``examples/train_ppo2.py --start-state``."""
+        if not isinstance(text, str):
+            raise TypeError(f"a start-state string is wanted, got {text!r}")
+        try:
+            pairs = [tuple(float(x) for x in item.split(":")) for item in text.split(",")]
+            if any(len(p) != 2 for p in pairs):
+                raise ValueError
+        except ValueError:
+            raise ValueError(f"--start-state wants LO:HI or LO:HI,LO:HI,... (one pair per state component); got {text!r}") from None
+        if len(pairs) == 1:
+            return cls(pairs[0][0], pairs[0][1])
+        return cls(tuple(p[0] for p in pairs), tuple(p[1] for p in pairs))
+
+    def check_kind(self, kind: int):
+        """The lengths against the kind, which the constructor does not know."""
+        if kind == A.REINMAV:
+            raise ValueError("ReinmavEnv takes no start-state ranges (its reset() is a no-op)")
+        nS = A.STATE_DIM[kind]
+        for name in ("lo", "hi"):
+            v = getattr(self, name)
+            if not isinstance(v, float) and len(v) != nS:
+                raise ValueError(f"{name} has {len(v)} components, the state of {A.KIND_NAMES[kind]} has {nS}")
+
+    def spec(self, kind: int) -> "A.StartStateSpec":
+        """``rmav_start_state_spec`` for a handle of ``kind`` (fp32; components past ``nS`` are 0)."""
+        self.check_kind(kind)
+        nS = A.STATE_DIM[kind]
+        lo, hi = self._pair(nS)
+        s = A.StartStateSpec((C.c_float * 16)(*(lo + (0.0,) * (16 - nS))), (C.c_float * 16)(*(hi + (0.0,) * (16 - nS))))
+        for i in range(nS):   # (two values that differ in fp64 may meet, never cross, in fp32; overflow to inf is refused here)
+            if not (np.isfinite(s.lo[i]) and np.isfinite(s.hi[i])):
+                raise ValueError(f"lo[{i}] / hi[{i}] are not finite in fp32")
+        return s
+
+    def coefficients(self, kind: int):
+        """``(h, m)`` as the library derives them from :meth:`spec`: fp64 from the spec's fp32 values, each rounded to fp32 once (two
+        ``float32`` arrays of ``nS``)."""
+        s = self.spec(kind)
+        nS = A.STATE_DIM[kind]
+        lo, hi = np.array(s.lo[:nS], np.float32).astype(np.float64), np.array(s.hi[:nS], np.float32).astype(np.float64)
+        return ((hi - lo) * 0.5).astype(np.float32), ((hi + lo) * 0.5).astype(np.float32)
+
+    @classmethod
+    def from_spec(cls, s: "A.StartStateSpec", kind: int) -> "StartState":
+        nS = A.STATE_DIM[kind]
+        return cls(tuple(s.lo[:nS]), tuple(s.hi[:nS]))
+
+    def __repr__(self):
+        return f"StartState(lo={self.lo!r}, hi={self.hi!r})"
+
+
+def check_start_state(start_state, kind=None):
+    """``start_state=`` as the constructors take it: None (the reference's U[-1, 1) on every component) or a :class:`StartState`; anything
+    else is refused here."""
+    if start_state is None:
+        return None
+    if not isinstance(start_state, StartState):
+        raise TypeError(f"start_state must be None or a StartState, got {start_state!r}")
+    if kind is not None:
+        start_state.check_kind(kind)
+    return start_state
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
@@ -428,7 +547,7 @@ class BatchedQuadrotor:
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
                  randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None,
                  disturbance: Optional[Disturbance] = None, sensor_noise: Optional[SensorNoise] = None,
-                 actuator: Optional[Actuator] = None):
+                 actuator: Optional[Actuator] = None, start_state: Optional[StartState] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
@@ -447,13 +566,18 @@ class BatchedQuadrotor:
         None = exact observations.
 
         ``actuator``: an :class:`Actuator` (first-order lag between the action and the dynamics; :attr:`actuator`), run inside the kernels;
-        None = the action reaches the dynamics unchanged."""
+        None = the action reaches the dynamics unchanged.
+
+        ``start_state``: a :class:`StartState` (the per-component range of every fresh state; :attr:`start_state`), applied inside the
+        kernels; None = the reference's U[-1, 1).  The constructor sets it and then calls :meth:`reset`, so the first episode of every
+        env is drawn under it (at reset index 1: index 0 is the draw of ``rmav_create``)."""
         frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         reward = check_reward(reward, self.kind)
         disturbance = check_disturbance(disturbance, self.kind)
         sensor_noise = check_sensor_noise(sensor_noise, self.kind)
         actuator = check_actuator(actuator, self.kind)
+        start_state = check_start_state(start_state, self.kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
         self.nS, self.nA = A.STATE_DIM[self.kind], A.ACTION_DIM[self.kind]
@@ -487,6 +611,9 @@ class BatchedQuadrotor:
             self.sensor_noise = sensor_noise
         if actuator is not None:
             self.actuator = actuator
+        if start_state is not None:   # (last: the reset behind it then runs with every other feature in force)
+            self.start_state = start_state
+            self.reset()
 
     # ---- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -632,6 +759,22 @@ class BatchedQuadrotor:
             A.check(self._lib.rmav_set_actuator(self._h, None))
         else:
             A.check(self._lib.rmav_set_actuator(self._h, C.byref(actuator.spec(self.kind, self.params))))
+
+    @property
+    def start_state(self) -> Optional[StartState]:
+        """The :class:`StartState` in force (``rmav_get_start_state``; values as the library holds them in fp32), or None: the reference's
+        U[-1, 1) on every component.  Assignable at any time: it draws nothing and does not touch the running episodes - every state drawn
+        from then on (``reset()``, every auto-reset) lies in the ranges."""
+        s, on = A.StartStateSpec(), C.c_int32()
+        A.check(self._lib.rmav_get_start_state(self._h, C.byref(s), C.byref(on)))
+        return StartState.from_spec(s, self.kind) if on.value else None
+
+    @start_state.setter
+    def start_state(self, start_state: Optional[StartState]):
+        if check_start_state(start_state, self.kind) is None:
+            A.check(self._lib.rmav_set_start_state(self._h, None))
+        else:
+            A.check(self._lib.rmav_set_start_state(self._h, C.byref(start_state.spec(self.kind))))
 
     def actuator_state(self, layout: str = "aos", device_out: bool = False):
         """The actuator state ``m`` of every env (``rmav_get_actuator_state``), ``nA`` values per env: with :attr:`actuator` the part of a

@@ -208,7 +208,8 @@ class RolloutCollector:
             # caller's envs - state, steps_beyond_done, reset counters, episode accumulators and totals, clocks -
             # are not advanced by it; the capture below records launches on the real env without executing them
             tmp = BatchedQuadrotor(env.kind, env.num_envs, device=env.device, seed=0, auto_reset=True,
-                                   track_episodes=env.track_episodes, params=env.params, actuator=getattr(env, "actuator", None))
+                                   track_episodes=env.track_episodes, params=env.params, actuator=getattr(env, "actuator", None),
+                                   start_state=getattr(env, "start_state", None))
             self.env = tmp
             try:
                 self._body()
@@ -548,6 +549,8 @@ class FusedPolicyCollector:
             refuse("an env with sensor_noise=", "sensor-noise")
         if not has_variants and getattr(env, "actuator", None) is not None:
             refuse("an env with actuator=", "actuator-lag")
+        if not has_variants and getattr(env, "start_state", None) is not None:
+            refuse("an env with start_state=", "start-state")
         self._rule = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
         if not has_variants and self._rule != (0, -math.inf, math.inf):
             refuse("deterministic= / clip_actions=", "action-rule")
