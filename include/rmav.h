@@ -180,7 +180,8 @@ int rmav_default_params(int kind, int reading_2d, rmav_params *out);
  * reset once (reset index 0), like the reference constructors (quadrotor3d.py:73-74).
  * params may be NULL (defaults).  hip_stream may be NULL (the handle creates its own non-blocking
  * stream) or a hipStream_t the caller owns (e.g. torch.cuda.current_stream().cuda_stream; pass
- * hipStreamLegacy == (void*)1 to name the legacy default stream, whose handle is 0). */
+ * hipStreamLegacy == (void*)1 to name the legacy default stream, whose handle is 0).
+ * n_envs <= 2^25: the size rule stated at rmav_rollout_pitched. */
 int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t seed,
                 uint64_t env_id_base, uint32_t flags, const rmav_params *params, void *hip_stream);
 int rmav_destroy(rmav_handle h);
@@ -295,7 +296,12 @@ int rmav_rollout(rmav_handle h, int32_t n_steps, int action_mode, const float *a
  * actions_in / actions_out [n_steps][nA][pitch], obs_out [n_steps][nS][pitch], rew_out / done_out [n_steps][pitch]; env i is
  * element i of every column, elements [N, pitch) are never written.  Same results as rmav_rollout.  Keeps the fast store path
  * for batch sizes that are not a multiple of 16.  rmav_trajectory_pitch() = N rounded up to a multiple
- * of 64; any pitch >= N is accepted. */
+ * of 64; any pitch in [N, 2^25] is accepted, a larger one is RMAV_ERR_INVALID (and so is a chunk_envs > N beyond it, which
+ * rmav_rollout_chunked turns into a pitch).
+ * The one size rule of the trajectory arrays, which also bounds n_envs (rmav_create: n_envs <= 2^25): ONE STEP of the widest
+ * array - nS <= 16 columns of 4 * pitch bytes - stays below 2^31 bytes, because the kernels add the offset of a column inside a
+ * step in 32 bits.  The number of steps is not bounded by it: an array may exceed 4 GiB (steps are reached with 64-bit pointers,
+ * or 32-bit step offsets only while the whole array stays below 4 GiB). */
 int64_t rmav_trajectory_pitch(rmav_handle h);
 int rmav_rollout_pitched(rmav_handle h, int32_t n_steps, int action_mode, const float *actions_in, float *actions_out,
                          float *obs_out, float *rew_out, uint8_t *done_out, int64_t pitch, int fused);

@@ -799,7 +799,7 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
     if (!out) return rmav_fail(RMAV_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (kind < 0 || kind >= kNumKinds) return rmav_fail(RMAV_ERR_INVALID, "bad kind %d", kind);
-    if (n_envs <= 0 || n_envs > ((int64_t)1 << 25))  // 32-bit buffer offsets, see rmav_kernels.hpp
+    if (n_envs <= 0 || n_envs > ((int64_t)1 << 25))  // 32-bit buffer offsets: one step of the widest array stays below 2^31 bytes (include/rmav.h, rmav_rollout_pitched)
         return rmav_fail(RMAV_ERR_INVALID, "n_envs out of range: %lld", (long long)n_envs);
     if (flags & ~(RMAV_F_AUTO_RESET | RMAV_F_TRACK_EPISODES))
         return rmav_fail(RMAV_ERR_INVALID, "unknown flag bits 0x%x", flags);
@@ -1095,8 +1095,10 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     CHECK_HANDLE(h);
     if (int rc = check_mem_layout(mem, layout)) return rc;
     if (n_steps <= 0) return rmav_fail(RMAV_ERR_INVALID, "n_steps must be > 0");
-    if (pitch != 0 && (pitch < h->n || pitch > (int64_t)0x3fffffff || mem != RMAV_DEVICE || layout != RMAV_SOA))
-        return rmav_fail(RMAV_ERR_INVALID, "a column pitch must be in [num_envs, 2^30) and needs device pointers and the feature-major layout");
+    // (the bound of num_envs, for the same reason: the kernels add the in-step column offset c * 4 * pitch, c < nS <= 16, in 32 bits -
+    // one step of the widest array stays below 2^31 bytes)
+    if (pitch != 0 && (pitch < h->n || pitch > ((int64_t)1 << 25) || mem != RMAV_DEVICE || layout != RMAV_SOA))
+        return rmav_fail(RMAV_ERR_INVALID, "a column pitch must be in [num_envs, 2^25 = 33554432] and needs device pointers and the feature-major layout");
     if (action_mode < RMAV_ACT_BUFFER || action_mode > RMAV_ACT_CONTROLLER)
         return rmav_fail(RMAV_ERR_INVALID, "unknown action_mode %d", action_mode);
     if (action_mode == RMAV_ACT_BUFFER && !actions_in)
