@@ -57,6 +57,9 @@ def main():
     ap.add_argument("--start-state", default=None, metavar="LO:HI[,LO:HI...]",
                     help="the range every episode's start state is drawn from, inside the kernels: one pair per state component, or a single "
                          "pair for all of them, e.g. -0.1:0.1; default: the reference's U[-1, 1) on every component; not with --actor bf16")
+    ap.add_argument("--termination", default=None, metavar="box=LO:HI,LO:HI[,LO:HI][:tilt=RAD]",
+                    help="termination rules inside the kernels, ORed into the env's own: a per-axis position box (inf = no bound), a tilt "
+                         "limit in radians, and always a finiteness test, e.g. box=-2:2,-2:2,0.3:inf:tilt=1.2; not with --actor bf16")
     ap.add_argument("--randomize", action="append", default=[], metavar="NAME=LO:HI",
                     help="per-episode domain randomisation inside the kernels, e.g. mass=0.8:1.2 (mass | load_mass | tether_length; "
                          "repeatable); not with --actor bf16")
@@ -108,9 +111,13 @@ def main():
         start_state = g.StartState.parse(args.start_state) if args.start_state is not None else None
     except (TypeError, ValueError) as e:
         ap.error(str(e))
+    try:
+        termination = g.Termination.parse(args.termination) if args.termination is not None else None
+    except (TypeError, ValueError) as e:
+        ap.error(str(e))
     env = g.BatchedQuadrotor(kind, args.num_env, seed=args.seed, max_episode_steps=args.max_episode_steps or None,
                              randomize=randomize or None, frame_skip=args.frame_skip, reward=reward, disturbance=disturbance,
-                             sensor_noise=sensor_noise, actuator=actuator, start_state=start_state)
+                             sensor_noise=sensor_noise, actuator=actuator, start_state=start_state, termination=termination)
     obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
     ret_norm = RunningReturnNorm(f"cuda:{env.device}") if args.normalize_reward else None   # ... and its ret=True half
     policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()
@@ -131,7 +138,7 @@ def main():
         eval_env = g.BatchedQuadrotor(kind, args.eval_envs, seed=args.seed, env_id_base=args.num_env,
                                       max_episode_steps=args.max_episode_steps or None, randomize=randomize or None,
                                       frame_skip=args.frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise,
-                                      actuator=actuator, start_state=start_state)
+                                      actuator=actuator, start_state=start_state, termination=termination)
     learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()

@@ -619,6 +619,55 @@ typedef struct rmav_start_state_spec {
 int rmav_set_start_state(rmav_handle h, const rmav_start_state_spec *spec);   /* NULL: the reference's U[-1,1) (the default) */
 int rmav_get_start_state(rmav_handle h, rmav_start_state_spec *out, int32_t *enabled);   /* either pointer may be NULL */
 
+/* ---- termination rules: a per-axis position box, a tilt limit and a finiteness test ----------------------------------------------------
+ * The reference's native envs end an episode on |pos| > pos_limit || |vel| > vel_limit: a sphere round the origin.  Its MuJoCo hovering task
+ * (gym_reinmav/envs/mujoco/mujoco_quad_hovering.py:55-60) ends on a per-axis box and a finiteness test instead - isfinite(ob).all() and
+ * ob[2] > 0.3 and |ob[0]| < 2 and |ob[1]| < 2 - and its two MuJoCo base envs on not isfinite(ob).all().  With a spec set the termination flag of
+ * EVERY ordinary dynamics step of a quadrotor handle - every sub-step of a frame skip - is
+ *     term = term_ref || rule(s)
+ * term_ref what the step computes without a spec, s the stored post-step fp32 state.  The rule is fp32, nothing contracted but the fmas written:
+ *     nonfinite = any c < nS: !(|s_c| < inf)
+ *     outside   = any body B, any axis i < dim: !(B_i >= pos_lo_i) || !(B_i <= pos_hi_i)
+ *                 bodies: the quadrotor s[0:dim]; for the slung-load kinds also the load (s[5:7] / s[10:13]).  Walls and floor apply to both.
+ *     tilted    = 2-D kinds:  |s[2]| > max_tilt                        (the angle is never wrapped)
+ *                 3-D kinds:  fma(w,w, fma(z,z, -fma(x,x, y*y))) < c * fma(w,w, fma(x,x, fma(y,y, z*z)))
+ *                             (w,x,y,z) = s[3:7];  c = (float)cos((double)max_tilt), computed on the host and rounded once;
+ *                             max_tilt = +inf passes c = -inf, which never fires
+ *     rule      = nonfinite || outside || tilted
+ * The 3-D tilt test is the world-z component of the body's z axis against cos(max_tilt), both sides multiplied by |q|^2: no division, no
+ * reciprocal square root.
+ *   - nothing downstream changes: the reward machine (the reference literal or the tracking reward's `terminal`), steps_beyond_done, the
+ *     frame-skip break, "termination wins over truncation" and trunc = 0, the actuator re-initialisation, the redraw of ranged constants and
+ *     wind, the auto-reset and the start-state map, the episode statistics and rmav_step_final's final_obs_out (the pre-reset state) see ONE
+ *     term, as before.
+ *   - nothing else depends on the spec: dist, the dynamics, every RNG stream and control() are unaffected.  The feature adds no stream and no
+ *     per-env state: a checkpoint is the spec alone.
+ *   - the rule is evaluated on states a step produces: rmav_reset, rmav_set_state and a fresh state are not tested.  A set takes effect with
+ *     the next step.
+ *   - identity: a spec with all bounds infinite and max_tilt = +inf differs from no spec only in `nonfinite`; on finite trajectories such a
+ *     handle stores, in every route, the bits of a handle without one.
+ * Launches of such a handle run kernels of their own, cut from those of a start-state spec, whose launch rules they
+ * share: the one-wavefront fused rollouts with ONE store policy (fused = 0 gives the bits of fused = 1; a chunk-major call is one launch per
+ * chunk).  A handle without a start-state spec passes the identity coefficients (h = 1, m = 0: the plain bits), one without actuator lag the
+ * flag that gates the filter, one without sensor noise skips the draw, one without a disturbance passes the all-zero one.  rmav_reset runs
+ * what it ran before.  rmav_rollout_policy / _boot / _norm run the three actors the start-state spec runs (RMAV_POLICY_FP32_MFMA,
+ * RMAV_POLICY_F16_MFMA, RMAV_POLICY_F16_SHARED); the other precisions return RMAV_ERR_INVALID with a message that names the feature.
+ * Validation: no NaN anywhere, pos_lo_i <= pos_hi_i, max_tilt in [0, pi] (pi as fp32 rounds it) or +inf, _reserved 0; RMAV_REINMAV takes no
+ * spec; anything else is RMAV_ERR_INVALID and the spec in force stays.  NULL switches the feature off: such a handle, like one that never
+ * set a spec, launches exactly the kernels it launched before.
+ * Ordering and capture as rmav_set_start_state: the step kernels and the one-wavefront rollouts take the thresholds by value; the policy
+ * kernels read a device copy in the handle's arena, which rmav_set_termination rewrites in stream order with one small launch
+ * (k_set_termination).  It neither allocates nor synchronises.
+ * rmav_get_termination: the last spec set (zeros before the first), and whether it is in force; either pointer may be NULL.
+ * Callers detect the feature by the symbols; RMAV_VERSION is unchanged. */
+typedef struct rmav_termination_spec {
+    float pos_lo[3], pos_hi[3];  /* per-axis box, metres; -inf / +inf = no bound on that side; 2-D kinds read [0..1] */
+    float max_tilt;              /* radians in [0, pi], or +inf = none */
+    int32_t _reserved;           /* must be 0 */
+} rmav_termination_spec;         /* 32 bytes */
+int rmav_set_termination(rmav_handle h, const rmav_termination_spec *spec);   /* NULL: the reference's rule alone (the default) */
+int rmav_get_termination(rmav_handle h, rmav_termination_spec *out, int32_t *enabled);   /* either pointer may be NULL */
+
 /* ---- what the auto-reset destroys: terminal observations and truncated flags ----------------------------------------------------
  * With RMAV_F_AUTO_RESET every observation a caller sees for a finished env is the fresh post-reset state.  A learner that
  * bootstraps a truncated episode (target r + gamma V(s_final): a truncated episode is not a failure) needs the state the dynamics

@@ -241,6 +241,12 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
+    } else if (h->term_on) {   // a handle with a termination spec: k_rollout_tc, which takes the start-state spec (the identity without one) and all it takes as well
+        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
+            if (int rc = rmav_launch_term_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
+        } else {
+            return rmav_fail(RMAV_ERR_INVALID, "no termination kernel for action mode %d", MODE);
+        }
     } else if (h->start_on) {   // a handle with a start-state spec: k_rollout_ss, which takes the actuator lag (switched off without a spec) and all it takes as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
             if (int rc = rmav_launch_start_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
@@ -360,7 +366,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
     // One with a disturbance (rmav_set_disturbance): k_rollout_ds.  One with sensor noise (rmav_set_sensor_noise): k_rollout_sn.
     // One with actuator lag (rmav_set_actuator): k_rollout_al.  One with a start-state spec (rmav_set_start_state): k_rollout_ss.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on)) {
+    // One with a termination spec (rmav_set_termination): k_rollout_tc.
+    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on || h->term_on)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -437,7 +444,11 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->start_on) {   // a handle with a start-state spec: k_step_ss for every batch size; the control() form is k_control behind it
+    if (h->term_on) {   // a handle with a termination spec: k_step_tc for every batch size; the control() form is k_control behind it
+        if (int rc = rmav_launch_term_step(h, a, bs, FinalArgs{})) return rc;
+        if (ctrl)
+            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
+    } else if (h->start_on) {   // a handle with a start-state spec: k_step_ss for every batch size; the control() form is k_control behind it
         if (int rc = rmav_launch_start_step(h, a, bs, FinalArgs{})) return rc;
         if (ctrl)
             if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
@@ -490,7 +501,9 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->start_on) {
+    if (h->term_on) {
+        if (int rc = rmav_launch_term_step(h, a, bs, fa)) return rc;
+    } else if (h->start_on) {
         if (int rc = rmav_launch_start_step(h, a, bs, fa)) return rc;
     } else if (h->actuator_on) {
         if (int rc = rmav_launch_actuator_step(h, a, bs, fa)) return rc;
@@ -860,6 +873,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         const size_t o_al = off; off += (kind != RMAV_REINMAV) ? up(sizeof(ActuatorDev)) : 0;
         // (... and of a start-state spec's)
         const size_t o_ss = off; off += (kind != RMAV_REINMAV) ? up(sizeof(StartDev)) : 0;
+        // (... and of a termination spec's)
+        const size_t o_tc = off; off += (kind != RMAV_REINMAV) ? up(sizeof(TermDev)) : 0;
         if (hipMalloc(&h->arena, off) != hipSuccess) {
             (void)hipGetLastError();
             h->arena = nullptr;
@@ -872,7 +887,8 @@ int rmav_create(rmav_handle *out, int kind, int64_t n_envs, int device, uint64_t
         h->totals = (Totals *)(b + o_tot);
         if (kind == RMAV_REINMAV) h->env_time = (double *)(b + o_time);
         else h->reward_dev = (RewardArgs *)(b + o_rw), h->disturb_dev = (DisturbSpec *)(b + o_ds), h->sensor_dev = (SensorDev *)(b + o_sn),
-                 h->actuator_dev = (ActuatorDev *)(b + o_al), h->start_dev = (StartDev *)(b + o_ss);
+                 h->actuator_dev = (ActuatorDev *)(b + o_al), h->start_dev = (StartDev *)(b + o_ss),
+                 h->term_dev = (TermDev *)(b + o_tc);
         if (tr) {
             h->ep_ret = (float *)(b + o_er);
             h->last_ret = (float *)(b + o_lr);
@@ -1171,7 +1187,7 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
     // (not rmav_step_control of a handle with a tracking reward, a disturbance, sensor noise or actuator lag: k_control runs behind k_step_rw / k_step_ds / k_step_sn / k_step_al, which would publish too early)
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on))) {
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on || h->term_on))) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {
@@ -1721,6 +1737,43 @@ int rmav_get_start_state(rmav_handle h, rmav_start_state_spec *out, int32_t *ena
     if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
     if (out) *out = h->start;   // (the last spec set - zeros before the first - also while it is switched off)
     if (enabled) *enabled = h->start_on;
+    return RMAV_OK;
+}
+
+// Termination rules: the spec on the handle.  Every stepping launch reads term_on (launch_rollout_kms, launch_step_k, launch_step_final_k;
+// rmav_ppo_abi.hip) and derives the thresholds from the spec when it is enqueued; the policy kernels read the device copy in the arena,
+// which every set rewrites in stream order with one small launch.  Nothing is allocated or synchronised; rmav_reset does not look here.
+int rmav_set_termination(rmav_handle h, const rmav_termination_spec *spec) {
+    CHECK_HANDLE(h);
+    if (!spec) {   // none: the launches of a handle that never had a spec
+        h->term_on = 0;
+        return RMAV_OK;
+    }
+    if (h->kind == RMAV_REINMAV) return rmav_fail(RMAV_ERR_INVALID, "ReinmavEnv takes no termination spec (its step() ends every episode)");
+    for (int i = 0; i < 3; ++i) {
+        const float lo = spec->pos_lo[i], hi = spec->pos_hi[i];
+        if (lo != lo || hi != hi) return rmav_fail(RMAV_ERR_INVALID, "termination pos_lo[%d] / pos_hi[%d] is NaN", i, i);
+        if (!(lo <= hi)) return rmav_fail(RMAV_ERR_INVALID, "termination pos_lo[%d] = %g is above pos_hi[%d] = %g", i, (double)lo, i, (double)hi);
+    }
+    const float mt = spec->max_tilt;
+    if (!((mt >= 0.0f && mt <= 3.14159274101257324f) || mt == __builtin_inff()))   // (pi as fp32 rounds it)
+        return rmav_fail(RMAV_ERR_INVALID, "termination max_tilt = %g must lie in [0, pi] or be +inf (none)", (double)mt);
+    if (spec->_reserved != 0) return rmav_fail(RMAV_ERR_INVALID, "termination _reserved must be 0");
+    const rmav_termination_spec old = h->term;
+    h->term = *spec;
+    if (int rc = rmav_sync_term_dev(h)) {   // the policy kernels' copy, in stream order
+        h->term = old;
+        if (h->term_on) (void)rmav_sync_term_dev(h);
+        return rc;
+    }
+    h->term_on = 1;
+    return RMAV_OK;
+}
+
+int rmav_get_termination(rmav_handle h, rmav_termination_spec *out, int32_t *enabled) {
+    if (!valid(h)) return rmav_fail(RMAV_ERR_INVALID, "invalid rmav_handle");
+    if (out) *out = h->term;   // (the last spec set - zeros before the first - also while it is switched off)
+    if (enabled) *enabled = h->term_on;
     return RMAV_OK;
 }
 

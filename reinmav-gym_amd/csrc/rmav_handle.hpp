@@ -1,8 +1,8 @@
 // rmav_handle.hpp - the one internal header of the translation units behind the C ABI: the handle / communicator structs, the error
 // helper, the handle check, the launch helpers, and the functions that cross a unit boundary.  librmav.so is built from one unit per
-// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus eleven that only launch kernels (rmav_policy_abi.hip,
+// public header (rmav_abi.hip, rmav_ppo_abi.hip, rmav_comm_abi.hip) plus thirteen that only launch kernels (rmav_policy_abi.hip,
 // rmav_range_abi.hip, rmav_skip_abi.hip, rmav_reward_abi.hip, rmav_disturb_abi.hip, rmav_sensor_abi.hip, rmav_sensor_policy_abi.hip,
-// rmav_actuator_abi.hip, rmav_actuator_policy_abi.hip, rmav_start_abi.hip, rmav_start_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
+// rmav_actuator_abi.hip, rmav_actuator_policy_abi.hip, rmav_start_abi.hip, rmav_start_policy_abi.hip, rmav_term_abi.hip, rmav_term_policy_abi.hip), so that they compile side by side; all of them take the same compiler flags but for ABIFLAGS (Makefile).
 #pragma once
 
 #include "../../include/rmav.h"
@@ -139,7 +139,28 @@ struct rmav_env_s {
     int32_t start_on;
     rmav_start_state_spec start;
     rmav::StartDev *start_dev;   // in the arena next to actuator_dev (k_set_start_state rewrites it)
+    // termination rules (rmav_set_termination): the spec and whether one is set.  term_on routes every stepping launch to the *_tc kernels -
+    // before the start-state spec, which those kernels take as well (the identity coefficients without one).  The step kernels and the
+    // one-wavefront rollouts take the thresholds by value, derived from the spec at the launch; the policy kernels read term_dev, which
+    // every set rewrites in stream order.  rmav_reset is untouched: the rule is evaluated on states a step produces.
+    int32_t term_on;
+    rmav_termination_spec term;
+    rmav::TermDev *term_dev;   // in the arena next to start_dev (k_set_termination rewrites it)
 };
+static_assert(sizeof(rmav_termination_spec) == 32, "seven floats and the reserved word");
+// the seven thresholds as the *_tc kernels take them (the 3-D kinds: the cosine of max_tilt, fp64, rounded once)
+inline rmav::TermArgs term_args(const rmav_env_s *h) {
+    rmav::TermArgs t{};
+    for (int i = 0; i < 3; ++i) t.v[i] = h->term.pos_lo[i], t.v[3 + i] = h->term.pos_hi[i];
+    t.v[6] = rmav::term_tilt(h->kind, h->term.max_tilt);
+    return t;
+}
+// the identity start coefficients (h = 1, m = 0 below 16: fma(1, v, 0) = v, the bits of a handle without a start-state spec)
+inline rmav::StartCoef start_identity() {
+    rmav::StartCoef c{};
+    for (int i = 0; i < 16; ++i) c.h[i] = 1.0f, c.m[i] = 0.0f;
+    return c;
+}
 static_assert(sizeof(rmav_start_state_spec) == 128, "thirty-two floats");
 // h and m of every component (from the spec's lo and hi, in fp64, each rounded once), as the *_ss kernels take them
 inline rmav::StartCoef start_coef(const rmav_env_s *h) {
@@ -247,6 +268,22 @@ inline rmav::PolicyStartArgs policy_start_args(const rmav_env_s *h, uint64_t t0)
         pa.m = nullptr;
     }
     return rmav::PolicyStartArgs{pa, &h->start_dev->c, h->actuator_on ? 1u : 0u, 0u};
+}
+// what the *_tc kernels take in StartArgs' place: the handle's, or - without a start-state spec - the identity coefficients
+inline rmav::StartArgs term_start_args(const rmav_env_s *h) {
+    if (h->start_on) return start_args(h);
+    return rmav::StartArgs{start_identity(), h->actuator_on ? 1u : 0u, 0u};
+}
+// what the policy kernels of a handle with a termination spec take: PolicyStartArgs - without a start-state spec the identity coefficients
+// and, for a handle with neither a disturbance nor an actuator spec, the calm disturbance spec sit in term_dev (k_set_termination wrote
+// them) - then the device copy of the thresholds
+inline rmav::PolicyTermArgs policy_term_args(const rmav_env_s *h, uint64_t t0) {
+    rmav::PolicyStartArgs ps = policy_start_args(h, t0);
+    if (!h->start_on) {
+        ps.ss = &h->term_dev->ident;
+        if (!h->actuator_on && !h->disturb_on) ps.pa.ds = &h->term_dev->calm;
+    }
+    return rmav::PolicyTermArgs{ps, &h->term_dev->t};
 }
 inline rmav::TimeLimitArgs tl_args(const rmav_env_s *h) { return rmav::TimeLimitArgs{h->last_trunc, h->time_limit}; }
 // what the *_dr kernels take: the arrays of the ranged parameters (allocated while their bit is set) and the ranges as (lo, hi - lo)
@@ -494,3 +531,14 @@ RMAV_INTERNAL int rmav_sync_start_dev(rmav_handle h);
 // rmav_start_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_ss, k_rollout_pair_ss, k_rollout_pair_shared_ss -
 // with rmav_launch_sensor_policy_rollout's arguments.
 RMAV_INTERNAL int rmav_launch_start_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
+
+// rmav_term_abi.hip: the launches of a handle with a termination spec (rmav_set_termination), shaped as those of a start-state spec, whose
+// arguments they take as well (a handle without one: the identity coefficients).  _rollout: ONE launch of k_rollout_tc<K, mode, time limit?,
+// reward?> (one store policy); _step: k_step_tc at bs threads per workgroup; _sync: k_set_termination, the handle's device copy (term_dev)
+// rewritten in stream order - no allocation, no synchronisation.  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_term_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_term_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_sync_term_dev(rmav_handle h);
+// rmav_term_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_tc, k_rollout_pair_tc, k_rollout_pair_shared_tc -
+// with rmav_launch_sensor_policy_rollout's arguments.
+RMAV_INTERNAL int rmav_launch_term_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);

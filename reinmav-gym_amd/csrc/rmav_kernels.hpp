@@ -32,6 +32,7 @@
 #include "rmav_sensor.hpp"
 #include "rmav_actuator.hpp"
 #include "rmav_start.hpp"
+#include "rmav_term.hpp"
 #include "rmav_policy.hpp"
 #include "rmav_policy_mfma.hpp"
 #include "rmav_policy_mfma32.hpp"
@@ -48,6 +49,9 @@
 // filter, the loads and the stores of its state sit behind ONE wave-uniform flag (ss_al: a handle with a start spec and no actuator lag
 // hands the command itself to the dynamics).  In every other kernel that flag is the constant true.
 #define RMAV_ROLLOUT_SS 0
+// RMAV_ROLLOUT_TC: likewise the termination rules of the *_tc wrappers (rmav_set_termination; rmav_term.hpp), which are cut from the *_ss
+// bodies: the termination flag of every dynamics sub-step is term || term_rule<K>(s, tc), directly behind Env<K>::step (tc: TermArgs).
+#define RMAV_ROLLOUT_TC 0
 
 namespace rmav {
 
@@ -424,6 +428,19 @@ struct PolicyStartArgs {
     const StartCoef *ss;
     uint32_t al_on;
     uint32_t _pad;
+};
+// ... and the POLICY kernels of a handle with a termination spec (the *_tc policy families): PolicyStartArgs with the handle's device copy of
+// the thresholds behind it.  TermDev is that copy (rmav_env_s::term_dev, rewritten in stream order by k_set_termination): the thresholds,
+// the identity start coefficients ss then points at for a handle without a start-state spec (h = 1, m = 0: the plain bits), and the calm
+// disturbance spec for a handle with neither a disturbance nor an actuator spec.
+struct TermDev {
+    TermArgs t;
+    StartCoef ident;
+    DisturbSpec calm;
+};
+struct PolicyTermArgs {
+    PolicyStartArgs ps;
+    const TermArgs *tc;
 };
 // the observation row of the *_al kernels: the noisy one, or - a handle without sensor noise, wave-uniform - the state itself
 template <int NS>
@@ -1005,6 +1022,90 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
 #define RMAV_ROLLOUT_SN 0
 }
 
+// The one-wavefront kernels of a handle with a termination spec (rmav_set_termination; TermArgs in rmav_term.hpp): k_rollout_ss's body and
+// argument list with the thresholds behind it.  Every dynamics sub-step ends the episode where the reference's rule or term_rule fires;
+// everything downstream sees one flag.  A handle without a start-state spec passes the identity coefficients (h = 1, m = 0), one without
+// actuator lag ss.al_on = 0, one without sensor noise al.sn_on = 0, one without a disturbance the all-zero spec.
+template <int K, int MODE, bool TL, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tc(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                       const ParamsT<double> pc_shared, const TimeLimitArgs tl, const RangeArgs dr,
+                                                       const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn,
+                                                       const ActuatorArgs al, const StartArgs ss, const TermArgs tc) {
+    constexpr int ST = ST_DEFAULT;
+    constexpr bool FIXED = false, BOOT = false, NORM = false, DR = true, FS = true, DS = true;
+    [[maybe_unused]] const ActRuleArgs ar{};
+    [[maybe_unused]] const BootArgs bt{};
+    [[maybe_unused]] const NormArgs nm{};
+    const ActuatorCoef &alc = al.c;
+    const float *const al_init = al.c.init;
+    float *const al_m = al.m;
+    const uint32_t al_sn = al.sn_on;
+    const StartCoef &ssc = ss.c;
+    const uint32_t ss_al = ss.al_on;
+    static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "launches with a termination spec run the one-wavefront kernels");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 1
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 1
+#undef RMAV_ROLLOUT_TC
+#define RMAV_ROLLOUT_TC 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_TC
+#define RMAV_ROLLOUT_TC 0
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 0
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 0
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
+// ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_ss with the rule behind every dynamics sub-step.  The thresholds are read
+// through the handle's device copy.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k_rollout_nrm_tc(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                               const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                               const BootArgs bt, const RangeArgs *drp, const PolicyTermArgs pts) {
+    const PolicyStartArgs &pss = pts.ps;
+    const PolicyActuatorArgs &ps = pss.pa;
+    const TermArgs &tc = *pts.tc;
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    const ActuatorCoef &alc = *ps.al;
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    const StartCoef &ssc = *pss.ss;
+    const uint32_t ss_al = pss.al_on;
+    const RangeArgs &dr = *drp;
+    const NormArgs nm{a.act_in};
+    constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
+    constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 1
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 1
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 1
+#undef RMAV_ROLLOUT_TC
+#define RMAV_ROLLOUT_TC 1
+#include "rmav_rollout_body.inc"
+#undef RMAV_ROLLOUT_TC
+#define RMAV_ROLLOUT_TC 0
+#undef RMAV_ROLLOUT_SS
+#define RMAV_ROLLOUT_SS 0
+#undef RMAV_ROLLOUT_AL
+#define RMAV_ROLLOUT_AL 0
+#undef RMAV_ROLLOUT_SN
+#define RMAV_ROLLOUT_SN 0
+}
+
 // reset_state<K> for the lanes of a wavefront that need it, computed cooperatively (all 64 lanes must be active).
 // Philox4x32-10 is ~20 quarter-rate 32x32->64 multiplies per call and reset_state needs ceil(nS / 4) calls (the counter
 // word c3 selects the block of four components); executed by a whole wavefront for the one or two lanes whose env has
@@ -1083,13 +1184,16 @@ struct StepHot {   // (documentation of the argument order; passed as separate s
 // sub-step - which reads m, not the action -, set to init where the env is reset and stored in place; al.sn_on = 0 skips the noise draw.
 // SS: the handle has a start-state spec (ss; k_step_ss): a finishing lane maps what it picked up from reset_state_wave (start_apply);
 // ss.al_on = 0 skips the filter and the loads and stores of its state (al.m may be NULL).
+// TC: the handle has a termination spec (tc; k_step_tc): the flag of every dynamics sub-step is term || term_rule<K>(s, tc).
 template <int K, bool CTRL, bool LAZY, int ST, bool TL = false, bool FIN = false, bool DR = false, bool FS = false, bool RW = false, bool DS = false,
-          bool SN = false, bool AL = false, bool SS = false>
+          bool SN = false, bool AL = false, bool SS = false, bool TC = false>
 __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t block_pl, const typename Env<K>::P &p_shared, const ParamsT<double> &pc_shared,
                                           const TimeLimitArgs &tl = TimeLimitArgs{}, const FinalArgs &fa = FinalArgs{}, const RangeArgs &dr = RangeArgs{},
                                           [[maybe_unused]] const FrameSkipArgs &fs = FrameSkipArgs{}, [[maybe_unused]] const RewardArgs &rw = RewardArgs{},
                                           [[maybe_unused]] const DisturbArgs &ds = DisturbArgs{}, [[maybe_unused]] const SensorArgs &sn = SensorArgs{},
-                                          [[maybe_unused]] const ActuatorArgs &al = ActuatorArgs{}, [[maybe_unused]] const StartArgs &ss = StartArgs{}) {
+                                          [[maybe_unused]] const ActuatorArgs &al = ActuatorArgs{}, [[maybe_unused]] const StartArgs &ss = StartArgs{},
+                                          [[maybe_unused]] const TermArgs &tc = TermArgs{}) {
+    static_assert(!TC || SS, "the step of a handle with a termination spec is cut from the start-state body");
     static_assert(!RW || FS, "the tracking reward is evaluated in the sub-step loop");
     static_assert(!SS || AL, "the step of a handle with a start spec is cut from the lagged body");
     // (wave-uniform; the constant true in every kernel but k_step_ss)
@@ -1224,6 +1328,7 @@ __device__ __forceinline__ void step_body(const RolloutArgs &a, const uint32_t b
                 } else {
                     Env<K>::step(s, act, pl, dist, term);
                 }
+                if constexpr (TC) term = term || term_rule<K>(s, tc);   // the termination rules (rmav_term.hpp)
                 float rj = -dist;
                 if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
                     rj = reward_rw<K>(s, c_rw, rw, term);
@@ -1637,6 +1742,25 @@ __global__ __launch_bounds__(kBlock) void k_step_ss(float *state_pl, int64_t n_p
     a.ep_ret = ep_ret_pl;
     a.rec = rec_pl;
     step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn, al, ss);
+}
+
+// The single-step kernel of a handle with a termination spec (rmav_set_termination): k_step_ss's body and argument list with the rule behind
+// every dynamics sub-step.
+template <int K, bool TL, bool RW>
+__global__ __launch_bounds__(kBlock) void k_step_tc(float *state_pl, int64_t n_pl, const float *act_pl, int64_t pitch_pl, uint32_t block_pl, uint32_t flags_pl,
+                                                    float *ep_ret_pl, EnvRec *rec_pl, const RolloutArgs a_in, const typename Env<K>::P p_shared,
+                                                    const ParamsT<double> pc_shared, const TimeLimitArgs tl, const FinalArgs fa, const RangeArgs dr,
+                                                    const FrameSkipArgs fs, const RewardArgs rw, const DisturbArgs ds, const SensorArgs sn,
+                                                    const ActuatorArgs al, const StartArgs ss, const TermArgs tc) {
+    RolloutArgs a = a_in;
+    a.state = state_pl;
+    a.n = n_pl;
+    a.act_in = act_pl;
+    a.pitch = pitch_pl;
+    a.flags = flags_pl;
+    a.ep_ret = ep_ret_pl;
+    a.rec = rec_pl;
+    step_body<K, false, false, ST_DEFAULT, TL, true, true, true, RW, true, true, true, true, true>(a, block_pl, p_shared, pc_shared, tl, fa, dr, fs, rw, ds, sn, al, ss, tc);
 }
 
 // rmav_observe: the observation of every env's current state at the step counter b, out nS * n floats, feature-major or - aos - batch-major.

@@ -46,6 +46,9 @@
 #else
                         Env<K>::step(s, ca, p, dist, term);
 #endif
+#if RMAV_PAIR_TC   // the termination rules (tc: TermArgs; rmav_term.hpp): one flag for everything downstream
+                        term = term || term_rule<K>(s, tc);
+#endif
                         float rj = -dist;
                         if constexpr (RW) {   // the tracking reward (RewardArgs) in the literal's place; steps_beyond_done advances as ever
                             rj = reward_rw<K>(s, c_rw, rw, term);

@@ -48,6 +48,9 @@
 // bodies: the spare state of rmav_pair_env_load.inc and the on-demand draw of rmav_pair_episode.inc go through start_apply, and the filter
 // with the loads and stores of its state sits behind one wave-uniform flag (ss_al: a handle with a start spec and no actuator lag).
 #define RMAV_PAIR_SS 0
+// RMAV_PAIR_TC: likewise the termination rules of the *_tc wrappers (rmav_set_termination; rmav_term.hpp), which are cut from the *_ss bodies:
+// the termination flag of every dynamics sub-step of rmav_pair_dynamics.inc is term || term_rule<K>(s, tc).
+#define RMAV_PAIR_TC 0
 
 namespace rmav {
 
@@ -487,6 +490,57 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_ss(cons
 #undef RMAV_PAIR_DR
 #define RMAV_PAIR_DR 0
 }
+// ... and of a handle with a termination spec (rmav_set_termination; rmav_term.hpp): k_rollout_pair_ss with the rule behind every dynamics
+// sub-step; the thresholds are read through the handle's device copy.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tc(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyTermArgs pts) {
+    const PolicyStartArgs &pss = pts.ps;
+    const PolicyActuatorArgs &ps = pss.pa;
+    const TermArgs &tc = *pts.tc;
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    ActuatorCoef alc;   // (as k_rollout_pair_al; unread without actuator lag)
+#pragma unroll
+    for (int c = 0; c < Dims<K>::NA; ++c) alc.alpha[c] = ps.al->alpha[c], alc.beta[c] = ps.al->beta[c];
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    const StartCoef &ssc = *pss.ss;
+    const uint32_t ss_al = pss.al_on;
+    constexpr int FMT = FMT_F16;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 1
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 1
+#undef RMAV_PAIR_SS
+#define RMAV_PAIR_SS 1
+#undef RMAV_PAIR_TC
+#define RMAV_PAIR_TC 1
+#include "rmav_pair_body.inc"
+#undef RMAV_PAIR_TC
+#define RMAV_PAIR_TC 0
+#undef RMAV_PAIR_SS
+#define RMAV_PAIR_SS 0
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 0
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 0
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
 
 // ---- one shared 2 x 64 trunk with a mean head and a value head (RMAV_POLICY_F16_SHARED) -------------------------------------------
 //
@@ -807,6 +861,56 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
 #undef RMAV_PAIR_SS
 #define RMAV_PAIR_SS 1
 #include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_SS
+#define RMAV_PAIR_SS 0
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 0
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 0
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 0
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 0
+}
+// ... and of a handle with a termination spec (rmav_set_termination; rmav_term.hpp): k_rollout_pair_shared_ss with the rule behind every dynamics
+// sub-step; the thresholds are read through the handle's device copy.
+template <int K, bool BOOT, bool RW>
+__global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_tc(const RolloutArgs a, const typename Env<K>::P p_shared,
+                                                                             const ParamsT<double> pc_shared, const TimeLimitArgs tl,
+                                                                             const BootArgs bt, const NormArgs nm, const RangeArgs dr, const PolicyTermArgs pts) {
+    const PolicyStartArgs &pss = pts.ps;
+    const PolicyActuatorArgs &ps = pss.pa;
+    const TermArgs &tc = *pts.tc;
+    const ActRuleArgs ar{ps.noise, ps.lo, ps.hi};
+    const FrameSkipArgs fs{ps.k};
+    [[maybe_unused]] const RewardArgs &rw = *ps.rw;
+    const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
+    const SensorArgs &sn = *ps.sn;
+    ActuatorCoef alc;   // (as k_rollout_pair_shared_al; unread without actuator lag)
+#pragma unroll
+    for (int c = 0; c < Dims<K>::NA; ++c) alc.alpha[c] = ps.al->alpha[c], alc.beta[c] = ps.al->beta[c];
+    const float *const al_init = ps.al->init;
+    float *const al_m = ps.m;
+    const uint32_t al_sn = ps.sn_on;
+    const StartCoef &ssc = *pss.ss;
+    const uint32_t ss_al = pss.al_on;
+    constexpr bool TL = BOOT, NORM = true, FS = true;
+    static_assert(K != REINMAV, "the four quadrotor kinds");
+#undef RMAV_PAIR_DR
+#define RMAV_PAIR_DR 1
+#undef RMAV_PAIR_DS
+#define RMAV_PAIR_DS 1
+#undef RMAV_PAIR_SN
+#define RMAV_PAIR_SN 1
+#undef RMAV_PAIR_AL
+#define RMAV_PAIR_AL 1
+#undef RMAV_PAIR_SS
+#define RMAV_PAIR_SS 1
+#undef RMAV_PAIR_TC
+#define RMAV_PAIR_TC 1
+#include "rmav_pair_shared_body.inc"
+#undef RMAV_PAIR_TC
+#define RMAV_PAIR_TC 0
 #undef RMAV_PAIR_SS
 #define RMAV_PAIR_SS 0
 #undef RMAV_PAIR_AL

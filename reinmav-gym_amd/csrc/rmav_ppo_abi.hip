@@ -109,9 +109,12 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
     // ... and one with sensor noise: k_rollout_nrm_sn is the disturbed kernel whose nets read the noisy observation
     // ... and one with actuator lag: the *_al kernels are the noisy ones with the filter between the clipped action and the dynamics
     // ... and one with a start-state spec: the *_ss kernels are the lagged ones whose fresh states go through the map
-    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on;
+    // ... and one with a termination spec: the *_tc kernels are those of a start-state spec with the rule behind every dynamics sub-step
+    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on || h->term_on;
     if (skipped) {
-        if (h->start_on) {
+        if (h->term_on) {
+            if (int rc = need_variants(precision, "a handle with a termination spec (rmav_set_termination)", "termination")) return rc;
+        } else if (h->start_on) {
             if (int rc = need_variants(precision, "a handle with a start-state spec (rmav_set_start_state)", "start-state")) return rc;
         } else if (h->actuator_on) {
             if (int rc = need_variants(precision, "a handle with actuator lag (rmav_set_actuator)", "actuator-lag")) return rc;
@@ -138,7 +141,9 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
             bt = &bt_r;
         }
     }
-    if (h->start_on) {
+    if (h->term_on) {
+        if (int rc = rmav_launch_term_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
+    } else if (h->start_on) {
         if (int rc = rmav_launch_start_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
     } else if (h->actuator_on) {
         if (int rc = rmav_launch_actuator_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;

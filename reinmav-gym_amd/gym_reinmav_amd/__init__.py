@@ -7,12 +7,12 @@ All arithmetic runs in the HIP kernels of ``librmav.so``; there is no CPU fallba
 """
 from . import _abi
 from ._abi import RmavError
-from .core import Actuator, BatchedQuadrotor, Disturbance, SensorNoise, StartState, TrackingReward, check_start_state
+from .core import Actuator, BatchedQuadrotor, Disturbance, SensorNoise, StartState, Termination, TrackingReward, check_start_state, check_termination
 from .registration import ENTRY_POINTS, make, register_envs
 from .vec_env import ENV_IDS, QuadrotorVecEnv, VecNormalize
 
 register_envs()
 
-__all__ = ["BatchedQuadrotor", "TrackingReward", "Disturbance", "SensorNoise", "Actuator", "StartState", "check_start_state", "QuadrotorVecEnv", "RmavError", "make", "register_envs", "ENTRY_POINTS", "ENV_IDS",
+__all__ = ["BatchedQuadrotor", "TrackingReward", "Disturbance", "SensorNoise", "Actuator", "StartState", "check_start_state", "Termination", "check_termination", "QuadrotorVecEnv", "RmavError", "make", "register_envs", "ENTRY_POINTS", "ENV_IDS",
            "VecNormalize", "_abi"]
 __version__ = "0.1.0"

@@ -91,6 +91,12 @@ class StartStateSpec(C.Structure):
     _fields_ = [("lo", C.c_float * 16), ("hi", C.c_float * 16)]
 
 
+class TerminationSpec(C.Structure):
+    """``rmav_termination_spec``."""
+
+    _fields_ = [("pos_lo", C.c_float * 3), ("pos_hi", C.c_float * 3), ("max_tilt", C.c_float), ("_reserved", C.c_int32)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -182,6 +188,8 @@ PROTOTYPES = {
     "rmav_set_actuator_state": (C.c_int, [C.c_void_p, _fp, C.c_int, C.c_int]),
     "rmav_set_start_state": (C.c_int, [C.c_void_p, C.POINTER(StartStateSpec)]),
     "rmav_get_start_state": (C.c_int, [C.c_void_p, C.POINTER(StartStateSpec), C.POINTER(C.c_int32)]),
+    "rmav_set_termination": (C.c_int, [C.c_void_p, C.POINTER(TerminationSpec)]),
+    "rmav_get_termination": (C.c_int, [C.c_void_p, C.POINTER(TerminationSpec), C.POINTER(C.c_int32)]),
     "rmav_episode_truncated": (C.c_int, [C.c_void_p, _u8p, C.c_int]),
     "rmav_step_final": (C.c_int, [C.c_void_p, _fp, _fp, _fp, _u8p, _fp, _u8p, C.c_int, C.c_int]),
     "rmav_rollout_policy_boot": (C.c_int, [C.c_void_p, C.c_int32, _fp, _fp, _fp, _fp, _u8p, _fp, _fp, _fp, _u8p, C.c_int]),

@@ -12,6 +12,8 @@ coalesced).  Trajectories are time-major: ``[T, N, dim]`` / ``[T, dim, N]``.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import re
 from typing import Optional
 
 import numpy as np
@@ -539,6 +541,127 @@ def check_start_state(start_state, kind=None):
     return start_state
 
 
+class Termination:
+    """Termination rules: a per-axis position box, a tilt limit and a finiteness test (``rmav_set_termination``, include/rmav.h), evaluated
+    inside the kernels behind every dynamics step and ORed into the reference's own rule::
+
+        ends = ends_ref or not isfinite(s).all() or any body outside [pos_lo, pos_hi] or tilt > max_tilt
+
+    ``pos_lo``, ``pos_hi``: None (no bound), one value for every axis or a sequence of ``dim`` (2 or 3; ``-inf`` / ``inf`` = no bound on
+    that side), ``pos_lo <= pos_hi``; the slung-load kinds test the load as well.  ``max_tilt``: radians in ``[0, pi]`` or None (no limit):
+    ``|theta|`` of the 2-D kinds (never wrapped), the angle between the body's z axis and the world's of the 3-D kinds.
+    ``Termination()`` adds the finiteness test alone.  The reference's MuJoCo hovering task is
+    ``Termination(pos_lo=(-2, -2, 0.3), pos_hi=(2, 2, inf))``.  Types, lengths, NaN and the order are checked here, before the library is
+    reached."""
+
+    def __init__(self, pos_lo=None, pos_hi=None, max_tilt=None):
+        self.pos_lo, self.pos_hi = self._bound("pos_lo", pos_lo, -math.inf), self._bound("pos_hi", pos_hi, math.inf)
+        lens = {len(x) for x in (self.pos_lo, self.pos_hi) if not isinstance(x, float)}
+        if len(lens) > 1:
+            raise ValueError(f"pos_lo has {len(self.pos_lo)} axes and pos_hi has {len(self.pos_hi)}")
+        los, his = self._pair(lens.pop() if lens else 1)
+        for i, (a, b) in enumerate(zip(los, his)):
+            if a > b:
+                raise ValueError(f"pos_lo[{i}] = {a!r} is above pos_hi[{i}] = {b!r}")
+        if max_tilt is None:
+            self.max_tilt = math.inf
+        else:
+            self.max_tilt = self._number("max_tilt", max_tilt)
+            if not (0.0 <= self.max_tilt <= float(np.float32(math.pi)) or self.max_tilt == math.inf):
+                raise ValueError(f"max_tilt must lie in [0, pi] or be None / inf (no limit), got {max_tilt!r}")
+
+    @staticmethod
+    def _number(name, v):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, (bool, np.bool_)):
+            raise TypeError(f"{name} must be a number, got {v!r}")
+        v = float(v)
+        if v != v:
+            raise ValueError(f"{name} must not be NaN")
+        return v
+
+    @classmethod
+    def _bound(cls, name, v, default):
+        if v is None:
+            return default
+        if isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_)):
+            return cls._number(name, v)
+        if isinstance(v, np.ndarray):
+            v = v.tolist()
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__"):
+            raise TypeError(f"{name} must be None, a number or a sequence of 2 or 3 of them, got {v!r}")
+        if len(v) not in (2, 3):
+            raise ValueError(f"{name} must have 2 or 3 axes, got {len(v)}")
+        return tuple(cls._number(f"{name}[{i}]", x) for i, x in enumerate(v))
+
+    def _pair(self, n):
+        return tuple((x,) * n if isinstance(x, float) else x for x in (self.pos_lo, self.pos_hi))
+
+    @classmethod
+    def parse(cls, text: str) -> "Termination":
+        """``"box=LO:HI,LO:HI[,LO:HI]"``, ``"tilt=RAD"`` or both joined by ``:`` (``box=-2:2,-2:2,0.3:inf:tilt=1.2``): the form of
+        ``examples/train_ppo2.py --termination``."""
+        if not isinstance(text, str):
+            raise TypeError(f"a termination string is wanted, got {text!r}")
+        bad = ValueError(f"--termination wants box=LO:HI,LO:HI[,LO:HI] and / or tilt=RAD, joined by ':'; got {text!r}")
+        lo = hi = tilt = None
+        try:
+            for key, val in re.findall(r"(?:^|:)(box|tilt)=(.*?)(?=:(?:box|tilt)=|$)", text):
+                if key == "tilt":
+                    tilt = float(val)
+                else:
+                    pairs = [tuple(float(x) for x in item.split(":")) for item in val.split(",")]
+                    if any(len(p) != 2 for p in pairs):
+                        raise bad
+                    lo, hi = tuple(p[0] for p in pairs), tuple(p[1] for p in pairs)
+        except ValueError:
+            raise bad from None
+        if (lo is None and tilt is None) or not re.fullmatch(r"(?:(?:^|:)(?:box|tilt)=[^=]*?(?=:(?:box|tilt)=|$))+", text):
+            raise bad
+        return cls(lo, hi, tilt)
+
+    def check_kind(self, kind: int):
+        """The lengths against the kind, which the constructor does not know."""
+        if kind == A.REINMAV:
+            raise ValueError("ReinmavEnv takes no termination rules (its step() ends every episode)")
+        dim = 2 if A.STATE_DIM[kind] in (5, 9) else 3
+        for name in ("pos_lo", "pos_hi"):
+            v = getattr(self, name)
+            if not isinstance(v, float) and len(v) != dim:
+                raise ValueError(f"{name} has {len(v)} axes, {A.KIND_NAMES[kind]} moves in {dim}")
+
+    def spec(self, kind: int) -> "A.TerminationSpec":
+        """``rmav_termination_spec`` for a handle of ``kind`` (fp32; the third axis of a 2-D kind is unbounded)."""
+        self.check_kind(kind)
+        dim = 2 if A.STATE_DIM[kind] in (5, 9) else 3
+        lo, hi = self._pair(dim)
+        lo, hi = lo + (-math.inf,) * (3 - dim), hi + (math.inf,) * (3 - dim)
+        s = A.TerminationSpec((C.c_float * 3)(*lo), (C.c_float * 3)(*hi), self.max_tilt, 0)
+        for i in range(dim):   # (two bounds that differ in fp64 may meet, never cross, in fp32)
+            if not s.pos_lo[i] <= s.pos_hi[i]:
+                raise ValueError(f"pos_lo[{i}] is above pos_hi[{i}] in fp32")
+        return s
+
+    @classmethod
+    def from_spec(cls, s: "A.TerminationSpec", kind: int) -> "Termination":
+        dim = 2 if A.STATE_DIM[kind] in (5, 9) else 3
+        return cls(tuple(s.pos_lo[:dim]), tuple(s.pos_hi[:dim]), None if s.max_tilt == math.inf else s.max_tilt)
+
+    def __repr__(self):
+        return f"Termination(pos_lo={self.pos_lo!r}, pos_hi={self.pos_hi!r}, max_tilt={self.max_tilt!r})"
+
+
+def check_termination(termination, kind=None):
+    """``termination=`` as the constructors take it: None (the reference's rule alone) or a :class:`Termination`; anything else is refused
+    here."""
+    if termination is None:
+        return None
+    if not isinstance(termination, Termination):
+        raise TypeError(f"termination must be None or a Termination, got {termination!r}")
+    if kind is not None:
+        termination.check_kind(kind)
+    return termination
+
+
 class BatchedQuadrotor:
     """N envs of ``kind`` ('quad2d' | 'quad2d_sl' | 'quad3d' | 'quad3d_sl') on GPU ``device``."""
 
@@ -547,7 +670,8 @@ class BatchedQuadrotor:
                  reading_2d: Optional[str] = None, use_torch_stream: bool = True, max_episode_steps: Optional[int] = None,
                  randomize: Optional[dict] = None, frame_skip: int = 1, reward: Optional[TrackingReward] = None,
                  disturbance: Optional[Disturbance] = None, sensor_noise: Optional[SensorNoise] = None,
-                 actuator: Optional[Actuator] = None, start_state: Optional[StartState] = None):
+                 actuator: Optional[Actuator] = None, start_state: Optional[StartState] = None,
+                 termination: Optional[Termination] = None):
         """``max_episode_steps``: episode time limit H (gym's ``TimeLimit``, applied inside the kernels: include/rmav.h,
         rmav_set_time_limit); None or 0 = no limit.
 
@@ -570,7 +694,10 @@ class BatchedQuadrotor:
 
         ``start_state``: a :class:`StartState` (the per-component range of every fresh state; :attr:`start_state`), applied inside the
         kernels; None = the reference's U[-1, 1).  The constructor sets it and then calls :meth:`reset`, so the first episode of every
-        env is drawn under it (at reset index 1: index 0 is the draw of ``rmav_create``)."""
+        env is drawn under it (at reset index 1: index 0 is the draw of ``rmav_create``).
+
+        ``termination``: a :class:`Termination` (position box, tilt limit and finiteness test ORed into the reference's rule;
+        :attr:`termination`), evaluated inside the kernels behind every dynamics step; None = the reference's rule alone."""
         frame_skip = check_frame_skip(frame_skip)
         self.kind = A.KIND_BY_NAME[kind] if isinstance(kind, str) else int(kind)
         reward = check_reward(reward, self.kind)
@@ -578,6 +705,7 @@ class BatchedQuadrotor:
         sensor_noise = check_sensor_noise(sensor_noise, self.kind)
         actuator = check_actuator(actuator, self.kind)
         start_state = check_start_state(start_state, self.kind)
+        termination = check_termination(termination, self.kind)
         self.kind_name = A.KIND_NAMES[self.kind]
         self.num_envs = int(num_envs)
         self.nS, self.nA = A.STATE_DIM[self.kind], A.ACTION_DIM[self.kind]
@@ -611,6 +739,8 @@ class BatchedQuadrotor:
             self.sensor_noise = sensor_noise
         if actuator is not None:
             self.actuator = actuator
+        if termination is not None:   # (the rule is evaluated on states a step produces: the reset below is not tested)
+            self.termination = termination
         if start_state is not None:   # (last: the reset behind it then runs with every other feature in force)
             self.start_state = start_state
             self.reset()
@@ -775,6 +905,21 @@ class BatchedQuadrotor:
             A.check(self._lib.rmav_set_start_state(self._h, None))
         else:
             A.check(self._lib.rmav_set_start_state(self._h, C.byref(start_state.spec(self.kind))))
+
+    @property
+    def termination(self) -> Optional[Termination]:
+        """The :class:`Termination` in force (``rmav_get_termination``; values as the library holds them in fp32), or None: the reference's
+        rule alone.  Assignable at any time: it takes effect with the next step and touches no state."""
+        s, on = A.TerminationSpec(), C.c_int32()
+        A.check(self._lib.rmav_get_termination(self._h, C.byref(s), C.byref(on)))
+        return Termination.from_spec(s, self.kind) if on.value else None
+
+    @termination.setter
+    def termination(self, termination: Optional[Termination]):
+        if check_termination(termination, self.kind) is None:
+            A.check(self._lib.rmav_set_termination(self._h, None))
+        else:
+            A.check(self._lib.rmav_set_termination(self._h, C.byref(termination.spec(self.kind))))
 
     def actuator_state(self, layout: str = "aos", device_out: bool = False):
         """The actuator state ``m`` of every env (``rmav_get_actuator_state``), ``nA`` values per env: with :attr:`actuator` the part of a

@@ -30,7 +30,7 @@ def shard_range(n_total: int, rank: int, world: int) -> Tuple[int, int]:
 
 def make_sharded(kind, n_total: int, rank: int, world: int, device: Optional[int] = None, seed: int = 0, **kw):
     """This rank's ``BatchedQuadrotor`` shard of an ``n_total``-env batch (same ``seed`` on every rank); ``kw`` are its other keywords
-    (``max_episode_steps``, ``randomize``, ``frame_skip``, ``reward``, ``disturbance``, ``sensor_noise``, ``actuator``, ``start_state``, ...), the same on every rank."""
+    (``max_episode_steps``, ``randomize``, ``frame_skip``, ``reward``, ``disturbance``, ``sensor_noise``, ``actuator``, ``start_state``, ``termination``, ...), the same on every rank."""
     from .core import BatchedQuadrotor
 
     start, count = shard_range(n_total, rank, world)

@@ -40,7 +40,7 @@ class NativeQuadrotorEnv(_EnvBase):
     _action_box = None    # (low, high, dtype)
     _reading_2d = None
 
-    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None, frame_skip: int = 1, reward=None, disturbance=None, sensor_noise=None, actuator=None, start_state=None):
+    def __init__(self, device: int = 0, seed=None, max_episode_steps=None, randomize=None, frame_skip: int = 1, reward=None, disturbance=None, sensor_noise=None, actuator=None, start_state=None, termination=None):
         kind = A.KIND_BY_NAME[self._kind]
         nS, nA = A.STATE_DIM[kind], A.ACTION_DIM[kind]
         lo, hi, dt = self._action_box
@@ -62,7 +62,7 @@ class NativeQuadrotorEnv(_EnvBase):
         self._batch = BatchedQuadrotor(kind, 1, device=device, seed=self._seed_value, auto_reset=False,
                                        track_episodes=self._limited, reading_2d=self._reading_2d,
                                        max_episode_steps=max_episode_steps, randomize=randomize, frame_skip=frame_skip,
-                                       reward=reward, disturbance=disturbance, sensor_noise=sensor_noise, actuator=actuator, start_state=start_state)
+                                       reward=reward, disturbance=disturbance, sensor_noise=sensor_noise, actuator=actuator, start_state=start_state, termination=termination)
         self._dim = 2 if nS in (5, 9) else 3
         self._has_load = nS in (9, 16)
         # Lean per-call path: preallocated host arrays and cached ctypes pointers, so a step() is one ABI call

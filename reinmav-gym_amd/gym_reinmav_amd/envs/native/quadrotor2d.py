@@ -12,6 +12,6 @@ class Quadrotor2D(NativeQuadrotorEnv):
     _kind = "quad2d"
     _action_box = (-10.0, 10.0, np.float32)  # quadrotor2d.py:62
 
-    def __init__(self, device: int = 0, seed=None, reading: str = "B", max_episode_steps=None, randomize=None, frame_skip: int = 1, reward=None, disturbance=None, sensor_noise=None, actuator=None, start_state=None):
+    def __init__(self, device: int = 0, seed=None, reading: str = "B", max_episode_steps=None, randomize=None, frame_skip: int = 1, reward=None, disturbance=None, sensor_noise=None, actuator=None, start_state=None, termination=None):
         self._reading_2d = reading
-        super().__init__(device=device, seed=seed, max_episode_steps=max_episode_steps, randomize=randomize, frame_skip=frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise, actuator=actuator, start_state=start_state)
+        super().__init__(device=device, seed=seed, max_episode_steps=max_episode_steps, randomize=randomize, frame_skip=frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise, actuator=actuator, start_state=start_state, termination=termination)

@@ -209,7 +209,7 @@ class RolloutCollector:
             # are not advanced by it; the capture below records launches on the real env without executing them
             tmp = BatchedQuadrotor(env.kind, env.num_envs, device=env.device, seed=0, auto_reset=True,
                                    track_episodes=env.track_episodes, params=env.params, actuator=getattr(env, "actuator", None),
-                                   start_state=getattr(env, "start_state", None))
+                                   start_state=getattr(env, "start_state", None), termination=getattr(env, "termination", None))
             self.env = tmp
             try:
                 self._body()
@@ -551,6 +551,8 @@ class FusedPolicyCollector:
             refuse("an env with actuator=", "actuator-lag")
         if not has_variants and getattr(env, "start_state", None) is not None:
             refuse("an env with start_state=", "start-state")
+        if not has_variants and getattr(env, "termination", None) is not None:
+            refuse("an env with termination=", "termination")
         self._rule = policy_action_rule(deterministic, clip_actions, lambda: (env.params.act_lo, env.params.act_hi))
         if not has_variants and self._rule != (0, -math.inf, math.inf):
             refuse("deterministic= / clip_actions=", "action-rule")

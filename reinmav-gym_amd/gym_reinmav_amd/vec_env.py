@@ -105,7 +105,7 @@ class LazyInfos:
 class QuadrotorVecEnv:
     def __init__(self, env_id: str, num_envs: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  numpy_io: bool = False, dict_infos=None, reading_2d=None, reuse_buffers: bool = False, max_episode_steps=None,
-                 terminal_observation: bool = False, randomize=None, frame_skip: int = 1, reward=None, disturbance=None, sensor_noise=None, actuator=None, start_state=None):
+                 terminal_observation: bool = False, randomize=None, frame_skip: int = 1, reward=None, disturbance=None, sensor_noise=None, actuator=None, start_state=None, termination=None):
         """``dict_infos``: True = a real ``list[dict]`` per step (default up to 4 096 envs), False = a :class:`LazyInfos` (default
         beyond): the same contract - ``len(infos) == num_envs``, ``infos[i].get('episode')`` - materialised on first use.
         ``max_episode_steps``: episode time limit (gym's ``TimeLimit``, inside the kernels); the info of an env that finished an
@@ -124,7 +124,7 @@ class QuadrotorVecEnv:
         kind = ENV_IDS.get(env_id, env_id)
         self.env = BatchedQuadrotor(kind, num_envs, device=device, seed=seed, env_id_base=env_id_base,
                                     auto_reset=True, track_episodes=True, reading_2d=reading_2d, max_episode_steps=max_episode_steps,
-                                    randomize=randomize, frame_skip=frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise, actuator=actuator, start_state=start_state)
+                                    randomize=randomize, frame_skip=frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise, actuator=actuator, start_state=start_state, termination=termination)
         self.num_envs = int(num_envs)
         self.numpy_io = bool(numpy_io)
         self.dict_infos = (num_envs <= 4096) if dict_infos is None else bool(dict_infos)
