@@ -72,6 +72,9 @@ def main():
     ap.add_argument("--eval-envs", dest="eval_envs", type=int, default=1024, metavar="M")
     ap.add_argument("--eval-steps", dest="eval_steps", type=int, default=0,
                     help="steps of an evaluation; default --max_episode_steps (every env then finishes one episode), 256 without one")
+    ap.add_argument("--fused-learner", dest="fused_learner", action="store_true",
+                    help="every minibatch's loss and gradients from the fused learner (rmav_ppo_grad) instead of torch autograd; the "
+                         "all-reduce, the norm clip and Adam stay in torch")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -139,7 +142,7 @@ def main():
                                       max_episode_steps=args.max_episode_steps or None, randomize=randomize or None,
                                       frame_skip=args.frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise,
                                       actuator=actuator, start_state=start_state, termination=termination)
-    learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm)
+    learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm, fused_learner=args.fused_learner)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()
     for it in range(iters):

@@ -238,6 +238,59 @@ int rmav_ret_normalize(rmav_handle h, const void *stats, const float *in, float 
 int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_t *done, const float *values, const float *boot,
                   const void *stats, float gamma, float lam, float reward_scale, float *adv_out, float *ret_out, double *sums_out);
 
+/* ---- the fused learner: clipped-surrogate loss of ONE minibatch and its gradient, one launch per net plus a fold ----------------------
+ * What gym_reinmav_amd.ppo.PPO.loss + backward() compute for an MlpPolicy(value_network = 'copy', hidden = 64) - two 2 x 64 tanh nets and
+ * a state-independent logstd - in fp32, with every activation, delta and weight-gradient accumulator in registers and LDS
+ * (csrc/rmav_learner.hpp).  The optimiser step, the gradient-norm clip and the data-parallel all-reduce stay with the caller.
+ * Per sample j of the minibatch (x = obs, or with obs_stats  x = clamp((obs - mean_f) * rstd_f, +-clip_f), THE arithmetic above; no
+ * gradient flows into the statistics):
+ *     mean = pi(x), v = vf(x);   z = (act - mean) exp(-logstd);   logp = -1/2 sum z^2 - sum logstd - nA/2 log 2 pi
+ *     ratio = exp(logp - logp_old);   a = (adv - adv_norm[0]) * adv_norm[1]
+ *     pg = mean_j max(-a ratio, -a clamp(ratio, 1 - clip, 1 + clip))
+ *     v_clip = val_old + clamp(v - val_old, +-clip);   vf = 1/2 mean_j max((v - ret)^2, (v_clip - ret)^2)
+ *     loss = pg + vf_coef vf - ent_coef sum_c (logstd_c + 1/2 log 2 pi e)
+ * Sub-gradients are torch autograd's: max() hands the gradient to the larger argument and halves it on a tie (so inside the clip range,
+ * where both arguments are equal, it flows as through the unclipped branch), clamp's gradient is 1 on the closed interval.
+ *
+ * The flat gradient, rmav_ppo_grad_param_count(kind) floats, in this fixed order, each tensor in torch's row-major shape:
+ *     pi.W1 [64][nS] | pi.b1 [64] | pi.W2 [64][64] | pi.b2 [64] | pi.W3 [nA][64] | pi.b3 [nA] |
+ *     vf.W1 [64][nS] | vf.b1 [64] | vf.W2 [64][64] | vf.b2 [64] | vf.W3 [1][64]  | vf.b3 [1]  | logstd [nA]
+ * (-1 for a bad kind.)  All five kinds. */
+typedef struct rmav_ppo_grad_spec {
+    float clip;      /* finite, >= 0 (PPO2: 0.2): the ratio clip AND the value clip, as in baselines' ppo2 */
+    float vf_coef;   /* finite (0.5) */
+    float ent_coef;  /* finite (0) */
+    int32_t _reserved; /* 0 */
+} rmav_ppo_grad_spec;
+int64_t rmav_ppo_grad_param_count(int kind);
+/* Bytes of the caller-owned DEVICE workspace of a call with this batch size (per-workgroup partial gradients; 16-byte aligned; its
+ * contents need no initialisation and mean nothing between calls).  -1 for a bad kind or batch < 1. */
+int64_t rmav_ppo_grad_workspace_bytes(int kind, int64_t batch);
+/* Three launches on the handle's stream (the policy net, the value net, the fold of the per-workgroup partials); nothing allocates,
+ * nothing synchronises, the handle's scratch buffer is not used.
+ *   batch       samples of the minibatch, in [1, 2^31)
+ *   idx         int64 [batch] on the DEVICE, or NULL: sample j is column idx[j] of every input array below (NULL: column j).  The
+ *               contents cannot be checked without a synchronisation - THE CALLER'S CONTRACT: 0 <= idx[j] < the pitch of every array
+ *               (obs_pitch, act_pitch, and the lengths of logp_old, val_old, adv, ret)
+ *   obs, act    feature-major [nS][obs_pitch], [nA][act_pitch] (pitches in floats; >= batch when idx is NULL); obs is RAW
+ *   logp_old, val_old, adv, ret   one float per column
+ *   adv_norm    2 floats on the DEVICE: the mean of the minibatch's advantages and 1 / (std + 1e-8)
+ *   params      HOST array of the 13 DEVICE pointers of the parameters, in the order above (as rmav_pack_policy takes them)
+ *   obs_stats   an observation-statistics buffer (rmav_obs_norm_bytes()), or NULL = x is obs
+ *   workspace   rmav_ppo_grad_workspace_bytes(kind, batch) bytes
+ *   grad_out    rmav_ppo_grad_param_count(kind) floats <- the gradient of loss
+ *   stats_out   4 floats <- loss, pg, vf, max_j ratio
+ * DETERMINISM: no floating-point atomics; the launch geometry and the order of every sum depend on (kind, batch) alone, and sample j is
+ * processed in position j whether it came through idx or not: the same inputs give the same bits, and a minibatch given by idx gives
+ * the bits of the same samples gathered into contiguous arrays and passed with idx = NULL.  Samples beyond batch in the last tile read
+ * the last sample's column and contribute exact zeros.
+ * RMAV_ERR_INVALID (the message names the argument): batch < 1, a NULL required pointer, a pitch too small, clip / vf_coef / ent_coef
+ * not finite, clip < 0. */
+int rmav_ppo_grad(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act, int64_t act_pitch,
+                  const float *logp_old, const float *val_old, const float *adv, const float *ret, const float *adv_norm,
+                  const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec, void *workspace, float *grad_out,
+                  float *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

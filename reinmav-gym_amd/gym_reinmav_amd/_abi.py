@@ -97,6 +97,12 @@ class TerminationSpec(C.Structure):
     _fields_ = [("pos_lo", C.c_float * 3), ("pos_hi", C.c_float * 3), ("max_tilt", C.c_float), ("_reserved", C.c_int32)]
 
 
+class PpoGradSpec(C.Structure):
+    """``rmav_ppo_grad_spec``."""
+
+    _fields_ = [("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("_reserved", C.c_int32)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -208,6 +214,10 @@ PROTOTYPES = {
     "rmav_ret_norm_merge": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int32]),
     "rmav_ret_normalize": (C.c_int, [C.c_void_p, _vp, _fp, _fp, C.c_int64, C.c_float]),
     "rmav_gae_norm": (C.c_int, [C.c_void_p, C.c_int32, _fp, _u8p, _fp, _fp, _vp, C.c_float, C.c_float, C.c_float, _fp, _fp, _vp]),
+    "rmav_ppo_grad_param_count": (C.c_int64, [C.c_int]),
+    "rmav_ppo_grad_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "rmav_ppo_grad": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_void_p), _vp,
+                                C.POINTER(PpoGradSpec), _vp, _fp, _fp]),
 }
 
 _lib = None

@@ -660,8 +660,13 @@ class PPO:
 
     def __init__(self, policy: MlpPolicy, lr: float = 3e-4, clip: float = 0.2, epochs: int = 4, minibatches: int = 4,
                  vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5, gamma: float = 0.99,
-                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None):
-        """``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`): baselines' ``VecNormalize(ret=True)`` in front of
+                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None, fused_learner: bool = False):
+        """``fused_learner=True``: every minibatch's loss and gradients come from the fused learner (``rmav_ppo_grad``: one launch per
+        net plus a fold, csrc/rmav_learner.hpp) instead of torch autograd; the all-reduce, the norm clip and Adam run unchanged on
+        the ``p.grad`` it leaves.  An ``MlpPolicy(value_network="copy", hidden=64)`` with CUDA parameters and a collector that has an
+        env handle; anything else is a ``ValueError``.  The default keeps the torch path, bit for bit.
+
+        ``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`): baselines' ``VecNormalize(ret=True)`` in front of
         GAE - ``update`` first merges the rollout's discounted returns into it, then computes the advantages from rewards scaled by
         the statistics that already include them (``ret_norm.py``); ``ro.rew`` stays raw.  ``self.adv`` / ``self.ret`` keep the
         ``[T, N]`` advantages / returns of the last ``update``."""
@@ -672,6 +677,50 @@ class PPO:
         self.opt = torch.optim.Adam(policy.parameters(), lr=lr, eps=1e-5)
         self.clip, self.epochs, self.minibatches = clip, epochs, minibatches
         self.vf_coef, self.ent_coef, self.max_grad_norm, self.gamma, self.lam = vf_coef, ent_coef, max_grad_norm, gamma, lam
+        self.fused_learner = bool(fused_learner)
+        self._fused = None   # (the 13 parameters in the ABI order, the flat gradient, its views): built by the first fused update
+        if self.fused_learner:
+            self._fused_params()
+
+    # the ABI order of rmav_ppo_grad's parameters and of its flat gradient, by NAME (parameters() order is logstd first)
+    _FUSED_NAMES = tuple(f"{net}.{k}.{w}" for net in ("pi", "vf") for k in range(3) for w in ("weight", "bias")) + ("logstd",)
+
+    def _fused_params(self):
+        """The policy's parameters in the fused learner's order; ValueError for a policy it does not compute."""
+        pol = self.policy
+        if getattr(pol, "shared", False):
+            raise ValueError('fused_learner=True computes value_network="copy" (two separate nets); this policy has value_network="shared"')
+        named = dict(pol.named_parameters())
+        if sorted(named) != sorted(self._FUSED_NAMES):
+            raise ValueError(f"fused_learner=True needs an MlpPolicy's parameters {self._FUSED_NAMES}, got {tuple(sorted(named))}")
+        hidden = pol.pi[0].out_features
+        if hidden != 64 or any(net[1].weight.shape != (64, 64) for net in (pol.pi, pol.vf)):
+            raise ValueError(f"fused_learner=True computes hidden=64 (the 2 x 64 baselines mlp), this policy has hidden={hidden}")
+        ps = [named[n] for n in self._FUSED_NAMES]
+        if not all(p.is_cuda for p in ps):
+            raise ValueError("fused_learner=True runs on the GPU: the policy's parameters are CPU tensors (move the policy to the env's device first)")
+        if not all(p.dtype == torch.float32 and p.is_contiguous() for p in ps):
+            raise ValueError("fused_learner=True needs contiguous fp32 parameters")
+        return ps
+
+    def _fused_step(self, env, obs, act, logp_old, val_old, adv, ret, idx):
+        """One minibatch through rmav_ppo_grad: leaves every ``p.grad`` (views of one flat buffer) and returns the device ``stats``."""
+        if self._fused is None:
+            ps = self._fused_params()
+            flat = torch.empty(sum(p.numel() for p in ps), dtype=torch.float32, device=ps[0].device)
+            views, o = [], 0
+            for p in ps:
+                views.append(flat[o:o + p.numel()].view_as(p))
+                o += p.numel()
+            self._fused = (ps, flat, views, torch.empty(4, dtype=torch.float32, device=flat.device))
+        ps, flat, views, stats = self._fused
+        std, mean = torch.std_mean(adv[idx])   # the two reductions the launch does not do (a data-parallel run keeps its per-rank moments)
+        adv_norm = torch.stack((mean, 1.0 / (std + 1e-8)))
+        env.ppo_grad(ps, obs, act, logp_old, val_old, adv, ret, adv_norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                     idx=idx, obs_norm=getattr(self.policy, "obs_norm", None), out=(flat, stats))
+        for p, g in zip(ps, views):
+            p.grad = g
+        return stats
 
     def _allreduce_grads(self):
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
@@ -719,10 +768,25 @@ class PPO:
         stats = {}
         B = T * N
         mb = B // self.minibatches
+        fused_env = None
+        if self.fused_learner:
+            fused_env = getattr(ro, "env", None)
+            if fused_env is None or getattr(fused_env, "_h", None) is None:
+                raise ValueError("fused_learner=True needs a collector with an env handle (ro.env: an open BatchedQuadrotor); this one has none")
+            if not ro.rew.is_cuda:
+                raise ValueError("fused_learner=True runs on the GPU: the collector's buffers are CPU tensors")
+            logp_old, val_old = logp_old.contiguous(), val_old.contiguous()
         for _ in range(self.epochs):
             perm = torch.randperm(B, device=obs.device)
             for i in range(self.minibatches):
                 idx = perm[i * mb:(i + 1) * mb]
+                if fused_env is not None:   # loss, gradients and statistics of the minibatch from rmav_ppo_grad; nothing is gathered but adv
+                    st = self._fused_step(fused_env, obs, act, logp_old, val_old, adv, ret, idx)
+                    self._allreduce_grads()
+                    torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+                    self.opt.step()
+                    stats = {"pg_loss": st[1], "vf_loss": st[2], "ratio_max": st[3]}
+                    continue
                 loss, pg, vf, ratio = self.loss(obs[:, idx], act[:, idx], logp_old[idx], val_old[idx], adv[idx], ret[idx])
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()

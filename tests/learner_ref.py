@@ -1,0 +1,291 @@
+"""The oracle and the inputs of the fused-learner tests (rmav_ppo_grad, csrc/rmav_learner.hpp).
+
+* ``oracle``: ``PPO.loss`` on a ``.double()`` copy of the policy on the CPU with autograd -> the flat gradient in the ABI order of
+  include/rmav_ppo.h, the four statistics, and three clearance distances of the batch (below).
+* ``restate``: the same arithmetic written out by hand in fp64 numpy - forward, loss, the sub-gradients of ``max`` / ``clamp`` as the
+  header documents them, the backward pass - i.e. what the kernel computes, with switches for the arithmetic mutants the host test uses.
+* ``make_case`` / ``trained_policy``: the inputs the GPU test and the host test share.
+
+Clearances.  An fp32 evaluation may legitimately take another branch than the fp64 one when a sample sits on a branch boundary, so
+the tests want every sample away from them:
+  ``ratio``     the smallest distance of any ratio from 1 - clip and 1 + clip
+  ``vclip``     the smallest distance of |v - val_old| from clip
+  ``vf_terms``  the smallest distance between (v - ret)^2 and (v_clip - ret)^2 over the samples with |v - val_old| > clip.  Inside the
+                value clip the two terms are the same number (v_clip = v up to rounding) and so are both branches' gradients: which one
+                an evaluation picks there changes nothing, and those samples carry no such distance.
+A random draw of 2 125 samples always has a few within 1e-3 of a boundary, so ``make_case`` draws the targets themselves - the ratio,
+v - val_old, the position of ret - from distributions with the boundary neighbourhoods cut out, and derives logp_old / val_old / ret from
+the fp64 policy outputs.  Every sample stays in the batch; the tests assert the clearances of what came out."""
+import math
+
+import numpy as np
+import torch
+
+NAMES = tuple(f"{net}.{k}.{w}" for net in ("pi", "vf") for k in range(3) for w in ("weight", "bias")) + ("logstd",)
+KINDS = {"quad2d": (5, 2), "quad2d_sl": (9, 2), "quad3d": (10, 4), "quad3d_sl": (16, 4), "reinmav": (13, 4)}
+CLIP, VF_COEF = 0.2, 0.5
+CLEAR = 1e-3
+# The GPU test's bound per parameter tensor, err = max|g - g64| / max|g64|:  err_kernel <= MARGIN * max(err_torch_fp32, FLOOR).
+# profiles/r23/learner.md derives both numbers.
+MARGIN = 10.0
+FLOOR = 2.0 ** -22
+BATCHES = (1, 31, 32, 33, 64, 65, 130, 2125)
+
+
+class TableNorm:
+    """``clamp((obs - mean_f) * rstd_f, -clip, clip)`` from given tables: what ``MlpPolicy.obs_norm`` needs (``normalize``, ``n_obs``)."""
+
+    def __init__(self, mean_f, rstd_f, clip_f):
+        self.mean_f, self.rstd_f, self.clip_f, self.n_obs = mean_f, rstd_f, float(clip_f), int(mean_f.numel())
+
+    def normalize(self, obs):
+        return torch.clamp((obs - self.mean_f[:, None]) * self.rstd_f[:, None], -self.clip_f, self.clip_f)
+
+    def to(self, **kw):
+        return TableNorm(self.mean_f.to(**kw), self.rstd_f.to(**kw), self.clip_f)
+
+    def buffer(self, device):
+        """the 432-byte statistics buffer of include/rmav_ppo.h with these tables (the running state left zero)"""
+        buf = torch.zeros(108, dtype=torch.float32)
+        n = self.n_obs
+        buf[72:72 + n] = self.mean_f.float()
+        buf[88:104] = 1.0
+        buf[88:88 + n] = self.rstd_f.float()
+        buf[104] = self.clip_f
+        return buf.to(device)
+
+
+def trained_policy(kind, seed, norm=None):
+    """An fp32 CPU MlpPolicy with trained-looking weights: the default init's 0.01 gain on the policy's last layer would hide errors in
+    W3's path, zero biases errors in theirs."""
+    from gym_reinmav_amd.ppo import MlpPolicy
+
+    nS, nA = KINDS[kind]
+    g = torch.Generator().manual_seed(1000 + seed)
+    pol = MlpPolicy(nS, nA, obs_norm=norm)
+    with torch.no_grad():
+        for net in (pol.pi, pol.vf):
+            for k, lin in enumerate(net):
+                lin.weight.copy_(torch.randn(lin.weight.shape, generator=g) * (0.6 / math.sqrt(lin.in_features) if k < 2 else 0.12))
+                lin.bias.copy_(torch.randn(lin.bias.shape, generator=g) * 0.1)
+        pol.logstd.copy_(torch.rand(nA, generator=g) * 0.8 - 0.5)
+    return pol
+
+
+def make_norm(kind, seed):
+    """tables with a non-trivial mean / rstd and a clip that bites (a few per cent of the standard-normal observations)"""
+    nS, _ = KINDS[kind]
+    g = torch.Generator().manual_seed(2000 + seed)
+    return TableNorm(torch.randn(nS, generator=g) * 0.3, torch.rand(nS, generator=g) + 0.7, 1.5)
+
+
+def _excluding(g, n, lo, hi, holes, width):
+    """n draws, uniform on [lo, hi] without the neighbourhoods (h - width, h + width) of the holes"""
+    x = lo + (hi - lo) * torch.rand(n, generator=g, dtype=torch.float64)
+    for _ in range(200):
+        bad = torch.zeros(n, dtype=torch.bool)
+        for h in holes:
+            bad |= (x - h).abs() < width
+        if not bad.any():
+            return x
+        x[bad] = lo + (hi - lo) * torch.rand(int(bad.sum()), generator=g, dtype=torch.float64)
+    raise AssertionError("no draw outside the holes")
+
+
+def make_case(kind, B, seed, norm=None, mode="mixed", clip=CLIP):
+    """fp32 CPU inputs of one minibatch for ``trained_policy(kind, seed, norm)``: dict(obs [nS, B], act [nA, B], logp_old, val_old, adv,
+    ret [B]).  ``mode``: 'mixed' (ratios over [0.5, 2] with both advantage signs, |v - val_old| on both sides of the clip, both vf
+    branches), 'pg_clipped' (every sample's clipped surrogate branch strictly active), 'vf_clipped' (v_clip's branch active everywhere
+    with |v - val_old| > clip)."""
+    nS, nA = KINDS[kind]
+    g = torch.Generator().manual_seed(3000 + 7 * seed + B)
+    pol = trained_policy(kind, seed, norm).double()
+    if norm is not None:
+        pol.obs_norm = norm.to(dtype=torch.float64)
+    obs = torch.randn(nS, B, generator=g).float()
+    with torch.no_grad():
+        mean, v = pol(obs.double())
+        act = (mean + torch.exp(pol.logstd)[:, None] * torch.randn(nA, B, generator=g, dtype=torch.float64)).float()
+        logp = pol.log_prob(mean, act.double())
+    adv = torch.randn(B, generator=g, dtype=torch.float64) * 1.5 + 0.3
+    w = 0.02
+    if mode == "pg_clipped":   # ratio well outside the range on the side that clips for the sample's advantage sign
+        a_sign = torch.sign(adv - adv.float().mean().double()) if B > 1 else torch.sign(adv)
+        up = 1.0 + clip + 0.1 + 0.6 * torch.rand(B, generator=g, dtype=torch.float64)
+        down = 1.0 - clip - 0.1 - 0.3 * torch.rand(B, generator=g, dtype=torch.float64)
+        ratio = torch.where(a_sign > 0, up, down)
+    else:
+        ratio = torch.exp(_excluding(g, B, math.log(0.5), math.log(2.0), (math.log(1 - clip), math.log(1 + clip)), w))
+        ratio[0] = 1.0 + 0.25 * clip   # sample 0 sits inside both clips, so that a batch of one has a gradient in every tensor
+    logp_old = (logp - torch.log(ratio)).float()
+    sign = torch.where(torch.rand(B, generator=g) < 0.5, -1.0, 1.0).double()
+    if mode == "vf_clipped":
+        d = sign * (clip + 0.05 + 0.35 * torch.rand(B, generator=g, dtype=torch.float64))
+    else:
+        d = sign * _excluding(g, B, 0.0, 3 * clip, (clip,), 0.05)
+        d[0] = sign[0] * 0.5 * clip
+    val_old = (v - d).float()
+    # ret: a margin m away from the midpoint of v and v_clip; beyond v_clip's side the clipped term is the larger one
+    vc = val_old.double() + torch.clamp(v - val_old.double(), -clip, clip)
+    m = 0.05 + 0.95 * torch.rand(B, generator=g, dtype=torch.float64)
+    side = torch.sign(d) if mode == "vf_clipped" else torch.where(torch.rand(B, generator=g) < 0.5, -1.0, 1.0).double()
+    ret = (0.5 * (v + vc) + side * m).float()   # vf_clipped: ret on v's side of the midpoint, so v_clip is the farther one
+    return dict(obs=obs, act=act, logp_old=logp_old, val_old=val_old, adv=adv.float(), ret=ret)
+
+
+def adv_moments(adv):
+    """(mean, 1 / (std + 1e-8)) of PPO.loss's normalisation.  A single sample has no std (PPO.loss is NaN there) and would normalise to
+    zero: the tests pass (0, 1) then, i.e. the raw advantage, so that B = 1 still has a policy gradient to check."""
+    if adv.numel() < 2:
+        return torch.zeros((), dtype=adv.dtype, device=adv.device), torch.ones((), dtype=adv.dtype, device=adv.device)
+    return adv.mean(), 1.0 / (adv.std() + 1e-8)
+
+
+def flat_grad(pol):
+    named = dict(pol.named_parameters())
+    return torch.cat([named[n].grad.reshape(-1) for n in NAMES])
+
+
+def slices(kind):
+    """{name: slice of the flat gradient}"""
+    nS, nA = KINDS[kind]
+    sizes = [64 * nS, 64, 4096, 64, 64 * nA, nA, 64 * nS, 64, 4096, 64, 64, 1, nA]
+    out, o = {}, 0
+    for n, s in zip(NAMES, sizes):
+        out[n] = slice(o, o + s)
+        o += s
+    return out
+
+
+def torch_learner(pol, case, clip=CLIP, vf_coef=VF_COEF, ent_coef=0.0):
+    """PPO.loss + backward on ``pol`` (any dtype / device; the case is moved to it) -> (flat grad, [loss, pg, vf, max ratio]) as fp64
+    numpy.  A single sample (its std is NaN) goes through PPO.loss's expressions with the raw advantage, as adv_moments says."""
+    from gym_reinmav_amd.ppo import PPO
+
+    p0 = next(pol.parameters())
+    c = {k: v.to(device=p0.device, dtype=p0.dtype) for k, v in case.items()}
+    ppo = PPO(pol, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef)
+    pol.zero_grad(set_to_none=True)
+    if c["adv"].numel() < 2:
+        loss, pg, vf, ratio = _loss_single(ppo, c)
+    else:
+        loss, pg, vf, ratio = ppo.loss(c["obs"], c["act"], c["logp_old"], c["val_old"], c["adv"], c["ret"])
+    loss.backward()
+    stats = np.array([float(loss.detach()), float(pg.detach()), float(vf.detach()), float(ratio.detach().max())])
+    return flat_grad(pol).detach().double().cpu().numpy(), stats
+
+
+def _loss_single(ppo, c):
+    a = c["adv"]
+    mean, v = ppo.policy(c["obs"])
+    logp = ppo.policy.log_prob(mean, c["act"])
+    ratio = torch.exp(logp - c["logp_old"])
+    pg = torch.max(-a * ratio, -a * torch.clamp(ratio, 1 - ppo.clip, 1 + ppo.clip)).mean()
+    v_clip = c["val_old"] + torch.clamp(v - c["val_old"], -ppo.clip, ppo.clip)
+    vf = 0.5 * torch.max((v - c["ret"]) ** 2, (v_clip - c["ret"]) ** 2).mean()
+    return pg + ppo.vf_coef * vf - ppo.ent_coef * ppo.policy.entropy(), pg, vf, ratio
+
+
+def oracle(kind, seed, case, norm=None, clip=CLIP, vf_coef=VF_COEF, ent_coef=0.0):
+    """-> (flat gradient fp64, stats fp64 [4], clearances dict) of PPO.loss on the .double() CPU policy with autograd"""
+    pol = trained_policy(kind, seed, norm).double()
+    if norm is not None:
+        pol.obs_norm = norm.to(dtype=torch.float64)
+    grad, stats = torch_learner(pol, case, clip, vf_coef, ent_coef)
+    with torch.no_grad():
+        c = {k: v.double() for k, v in case.items()}
+        mean, v = pol(c["obs"])
+        ratio = torch.exp(pol.log_prob(mean, c["act"]) - c["logp_old"])
+        d = (v - c["val_old"]).abs()
+        vc = c["val_old"] + torch.clamp(v - c["val_old"], -clip, clip)
+        gap = ((v - c["ret"]) ** 2 - (vc - c["ret"]) ** 2).abs()[d > clip]
+        clear = {"ratio": float(torch.minimum((ratio - (1 - clip)).abs(), (ratio - (1 + clip)).abs()).min()),
+                 "vclip": float((d - clip).abs().min()),
+                 "vf_terms": float(gap.min()) if gap.numel() else math.inf}
+    return grad, stats, clear
+
+
+# ---- the restatement: what the kernel computes, by hand, in fp64 ---------------------------------------------------------------------
+MUTANTS = ("no_inv_b", "no_tanh_prime", "clip_wrong_side", "no_value_clip", "raw_adv", "no_vf_coef", "ent_sign")
+
+
+def params64(pol):
+    named = dict(pol.named_parameters())
+    return [named[n].detach().double().cpu().numpy().copy() for n in NAMES]
+
+
+def restate(P, case, norm=None, clip=CLIP, vf_coef=VF_COEF, ent_coef=0.0, mutant=None):
+    """P: the 13 fp64 arrays in the ABI order -> (flat gradient, stats [loss, pg, vf, max ratio])"""
+    assert mutant is None or mutant in MUTANTS
+    c = {k: v.double().numpy() for k, v in case.items()}
+    x = c["obs"]
+    if norm is not None:
+        x = np.clip((x - norm.mean_f.double().numpy()[:, None]) * norm.rstd_f.double().numpy()[:, None], -norm.clip_f, norm.clip_f)
+    B = x.shape[1]
+    inv_b = 1.0 if mutant == "no_inv_b" else 1.0 / B
+    logstd = P[12]
+    nA = logstd.size
+
+    def forward(W1, b1, W2, b2, W3, b3):
+        h1 = np.tanh(W1 @ x + b1[:, None])
+        h2 = np.tanh(W2 @ h1 + b2[:, None])
+        return h1, h2, W3 @ h2 + b3[:, None]
+
+    def backward(W2, W3, h1, h2, d3, skip_tanh_prime):
+        d2 = (W3.T @ d3) * (1.0 if skip_tanh_prime else (1.0 - h2 * h2))
+        d1 = (W2.T @ d2) * (1.0 - h1 * h1)
+        return [d1 @ x.T, d1.sum(1), d2 @ h1.T, d2.sum(1), d3 @ h2.T, d3.sum(1)]
+
+    # policy net
+    h1, h2, mean = forward(*P[0:6])
+    inv_std = np.exp(-logstd)[:, None]
+    z = (c["act"] - mean) * inv_std
+    logp = -0.5 * (z * z).sum(0) - logstd.sum() - 0.5 * nA * math.log(2 * math.pi)
+    ratio = np.exp(logp - c["logp_old"])
+    if mutant == "raw_adv":
+        a = c["adv"]
+    else:
+        m = c["adv"].mean() if B > 1 else 0.0
+        rstd = 1.0 / (c["adv"].std(ddof=1) + 1e-8) if B > 1 else 1.0
+        a = (c["adv"] - m) * rstd
+    lo, hi = 1.0 - clip, 1.0 + clip
+    t1, t2 = -a * ratio, -a * np.clip(ratio, lo, hi)
+    inside = (ratio >= lo) & (ratio <= hi)
+    if mutant == "clip_wrong_side":   # min instead of max: the surrogate keeps the gradient where PPO cuts it
+        pg_s = np.minimum(t1, t2)
+        g_ratio = np.where((t1 < t2) | inside, -a, 0.0)
+    else:
+        pg_s = np.maximum(t1, t2)
+        g_ratio = np.where((t1 > t2) | ((t1 == t2) & inside), -a, np.where(t1 == t2, -0.5 * a, 0.0))
+    gl = g_ratio * ratio * inv_b
+    g_pi = backward(P[2], P[4], h1, h2, gl[None, :] * z * inv_std, False)
+    g_logstd = (gl[None, :] * (z * z - 1.0)).sum(1) + (ent_coef if mutant == "ent_sign" else -ent_coef)
+    # value net
+    h1, h2, v = forward(*P[6:12])
+    v = v[0]
+    dv = v - c["val_old"]
+    vc = c["val_old"] + np.clip(dv, -clip, clip)
+    u1, u2 = v - c["ret"], vc - c["ret"]
+    e1, e2 = u1 * u1, u2 * u2
+    ins = (dv >= -clip) & (dv <= clip)
+    if mutant == "no_value_clip":
+        vf_s, gv = e1, 2.0 * u1
+    else:
+        vf_s = np.maximum(e1, e2)
+        gv = np.where(e1 > e2, 2.0 * u1, np.where(e1 < e2, np.where(ins, 2.0 * u2, 0.0), u1 + np.where(ins, u2, 0.0)))
+    coef = 1.0 if mutant == "no_vf_coef" else vf_coef
+    g_vf = backward(P[8], P[10], h1, h2, (coef * 0.5 * gv * inv_b)[None, :], mutant == "no_tanh_prime")
+    pg, vf = pg_s.mean(), 0.5 * vf_s.mean()
+    ent = (logstd + 0.5 * math.log(2 * math.pi * math.e)).sum()
+    stats = np.array([pg + vf_coef * vf - ent_coef * ent, pg, vf, ratio.max()])
+    return np.concatenate([t.reshape(-1) for t in g_pi + g_vf + [g_logstd]]), stats
+
+
+def tensor_errors(kind, g, g64):
+    """{name: max|g - g64| / max|g64|} per parameter tensor"""
+    out = {}
+    for n, s in slices(kind).items():
+        ref = np.abs(g64[s]).max()
+        assert ref > 0, n   # (the exact-zero cases are compared bit for bit, not through this)
+        out[n] = float(np.abs(g[s] - g64[s]).max() / ref)
+    return out

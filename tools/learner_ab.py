@@ -1,0 +1,123 @@
+#!/usr/bin/env python3
+"""A/B of the PPO learner: torch autograd (PPO.update as it always was) against the fused learner (PPO(fused_learner=True) ->
+rmav_ppo_grad), in ONE process, alternating, on the same rollouts.
+
+    python tools/learner_ab.py [--envs 65536] [--steps 32] [--rounds 6] [--out profiles/r23/learner_ab.json]
+
+Shape: quadrotor3d, the per-GPU shape of the PPO benchmark (65 536 envs x 32 steps, 4 epochs x 4 minibatches of 524 288 samples).
+Reports, as one JSON object (also written to --out):
+  update_ms        ms per PPO.update on each path (median and min over the rounds; HIP events around the call, which ends in a host
+                   read of its statistics)
+  grad_us          us per rmav_ppo_grad call (two net launches + the fold) on one minibatch, by HIP events, median of 20
+  flop             the FLOP count of one minibatch: 6 (2 nS 64 + 2 64 64 + 64 nA + 64) per sample (forward, backward and weight
+                   gradients of both nets count 2 FLOP per multiply-add), and the fraction of the fp32 matrix roofline (155 TFLOP/s) and
+                   of the plain vector-FMA rate (half of it) the call reaches
+  end_to_end       env-steps/s of collect + update per actor (fp32 matrix-core, f16 pair) and path
+Timings of one process on one GPU; the two paths see the same rollout data in every round."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "reinmav-gym_amd"))
+
+MATRIX_FP32_TFLOPS = 155.0
+
+
+def timed(fn, torch):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+
+    import gym_reinmav_amd as g
+    from gym_reinmav_amd.ppo import PPO, FusedPolicyCollector, MlpPolicy
+
+    torch.manual_seed(0)
+    N, T = args.envs, args.steps
+    res = {"shape": {"kind": "quad3d", "envs": N, "steps": T, "epochs": 4, "minibatches": 4, "minibatch": N * T // 4},
+           "device": torch.cuda.get_device_name(0)}
+    env = g.BatchedQuadrotor("quad3d", N, seed=0)
+    pols = {"torch": MlpPolicy(env.nS, env.nA).cuda()}
+    pols["fused"] = copy.deepcopy(pols["torch"])
+    ppos = {k: PPO(p, fused_learner=(k == "fused")) for k, p in pols.items()}
+    ro = FusedPolicyCollector(env, pols["torch"], T)
+    ms = {"torch": [], "fused": []}
+    for r in range(args.rounds + 1):   # round 0 warms both paths up (allocator, lazy initialisation)
+        ro.collect()
+        for k in ("torch", "fused") if r % 2 == 0 else ("fused", "torch"):
+            t, st = timed(lambda: ppos[k].update(ro), torch)
+            if r:
+                ms[k].append(t)
+        ro.roll_over()
+    res["update_ms"] = {k: {"median": statistics.median(v), "min": min(v), "all": v} for k, v in ms.items()}
+    res["update_speedup_median"] = res["update_ms"]["torch"]["median"] / res["update_ms"]["fused"]["median"]
+
+    # one rmav_ppo_grad call on one minibatch of the last rollout
+    ppo = ppos["fused"]
+    B = N * T
+    obs = ro.obs[:T].permute(1, 0, 2).reshape(env.nS, B)
+    act = ro.act.permute(1, 0, 2).reshape(env.nA, B)
+    logp, val = ro.logp.reshape(-1), ro.val[:T].reshape(-1).contiguous()
+    adv, ret = ppo.adv.reshape(-1), ppo.ret.reshape(-1)
+    idx = torch.randperm(B, device="cuda")[:B // 4]
+    ts = []
+    for _ in range(23):
+        t, _ = timed(lambda: ppo._fused_step(env, obs, act, logp, val, adv, ret, idx), torch)
+        ts.append(t * 1e3)
+    step_us = statistics.median(ts[3:])
+    an = torch.stack((adv[idx].mean(), 1.0 / (adv[idx].std() + 1e-8)))
+    ps, flat, _, stats = ppo._fused
+    ts = []
+    for _ in range(23):
+        t, _ = timed(lambda: env.ppo_grad(ps, obs, act, logp, val, adv, ret, an, idx=idx, out=(flat, stats)), torch)
+        ts.append(t * 1e3)
+    grad_us = statistics.median(ts[3:])
+    flop = 6 * (2 * env.nS * 64 + 2 * 64 * 64 + 64 * env.nA + 64) * (B // 4)
+    res["grad_us"] = {"rmav_ppo_grad": grad_us, "with_adv_moments_and_grad_views": step_us, "samples": B // 4}
+    res["flop"] = {"per_minibatch": flop, "tflops": flop / grad_us / 1e6, "of_matrix_fp32_roofline": flop / grad_us / 1e6 / MATRIX_FP32_TFLOPS,
+                   "of_vector_fma_rate": flop / grad_us / 1e6 / (MATRIX_FP32_TFLOPS / 2), "roofline_tflops": MATRIX_FP32_TFLOPS}
+
+    # end to end: collect + update, per actor and path
+    res["end_to_end"] = {}
+    for actor, kw in (("fp32_mfma", {}), ("f16_pair", {"f16_mfma": True})):
+        for k in ("torch", "fused"):
+            col = FusedPolicyCollector(env, pols[k], T, **kw)
+            rates = []
+            for r in range(4):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                col.collect()
+                ppos[k].update(col)
+                col.roll_over()
+                torch.cuda.synchronize()
+                if r:
+                    rates.append(N * T / (time.perf_counter() - t0))
+            res["end_to_end"][f"{actor}/{k}"] = {"env_steps_per_s_median": statistics.median(rates), "all": rates}
+    env.close()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
