@@ -72,9 +72,12 @@ def main():
     ap.add_argument("--eval-envs", dest="eval_envs", type=int, default=1024, metavar="M")
     ap.add_argument("--eval-steps", dest="eval_steps", type=int, default=0,
                     help="steps of an evaluation; default --max_episode_steps (every env then finishes one episode), 256 without one")
+    ap.add_argument("--value-network", dest="value_network", default="copy", choices=["copy", "shared"],
+                    help="copy: a separate value net of the policy's shape; shared: a value head on the policy's latent (what baselines "
+                         "builds for these envs), collected by the f16 shared-trunk actor whatever --actor says (not with --actor bf16)")
     ap.add_argument("--fused-learner", dest="fused_learner", action="store_true",
-                    help="every minibatch's loss and gradients from the fused learner (rmav_ppo_grad) instead of torch autograd; the "
-                         "all-reduce, the norm clip and Adam stay in torch")
+                    help="every minibatch's loss and gradients from the fused learner (rmav_ppo_grad, or rmav_ppo_grad_shared with "
+                         "--value-network shared) instead of torch autograd; the all-reduce, the norm clip and Adam stay in torch")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -86,6 +89,8 @@ def main():
     kind = g.ENV_IDS[args.env]
     if args.bootstrap_truncated and not args.max_episode_steps:
         ap.error("--bootstrap_truncated needs --max_episode_steps")
+    if args.value_network == "shared" and args.actor == "bf16":
+        ap.error("--value-network shared runs on the f16 shared-trunk actor, not with --actor bf16")
     randomize = {}
     for item in args.randomize:
         try:
@@ -123,7 +128,7 @@ def main():
                              sensor_noise=sensor_noise, actuator=actuator, start_state=start_state, termination=termination)
     obs_norm = RunningObsNorm(env.nS, f"cuda:{env.device}") if args.normalize_obs else None   # run.py:91-92 VecNormalize(env)
     ret_norm = RunningReturnNorm(f"cuda:{env.device}") if args.normalize_reward else None   # ... and its ret=True half
-    policy = MlpPolicy(env.nS, env.nA, obs_norm=obs_norm).cuda()
+    policy = MlpPolicy(env.nS, env.nA, value_network=args.value_network, obs_norm=obs_norm).cuda()
     if args.load_path:                                      # run.py:188 model.load(load_path)
         policy.load_state_dict(torch.load(args.load_path, map_location="cuda"))
         if obs_norm is not None and os.path.exists(args.load_path + ".obs_norm"):

@@ -291,6 +291,30 @@ int rmav_ppo_grad(rmav_handle h, int64_t batch, const int64_t *idx, const float 
                   const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec, void *workspace, float *grad_out,
                   float *stats_out);
 
+/* ---- the fused learner of the shared-trunk policy: the same loss, ONE net launch plus the fold -------------------------------------
+ * What PPO.loss + backward() compute for an MlpPolicy(value_network = 'shared', hidden = 64): ONE 2 x 64 tanh trunk whose latent h2
+ * feeds the mean head pi.2 and the scalar value head vf.0 (csrc/rmav_learner_shared.hpp).  The loss, the sub-gradient rules, the
+ * arithmetic of x, the statistics and the determinism rule are those of the block above, with  mean = W3 h2 + b3,  v = w_v . h2 + b_v.
+ * What differs:
+ *   one trunk       the observation is read and normalised once, layers 1 and 2 run forward once
+ *   the summed delta   the trunk's gradient is that of BOTH heads: delta 2 = (W3^T d_mean + w_v d_v) * (1 - h2^2), the value head's
+ *                   delta carrying vf_coef
+ *   two launches    the net and the fold of the per-workgroup partials (rmav_ppo_grad: three)
+ * The flat gradient, rmav_ppo_grad_shared_param_count(kind) = 64 nS + 64 + 4096 + 64 + 64 nA + nA + 64 + 1 + nA floats, and the HOST
+ * array params of 9 DEVICE pointers, in this fixed order, each tensor in torch's row-major shape:
+ *     pi.W1 [64][nS] | pi.b1 [64] | pi.W2 [64][64] | pi.b2 [64] | pi.W3 [nA][64] | pi.b3 [nA] | vf.W [1][64] | vf.b [1] | logstd [nA]
+ * (-1 for a bad kind.)  All five kinds. */
+int64_t rmav_ppo_grad_shared_param_count(int kind);
+/* Bytes of the caller-owned DEVICE workspace: workgroups * (rmav_ppo_grad_shared_param_count(kind) + 4) * 4 with one workgroup per
+ * 64-sample tile up to 512; the rules of rmav_ppo_grad_workspace_bytes.  -1 for a bad kind or batch < 1. */
+int64_t rmav_ppo_grad_shared_workspace_bytes(int kind, int64_t batch);
+/* The arguments of rmav_ppo_grad with the same meaning, checks and messages; params holds the 9 pointers above, workspace and grad_out
+ * have the sizes the two functions above give.  stats_out: loss, pg, vf, max_j ratio. */
+int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+                         int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
+                         const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
+                         void *workspace, float *grad_out, float *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

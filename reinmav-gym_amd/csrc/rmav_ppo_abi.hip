@@ -1,5 +1,5 @@
 // rmav_ppo_abi.hip - the C ABI of include/rmav_ppo.h: policy weights, the policy-in-kernel rollouts (their kernels are launched from
-// rmav_policy_abi.hip), GAE, the observation / return normalisers and the fused learner (rmav_ppo_grad).
+// rmav_policy_abi.hip), GAE, the observation / return normalisers and the fused learners (rmav_ppo_grad, rmav_ppo_grad_shared).
 #include <cstdint>
 #include <cstring>
 
@@ -8,6 +8,7 @@
 #include "rmav_obs_norm.hpp"
 #include "rmav_ret_norm.hpp"   // (brings rmav_gae.hpp)
 #include "rmav_learner.hpp"
+#include "rmav_learner_shared.hpp"
 
 using namespace rmav;
 
@@ -516,6 +517,71 @@ int rmav_ppo_grad(rmav_handle h, int64_t batch, const int64_t *idx, const float 
     }
     hipLaunchKernelGGL(k_learner_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, h->stream, (const float *)workspace, (int32_t)groups,
                        a.pstride, n_params, lay.off[12], a.na, a.batch, a.vf_coef, spec->ent_coef, params[12], grad_out, stats_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// ---- the fused learner of the shared-trunk policy: one net launch and the same fold, csrc/rmav_learner_shared.hpp ----------------------
+int64_t rmav_ppo_grad_shared_param_count(int kind) {
+    if (kind < 0 || kind >= kNumKinds) return -1;
+    return trunk_layout(kStateDim[kind], kActionDim[kind]).off[kTrkParams];
+}
+
+int64_t rmav_ppo_grad_shared_workspace_bytes(int kind, int64_t batch) {
+    if (kind < 0 || kind >= kNumKinds || batch < 1) return -1;
+    return (int64_t)learner_groups(batch) * (rmav_ppo_grad_shared_param_count(kind) + kLrnStats) * (int64_t)sizeof(float);
+}
+
+int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+                         int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
+                         const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
+                         void *workspace, float *grad_out, float *stats_out) {
+    CHECK_HANDLE(h);
+    if (batch < 1 || batch > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "batch must be in [1, 2^31), got %lld", (long long)batch);
+    const struct {
+        const void *p;
+        const char *name;
+    } need[] = {{obs, "obs"}, {act, "act"}, {logp_old, "logp_old"}, {val_old, "val_old"}, {adv, "adv"}, {ret, "ret"}, {adv_norm, "adv_norm"},
+                {params, "params"}, {spec, "spec"}, {workspace, "workspace"}, {grad_out, "grad_out"}, {stats_out, "stats_out"}};
+    for (const auto &n : need)
+        if (!n.p) return rmav_fail(RMAV_ERR_INVALID, "%s is NULL (required)", n.name);
+    for (int k = 0; k < kTrkParams; ++k)
+        if (!params[k]) return rmav_fail(RMAV_ERR_INVALID, "params[%d] is NULL (9 device pointers: pi W1 b1 W2 b2 W3 b3, vf W b, logstd)", k);
+    const int64_t min_pitch = idx ? 1 : batch;
+    if (obs_pitch < min_pitch) return rmav_fail(RMAV_ERR_INVALID, "obs_pitch must be >= %lld, got %lld", (long long)min_pitch, (long long)obs_pitch);
+    if (act_pitch < min_pitch) return rmav_fail(RMAV_ERR_INVALID, "act_pitch must be >= %lld, got %lld", (long long)min_pitch, (long long)act_pitch);
+    if (spec->clip - spec->clip != 0.0f || spec->clip < 0.0f) return rmav_fail(RMAV_ERR_INVALID, "clip must be finite and >= 0, got %g", (double)spec->clip);
+    if (spec->vf_coef - spec->vf_coef != 0.0f) return rmav_fail(RMAV_ERR_INVALID, "vf_coef must be finite, got %g", (double)spec->vf_coef);
+    if (spec->ent_coef - spec->ent_coef != 0.0f) return rmav_fail(RMAV_ERR_INVALID, "ent_coef must be finite, got %g", (double)spec->ent_coef);
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "workspace must be 16-byte aligned");
+    if (obs_stats && (reinterpret_cast<uintptr_t>(obs_stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "obs_stats must be 16-byte aligned");
+    TrunkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.idx = idx;
+    a.obs = obs;
+    a.act = act;
+    a.obs_pitch = obs_pitch;
+    a.act_pitch = act_pitch;
+    a.logp_old = logp_old;
+    a.val_old = val_old;
+    a.adv = adv;
+    a.ret = ret;
+    a.adv_norm = adv_norm;
+    a.norm_tab = obs_stats ? ((const ObsNormStats *)obs_stats)->mean_f : nullptr;
+    a.partial = (float *)workspace;
+    a.clip = spec->clip;
+    a.vf_coef = spec->vf_coef;
+    a.batch = (int32_t)batch;
+    a.ns = kStateDim[h->kind];
+    a.na = kActionDim[h->kind];
+    for (int k = 0; k < kTrkParams; ++k) a.p[k] = params[k];
+    const TrunkLayout lay = trunk_layout(a.ns, a.na);
+    const int32_t n_params = lay.off[kTrkParams];
+    const int groups = learner_groups(batch);   // (kind, batch) alone decide the geometry
+    hipLaunchKernelGGL(k_trunk_grad, dim3((unsigned)groups), dim3(kLrnThreads), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_learner_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, h->stream, (const float *)workspace, (int32_t)groups,
+                       n_params + kLrnStats, n_params, lay.off[8], a.na, a.batch, a.vf_coef, spec->ent_coef, params[8], grad_out, stats_out);
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
 }

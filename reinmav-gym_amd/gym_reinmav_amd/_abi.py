@@ -218,6 +218,10 @@ PROTOTYPES = {
     "rmav_ppo_grad_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
     "rmav_ppo_grad": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_void_p), _vp,
                                 C.POINTER(PpoGradSpec), _vp, _fp, _fp]),
+    "rmav_ppo_grad_shared_param_count": (C.c_int64, [C.c_int]),
+    "rmav_ppo_grad_shared_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "rmav_ppo_grad_shared": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_void_p),
+                                       _vp, C.POINTER(PpoGradSpec), _vp, _fp, _fp]),
 }
 
 _lib = None

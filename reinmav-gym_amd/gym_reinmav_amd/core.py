@@ -1185,6 +1185,48 @@ class BatchedQuadrotor:
                                         vp(ret), vp(adv_norm), ptrs, vp(obs_norm), C.byref(spec), vp(ws), vp(grad), vp(stats)))
         return grad, stats
 
+    def ppo_grad_shared(self, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip: float = 0.2, vf_coef: float = 0.5,
+                        ent_coef: float = 0.0, idx=None, obs_norm=None, out=None):
+        """:meth:`ppo_grad` for the shared-trunk policy (``rmav_ppo_grad_shared``, include/rmav_ppo.h): one net launch and a fold.
+
+        ``policy_params``: the 9 contiguous fp32 CUDA tensors ``pi.W1 b1 W2 b2 W3 b3 | vf.W vf.b | logstd`` of an
+        ``MlpPolicy(value_network="shared", hidden=64)``; every other argument, the returned ``(grad, stats)`` (the flat gradient in
+        that order) and the caller's contract on ``idx`` are :meth:`ppo_grad`'s.  The cached outputs and the workspace are this
+        method's own."""
+        f32 = torch.float32
+        M = int(obs.shape[1])
+        assert tuple(obs.shape) == (self.nS, M) and tuple(act.shape) == (self.nA, M) and obs.dtype == f32 and act.dtype == f32
+        assert obs.stride(1) == 1 and act.stride(1) == 1, "obs / act are feature-major with unit stride along the samples"
+        for x in (logp_old, val_old, adv, ret):
+            assert x.dtype == f32 and tuple(x.shape) == (M,) and x.is_contiguous()
+        assert adv_norm.dtype == f32 and adv_norm.numel() == 2 and adv_norm.is_contiguous()
+        ps = [p.detach() for p in policy_params]
+        assert len(ps) == 9 and all(p.is_cuda and p.dtype == f32 and p.is_contiguous() for p in ps), "9 contiguous fp32 CUDA tensors"
+        if idx is not None:
+            assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and idx.is_cuda
+        B = M if idx is None else int(idx.numel())
+        n_par = int(self._lib.rmav_ppo_grad_shared_param_count(self.kind))
+        assert sum(p.numel() for p in ps) == n_par, "the parameters are not those of an MlpPolicy(value_network='shared', hidden=64) of this env"
+        cache = self.__dict__.setdefault("_ppo_grad_shared_cache", {})
+        dev = obs.device
+        if out is None:
+            if "out" not in cache:
+                cache["out"] = (torch.empty(n_par, dtype=f32, device=dev), torch.empty(4, dtype=f32, device=dev))
+            out = cache["out"]
+        grad, stats = out
+        assert grad.dtype == f32 and grad.numel() == n_par and grad.is_contiguous() and stats.dtype == f32 and stats.numel() == 4
+        need = int(self._lib.rmav_ppo_grad_shared_workspace_bytes(self.kind, max(B, 1)))
+        ws = cache.get("ws")
+        if ws is None or ws.numel() < need:
+            ws = cache["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ptrs = (C.c_void_p * 9)(*[p.data_ptr() for p in ps])
+        spec = A.PpoGradSpec(float(clip), float(vf_coef), float(ent_coef), 0)
+        pitch = lambda x: int(x.stride(0)) if x.shape[0] > 1 else M  # noqa: E731
+        vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        A.check(self._lib.rmav_ppo_grad_shared(self._h, B, vp(idx), vp(obs), pitch(obs), vp(act), pitch(act), vp(logp_old), vp(val_old),
+                                               vp(adv), vp(ret), vp(adv_norm), ptrs, vp(obs_norm), C.byref(spec), vp(ws), vp(grad), vp(stats)))
+        return grad, stats
+
     def normalize_(self, x, mean: float, rstd: float):
         """In place ``x <- (x - mean) * rstd`` on the env's stream (advantage normalisation)."""
         A.check(self._lib.rmav_normalize(self._h, self._ptr(x), x.numel(), float(mean), float(rstd)))

@@ -70,7 +70,8 @@ class MlpPolicy(torch.nn.Module):
     ``value_network``: ``'copy'`` (default) = a separate value net of the same shape - baselines' MuJoCo default and its classic
     ``MlpPolicy``; ``'shared'`` = a scalar value head on the policy's latent - what baselines' ``build_policy`` does when
     ``value_network`` is None, i.e. for an env type without a ppo2 defaults entry such as the native envs of gym_reinmav
-    (``run.py:63-68``; third-party behaviour restated from memory).  ``self.vf`` is then the one-layer head.
+    (``run.py:63-68``; third-party behaviour restated from memory).  ``self.vf`` is then the one-layer head.  Both architectures have
+    an in-kernel actor (``FusedPolicyCollector``) and, with ``hidden=64``, a fused learner (``PPO(fused_learner=True)``).
 
     ``obs_norm`` (a :class:`~gym_reinmav_amd.obs_norm.RunningObsNorm`): ``forward`` first normalises its input,
     ``clamp((obs - mean_f) * rstd_f, -clip, clip)`` in fp32 from the statistics buffer's tables - the numbers the in-kernel actors of
@@ -661,10 +662,12 @@ class PPO:
     def __init__(self, policy: MlpPolicy, lr: float = 3e-4, clip: float = 0.2, epochs: int = 4, minibatches: int = 4,
                  vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5, gamma: float = 0.99,
                  lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None, fused_learner: bool = False):
-        """``fused_learner=True``: every minibatch's loss and gradients come from the fused learner (``rmav_ppo_grad``: one launch per
-        net plus a fold, csrc/rmav_learner.hpp) instead of torch autograd; the all-reduce, the norm clip and Adam run unchanged on
-        the ``p.grad`` it leaves.  An ``MlpPolicy(value_network="copy", hidden=64)`` with CUDA parameters and a collector that has an
-        env handle; anything else is a ``ValueError``.  The default keeps the torch path, bit for bit.
+        """``fused_learner=True``: every minibatch's loss and gradients come from the fused learner instead of torch autograd
+        (``value_network="copy"``: ``rmav_ppo_grad``, one launch per net plus a fold, csrc/rmav_learner.hpp; ``"shared"``:
+        ``rmav_ppo_grad_shared``, one launch for the trunk and both heads plus the fold, csrc/rmav_learner_shared.hpp); the
+        all-reduce, the norm clip and Adam run unchanged on the ``p.grad`` it leaves.  An ``MlpPolicy(hidden=64)`` of either
+        architecture with CUDA parameters and a collector that has an env handle; anything else is a ``ValueError``.  The default keeps
+        the torch path, bit for bit.
 
         ``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`): baselines' ``VecNormalize(ret=True)`` in front of
         GAE - ``update`` first merges the rollout's discounted returns into it, then computes the advantages from rewards scaled by
@@ -678,33 +681,37 @@ class PPO:
         self.clip, self.epochs, self.minibatches = clip, epochs, minibatches
         self.vf_coef, self.ent_coef, self.max_grad_norm, self.gamma, self.lam = vf_coef, ent_coef, max_grad_norm, gamma, lam
         self.fused_learner = bool(fused_learner)
-        self._fused = None   # (the 13 parameters in the ABI order, the flat gradient, its views): built by the first fused update
+        self._fused = None   # (the 13 or 9 parameters in the ABI order, the flat gradient, its views): built by the first fused update
         if self.fused_learner:
             self._fused_params()
 
     # the ABI order of rmav_ppo_grad's parameters and of its flat gradient, by NAME (parameters() order is logstd first)
     _FUSED_NAMES = tuple(f"{net}.{k}.{w}" for net in ("pi", "vf") for k in range(3) for w in ("weight", "bias")) + ("logstd",)
+    # ... and of rmav_ppo_grad_shared's: the trunk and the mean head, the value head, logstd
+    _FUSED_NAMES_SHARED = tuple(f"pi.{k}.{w}" for k in range(3) for w in ("weight", "bias")) + ("vf.0.weight", "vf.0.bias", "logstd")
 
     def _fused_params(self):
-        """The policy's parameters in the fused learner's order; ValueError for a policy it does not compute."""
+        """The policy's parameters in the fused learner's order (that of its architecture); ValueError for a policy it does not compute."""
         pol = self.policy
-        if getattr(pol, "shared", False):
-            raise ValueError('fused_learner=True computes value_network="copy" (two separate nets); this policy has value_network="shared"')
+        shared = bool(getattr(pol, "shared", False))
+        names = self._FUSED_NAMES_SHARED if shared else self._FUSED_NAMES
         named = dict(pol.named_parameters())
-        if sorted(named) != sorted(self._FUSED_NAMES):
-            raise ValueError(f"fused_learner=True needs an MlpPolicy's parameters {self._FUSED_NAMES}, got {tuple(sorted(named))}")
+        if sorted(named) != sorted(names):
+            raise ValueError(f"fused_learner=True needs an MlpPolicy's parameters {names}, got {tuple(sorted(named))}")
         hidden = pol.pi[0].out_features
-        if hidden != 64 or any(net[1].weight.shape != (64, 64) for net in (pol.pi, pol.vf)):
+        if hidden != 64 or any(net[1].weight.shape != (64, 64) for net in ((pol.pi,) if shared else (pol.pi, pol.vf))):
             raise ValueError(f"fused_learner=True computes hidden=64 (the 2 x 64 baselines mlp), this policy has hidden={hidden}")
-        ps = [named[n] for n in self._FUSED_NAMES]
+        ps = [named[n] for n in names]
         if not all(p.is_cuda for p in ps):
-            raise ValueError("fused_learner=True runs on the GPU: the policy's parameters are CPU tensors (move the policy to the env's device first)")
+            what = 'this value_network="shared" policy\'s' if shared else "the policy's"
+            raise ValueError(f"fused_learner=True runs on the GPU: {what} parameters are CPU tensors (move the policy to the env's device first)")
         if not all(p.dtype == torch.float32 and p.is_contiguous() for p in ps):
             raise ValueError("fused_learner=True needs contiguous fp32 parameters")
         return ps
 
     def _fused_step(self, env, obs, act, logp_old, val_old, adv, ret, idx):
-        """One minibatch through rmav_ppo_grad: leaves every ``p.grad`` (views of one flat buffer) and returns the device ``stats``."""
+        """One minibatch through rmav_ppo_grad (a shared-trunk policy: rmav_ppo_grad_shared): leaves every ``p.grad`` (views of one flat
+        buffer) and returns the device ``stats``."""
         if self._fused is None:
             ps = self._fused_params()
             flat = torch.empty(sum(p.numel() for p in ps), dtype=torch.float32, device=ps[0].device)
@@ -716,8 +723,9 @@ class PPO:
         ps, flat, views, stats = self._fused
         std, mean = torch.std_mean(adv[idx])   # the two reductions the launch does not do (a data-parallel run keeps its per-rank moments)
         adv_norm = torch.stack((mean, 1.0 / (std + 1e-8)))
-        env.ppo_grad(ps, obs, act, logp_old, val_old, adv, ret, adv_norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
-                     idx=idx, obs_norm=getattr(self.policy, "obs_norm", None), out=(flat, stats))
+        grad_fn = env.ppo_grad_shared if getattr(self.policy, "shared", False) else env.ppo_grad
+        grad_fn(ps, obs, act, logp_old, val_old, adv, ret, adv_norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
+                idx=idx, obs_norm=getattr(self.policy, "obs_norm", None), out=(flat, stats))
         for p, g in zip(ps, views):
             p.grad = g
         return stats

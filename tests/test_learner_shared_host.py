@@ -1,0 +1,126 @@
+"""The shared-trunk fused learner (rmav_ppo_grad_shared), what can be checked without a GPU: the hand-written fp64 restatement of its
+arithmetic (learner_shared_ref.restate: one forward, two heads, the summed delta) agrees with central differences and with the autograd
+oracle; each arithmetic mutant - learner_ref's seven and the two that cut one head's delta off the trunk - lands at least a decade
+outside the bound the GPU test uses, on the GPU test's own inputs; the inputs the GPU test draws keep the three clearance distances;
+the clipped modes give exact zeros; and PPO(fused_learner=True) accepts the architecture and refuses what it does not compute."""
+import numpy as np
+import pytest
+import torch
+
+import learner_shared_ref as R
+
+SEED = R.SEED
+
+
+def _loss64(P, case, norm, ent_coef):
+    return R.restate(P, case, norm, ent_coef=ent_coef)[1][0]
+
+
+@pytest.mark.parametrize("kind", sorted(R.KINDS))
+@pytest.mark.parametrize("with_norm", [False, True])
+def test_restatement_agrees_with_central_differences_and_autograd(kind, with_norm):
+    norm = R.make_norm(kind, SEED) if with_norm else None
+    case = R.make_case(kind, 65, SEED, norm)
+    P = R.params64(R.trained_policy(kind, SEED, norm))
+    g, stats = R.restate(P, case, norm, ent_coef=0.01)
+    g64, s64, clear = R.oracle(kind, SEED, case, norm, ent_coef=0.01)
+    assert min(clear.values()) >= R.CLEAR, clear
+    np.testing.assert_allclose(stats, s64, rtol=1e-12, atol=1e-13)
+    assert max(R.tensor_errors(kind, g, g64).values()) < 1e-11
+    # central differences on a handful of entries of every tensor (fp64, h = 1e-6: truncation ~1e-12, rounding ~1e-10 of the loss)
+    rng = np.random.default_rng(5)
+    o = 0
+    for k, p in enumerate(P):
+        for e in rng.choice(p.size, size=min(4, p.size), replace=False):
+            h = 1e-6
+            flat = p.reshape(-1)
+            keep = flat[e]
+            flat[e] = keep + h
+            up = _loss64(P, case, norm, 0.01)
+            flat[e] = keep - h
+            dn = _loss64(P, case, norm, 0.01)
+            flat[e] = keep
+            fd = (up - dn) / (2 * h)
+            assert abs(fd - g[o + e]) <= 1e-8 + 1e-6 * abs(g[o + e]), (R.NAMES[k], int(e), fd, g[o + e])
+        o += p.size
+    assert o == g.size == sum(s.stop - s.start for s in R.slices(kind).values())
+
+
+@pytest.mark.parametrize("kind,B", [("quad2d", 33), ("quad3d", 130), ("quad3d_sl", 2125), ("reinmav", 65)])
+@pytest.mark.parametrize("mutant", R.MUTANTS)
+def test_mutants_land_a_decade_outside_the_gpu_bound(kind, B, mutant):
+    """The GPU test's bound is margin(B) * max(err of the torch fp32 learner, FLOOR) per tensor (margin(B) = MARGIN at these sizes);
+    here the fp32 learner runs on the CPU (the same expressions, the same precision) and stands for it."""
+    ent = 0.01
+    assert R.margin(B) == R.MARGIN
+    case = R.make_case(kind, B, SEED)
+    g64, _, clear = R.oracle(kind, SEED, case, ent_coef=ent)
+    assert min(clear.values()) >= R.CLEAR, clear
+    g32, _ = R.torch_learner(R.trained_policy(kind, SEED), case, ent_coef=ent)
+    e32 = R.tensor_errors(kind, g32, g64)
+    bound = {n: R.MARGIN * max(e, R.FLOOR) for n, e in e32.items()}
+    assert max(bound.values()) < 1e-4, bound   # the bound itself is of the order of fp32 rounding
+    P = R.params64(R.trained_policy(kind, SEED))
+    clean = R.tensor_errors(kind, R.restate(P, case, ent_coef=ent)[0], g64)
+    assert all(clean[n] <= bound[n] for n in bound)
+    em = R.tensor_errors(kind, R.restate(P, case, ent_coef=ent, mutant=mutant)[0], g64)
+    worst = max(em[n] / bound[n] for n in bound)
+    assert worst >= 10.0, (mutant, worst, em)
+
+
+def test_the_margin_is_the_chain_rule_evaluated():
+    assert [R.margin(B) for B in R.BATCHES] == [R.MARGIN] * len(R.BATCHES)
+    assert R.chain(2125) == 64 + 64 + 34 and R.chain(32833) == 64 + 128 + 512
+    assert 33.4 < R.margin(32833) < 33.6
+
+
+@pytest.mark.parametrize("kind", sorted(R.KINDS))
+def test_the_gpu_inputs_keep_their_clearances(kind):
+    """every (B, statistics) case the GPU test runs: ratios away from 1 +- clip, |v - val_old| away from clip, the two vf terms apart"""
+    for B in R.BATCHES + ((32833,) if kind == "quad3d" else ()):
+        for with_norm in (False, True):
+            norm = R.make_norm(kind, SEED) if with_norm else None
+            case = R.make_case(kind, B, SEED, norm)
+            _, _, clear = R.oracle(kind, SEED, case, norm)
+            assert min(clear.values()) >= R.CLEAR, (B, with_norm, clear)
+            if B >= 64:   # both sides of both clips, both advantage signs
+                P = R.params64(R.trained_policy(kind, SEED, norm))
+                _, stats = R.restate(P, case, norm)
+                assert stats[3] > 1.2 and case["adv"].min() < 0 < case["adv"].max()
+
+
+@pytest.mark.parametrize("kind", ["quad2d_sl", "quad3d"])
+def test_exact_cases_in_the_restatement(kind):
+    """the batches the GPU test uses for its bitwise zeros: a clipped branch kills its head's gradient exactly, both kill the net's"""
+    sl = R.slices(kind)
+    P = R.params64(R.trained_policy(kind, SEED))
+    trunk = slice(0, sl["pi.2.weight"].start)
+    g, _ = R.restate(P, R.make_case(kind, 130, SEED, mode="pg_clipped"), ent_coef=0.01)
+    assert not g[sl["pi.2.weight"]].any() and not g[sl["pi.2.bias"]].any()
+    np.testing.assert_array_equal(g[sl["logstd"]], -0.01)
+    assert np.abs(g[trunk]).max() > 0 and np.abs(g[sl["vf.0.weight"]]).max() > 0
+    g, _ = R.restate(P, R.make_case(kind, 130, SEED, mode="vf_clipped"))
+    assert not g[sl["vf.0.weight"]].any() and not g[sl["vf.0.bias"]].any()
+    assert np.abs(g[trunk]).max() > 0 and np.abs(g[sl["pi.2.weight"]]).max() > 0 and np.abs(g[sl["logstd"]]).max() > 0
+    g, _ = R.restate(P, R.make_case(kind, 130, SEED, mode="both_clipped"), ent_coef=0.01)
+    assert not g[:sl["logstd"].start].any(), "all eight net tensors"
+    np.testing.assert_array_equal(g[sl["logstd"]], -0.01)
+
+
+def test_fused_learner_accepts_the_architecture_and_refuses_the_rest():
+    from gym_reinmav_amd.ppo import PPO, MlpPolicy
+
+    with pytest.raises(ValueError, match='value_network="shared"') as ei:
+        PPO(MlpPolicy(10, 4, value_network="shared"), fused_learner=True)
+    assert "CPU tensors" in str(ei.value)
+    with pytest.raises(ValueError, match="hidden=32"):
+        PPO(MlpPolicy(10, 4, hidden=32, value_network="shared"), fused_learner=True)
+    ppo = PPO(MlpPolicy(10, 4, value_network="shared"))   # without the flag: the torch path
+    assert ppo.fused_learner is False and ppo._fused is None
+    # the order of the nine tensors, by name (the checks that precede the device check pass for a CPU policy of the right shape)
+    assert PPO._FUSED_NAMES_SHARED == R.NAMES
+    pol = MlpPolicy(10, 4, value_network="shared")
+    assert sorted(dict(pol.named_parameters())) == sorted(R.NAMES)
+    half = MlpPolicy(10, 4, value_network="shared").half()
+    with pytest.raises(ValueError):   # (CPU or non-fp32: either way refused in the constructor)
+        PPO(half, fused_learner=True)

@@ -2,7 +2,7 @@
 """A/B of the PPO learner: torch autograd (PPO.update as it always was) against the fused learner (PPO(fused_learner=True) ->
 rmav_ppo_grad), in ONE process, alternating, on the same rollouts.
 
-    python tools/learner_ab.py [--envs 65536] [--steps 32] [--rounds 6] [--out profiles/r23/learner_ab.json]
+    python tools/learner_ab.py [--envs 65536] [--steps 32] [--rounds 6] [--value-network copy|shared] [--out profiles/r23/learner_ab.json]
 
 Shape: quadrotor3d, the per-GPU shape of the PPO benchmark (65 536 envs x 32 steps, 4 epochs x 4 minibatches of 524 288 samples).
 Reports, as one JSON object (also written to --out):
@@ -13,7 +13,12 @@ Reports, as one JSON object (also written to --out):
                    gradients of both nets count 2 FLOP per multiply-add), and the fraction of the fp32 matrix roofline (155 TFLOP/s) and
                    of the plain vector-FMA rate (half of it) the call reaches
   end_to_end       env-steps/s of collect + update per actor (fp32 matrix-core, f16 pair) and path
-Timings of one process on one GPU; the two paths see the same rollout data in every round."""
+Timings of one process on one GPU; the two paths see the same rollout data in every round.
+
+--value-network shared: the same for an MlpPolicy(value_network="shared") and rmav_ppo_grad_shared (one net launch + the fold).  flop
+is then 6 (nS 64 + 64 64 + 64 (nA + 1)) per sample, grad_us also holds one rmav_ppo_grad call on a copy policy of the same shapes taken
+in the same session (rmav_ppo_grad_copy_same_session), and end_to_end has the one actor of that architecture, f16_shared.  The default,
+copy, prints what it always printed."""
 import argparse
 import copy
 import json
@@ -42,6 +47,7 @@ def main():
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--value-network", dest="value_network", default="copy", choices=["copy", "shared"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -51,10 +57,13 @@ def main():
 
     torch.manual_seed(0)
     N, T = args.envs, args.steps
+    shared = args.value_network == "shared"
     res = {"shape": {"kind": "quad3d", "envs": N, "steps": T, "epochs": 4, "minibatches": 4, "minibatch": N * T // 4},
            "device": torch.cuda.get_device_name(0)}
+    if shared:
+        res["shape"]["value_network"] = "shared"
     env = g.BatchedQuadrotor("quad3d", N, seed=0)
-    pols = {"torch": MlpPolicy(env.nS, env.nA).cuda()}
+    pols = {"torch": MlpPolicy(env.nS, env.nA, value_network=args.value_network).cuda()}
     pols["fused"] = copy.deepcopy(pols["torch"])
     ppos = {k: PPO(p, fused_learner=(k == "fused")) for k, p in pols.items()}
     ro = FusedPolicyCollector(env, pols["torch"], T)
@@ -69,7 +78,7 @@ def main():
     res["update_ms"] = {k: {"median": statistics.median(v), "min": min(v), "all": v} for k, v in ms.items()}
     res["update_speedup_median"] = res["update_ms"]["torch"]["median"] / res["update_ms"]["fused"]["median"]
 
-    # one rmav_ppo_grad call on one minibatch of the last rollout
+    # one rmav_ppo_grad (shared: rmav_ppo_grad_shared) call on one minibatch of the last rollout
     ppo = ppos["fused"]
     B = N * T
     obs = ro.obs[:T].permute(1, 0, 2).reshape(env.nS, B)
@@ -84,19 +93,30 @@ def main():
     step_us = statistics.median(ts[3:])
     an = torch.stack((adv[idx].mean(), 1.0 / (adv[idx].std() + 1e-8)))
     ps, flat, _, stats = ppo._fused
-    ts = []
-    for _ in range(23):
-        t, _ = timed(lambda: env.ppo_grad(ps, obs, act, logp, val, adv, ret, an, idx=idx, out=(flat, stats)), torch)
-        ts.append(t * 1e3)
-    grad_us = statistics.median(ts[3:])
-    flop = 6 * (2 * env.nS * 64 + 2 * 64 * 64 + 64 * env.nA + 64) * (B // 4)
-    res["grad_us"] = {"rmav_ppo_grad": grad_us, "with_adv_moments_and_grad_views": step_us, "samples": B // 4}
+
+    def grad_call_us(fn, ps, out):
+        ts = []
+        for _ in range(23):
+            t, _ = timed(lambda: fn(ps, obs, act, logp, val, adv, ret, an, idx=idx, out=out), torch)
+            ts.append(t * 1e3)
+        return statistics.median(ts[3:])
+
+    grad_us = grad_call_us(env.ppo_grad_shared if shared else env.ppo_grad, ps, (flat, stats))
+    if shared:
+        flop = 6 * (env.nS * 64 + 64 * 64 + 64 * (env.nA + 1)) * (B // 4)
+        res["grad_us"] = {"rmav_ppo_grad_shared": grad_us, "with_adv_moments_and_grad_views": step_us, "samples": B // 4}
+        cps = PPO(MlpPolicy(env.nS, env.nA).cuda(), fused_learner=True)._fused_params()   # the copy learner on the same minibatch
+        res["grad_us"]["rmav_ppo_grad_copy_same_session"] = grad_call_us(env.ppo_grad, cps, None)
+        res["flop_of_copy"] = flop / (6 * (2 * env.nS * 64 + 2 * 64 * 64 + 64 * env.nA + 64) * (B // 4))
+    else:
+        flop = 6 * (2 * env.nS * 64 + 2 * 64 * 64 + 64 * env.nA + 64) * (B // 4)
+        res["grad_us"] = {"rmav_ppo_grad": grad_us, "with_adv_moments_and_grad_views": step_us, "samples": B // 4}
     res["flop"] = {"per_minibatch": flop, "tflops": flop / grad_us / 1e6, "of_matrix_fp32_roofline": flop / grad_us / 1e6 / MATRIX_FP32_TFLOPS,
                    "of_vector_fma_rate": flop / grad_us / 1e6 / (MATRIX_FP32_TFLOPS / 2), "roofline_tflops": MATRIX_FP32_TFLOPS}
 
     # end to end: collect + update, per actor and path
     res["end_to_end"] = {}
-    for actor, kw in (("fp32_mfma", {}), ("f16_pair", {"f16_mfma": True})):
+    for actor, kw in ((("f16_shared", {}),) if shared else (("fp32_mfma", {}), ("f16_pair", {"f16_mfma": True}))):
         for k in ("torch", "fused"):
             col = FusedPolicyCollector(env, pols[k], T, **kw)
             rates = []
