@@ -10,7 +10,7 @@
 #include <ctime>
 #include <new>
 
-#include "rmav_handle.hpp"
+#include "rmav_ladder.hpp"
 #include "rmav_core_kernels.hpp"
 
 using namespace rmav;
@@ -241,53 +241,11 @@ int launch_rollout_kms(rmav_handle h, const RolloutArgs &a_in) {
             }
         }
         if (!launched) hipLaunchKernelGGL((k_rollout<K, MODE, ST>), grid, block, lds_per_pair * g, h->stream, a, kp.p, kp.pc);
-    } else if (h->term_on) {   // a handle with a termination spec: k_rollout_tc, which takes the start-state spec (the identity without one) and all it takes as well
+    } else if (const Rung r = rung_of(h)) {   // a handle on the feature ladder: the highest rung's kernels, which take what every rung below takes as well
         if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_term_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
+            if (int rc = kLadder[r].rollout(h, MODE, ST, a)) return rc;   // (the rungs above the tracking reward have one store policy and ignore ST)
         } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no termination kernel for action mode %d", MODE);
-        }
-    } else if (h->start_on) {   // a handle with a start-state spec: k_rollout_ss, which takes the actuator lag (switched off without a spec) and all it takes as well
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_start_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no start-state kernel for action mode %d", MODE);
-        }
-    } else if (h->actuator_on) {   // a handle with actuator lag: k_rollout_al, which takes the sensor noise (switched off without a spec) and all it takes as well
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_actuator_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no actuator-lag kernel for action mode %d", MODE);
-        }
-    } else if (h->sensor_on) {   // a handle with sensor noise: k_rollout_sn, which takes the disturbance (all-zero without one) and all it takes as well
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_sensor_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no sensor-noise kernel for action mode %d", MODE);
-        }
-    } else if (h->disturb_on) {   // a handle with a disturbance: k_rollout_ds, which takes the reward, the skip, the range and the time limit as well
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_disturb_rollout(h, MODE, a)) return rc;   // (one store policy: ST is not passed on)
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no disturbed kernel for action mode %d", MODE);
-        }
-    } else if (h->reward_on) {   // a handle with a tracking reward: k_rollout_rw, which takes the skip, the range and the time limit as well
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_reward_rollout(h, MODE, ST, a)) return rc;
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no tracking-reward kernel for action mode %d", MODE);
-        }
-    } else if (h->frame_skip > 1) {   // a handle with a frame skip: k_rollout_fs, which takes the range and the time limit as well
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_skip_rollout(h, MODE, ST, a)) return rc;
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no frame-skip kernel for action mode %d", MODE);
-        }
-    } else if (h->range_mask) {   // a handle with a parameter range: k_rollout_dr, with or without a time limit (launch_rollout_km routes it here)
-        if constexpr (K != REINMAV && (MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER)) {
-            if (int rc = rmav_launch_ranged_rollout(h, MODE, ST, a)) return rc;
-        } else {
-            return rmav_fail(RMAV_ERR_INVALID, "no ranged kernel for action mode %d", MODE);
+            return rmav_fail(RMAV_ERR_INVALID, "no %s kernel for action mode %d", kLadder[r].noun, MODE);
         }
     } else {
         if (h->time_limit > 0) {   // (one launch per chunk of a chunk-major call: launch_rollout_km)
@@ -362,12 +320,8 @@ int launch_rollout_km(rmav_handle h, const RolloutArgs &a) {
     constexpr bool has_split = (MODE == ACT_RANDOM || MODE == ACT_CONTROLLER || MODE == ACT_BUFFER) && K != REINMAV;
     // A handle with an episode time limit runs the one-wavefront kernels (k_rollout_tl): the two-wavefront kernels have no time-limited
     // variant, so RMAV_TUNE_SPLIT / RMAV_TUNE_SLICE do not apply; a chunk-major call is one launch per chunk.
-    // A handle with a parameter range (rmav_set_env_param_range) likewise: k_rollout_dr.
-    // A handle with a frame skip (rmav_set_frame_skip) likewise: k_rollout_fs.  One with a tracking reward (rmav_set_reward): k_rollout_rw.
-    // One with a disturbance (rmav_set_disturbance): k_rollout_ds.  One with sensor noise (rmav_set_sensor_noise): k_rollout_sn.
-    // One with actuator lag (rmav_set_actuator): k_rollout_al.  One with a start-state spec (rmav_set_start_state): k_rollout_ss.
-    // One with a termination spec (rmav_set_termination): k_rollout_tc.
-    if (K != REINMAV && (h->time_limit > 0 || h->range_mask || h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on || h->term_on)) {
+    // A handle on the feature ladder (rmav_ladder.hpp) likewise: the one-wavefront kernels of its rung, k_rollout_dr ... k_rollout_tc.
+    if (K != REINMAV && (h->time_limit > 0 || rung_of(h) != RUNG_NONE)) {
         if (h->chunk > 0) {
             for (int64_t first = 0; first < h->n; first += h->chunk) {
                 const RolloutArgs b = slice_args<K>(h, a, first, h->chunk);
@@ -444,34 +398,10 @@ template <int K> int launch_step_k(rmav_handle h, const RolloutArgs &a, bool ctr
     if (h->xchg.armed && h->xchg.fired) h->xchg.stale = true;   // the armed launch's snapshot is no longer the latest
     const KindParams<K> kp = kind_params<K>(h);
     const int st = step_store(h), bs = step_block(h);
-    if (h->term_on) {   // a handle with a termination spec: k_step_tc for every batch size; the control() form is k_control behind it
-        if (int rc = rmav_launch_term_step(h, a, bs, FinalArgs{})) return rc;
-        if (ctrl)
+    if (const Rung r = rung_of(h)) {   // a handle on the feature ladder: its rung's k_step_* for every batch size (eager record load, default store policy)
+        if (int rc = kLadder[r].step(h, a, ctrl, bs, FinalArgs{})) return rc;
+        if (ctrl && kLadder[r].control_behind)   // (only the ranged kernel has a form that ends with control(): k_control behind the others)
             if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
-    } else if (h->start_on) {   // a handle with a start-state spec: k_step_ss for every batch size; the control() form is k_control behind it
-        if (int rc = rmav_launch_start_step(h, a, bs, FinalArgs{})) return rc;
-        if (ctrl)
-            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
-    } else if (h->actuator_on) {   // a handle with actuator lag: k_step_al for every batch size; the control() form is k_control (the command) behind it
-        if (int rc = rmav_launch_actuator_step(h, a, bs, FinalArgs{})) return rc;
-        if (ctrl)
-            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
-    } else if (h->sensor_on) {   // a handle with sensor noise: k_step_sn for every batch size; the control() form is k_control (of the true state) behind it
-        if (int rc = rmav_launch_sensor_step(h, a, bs, FinalArgs{})) return rc;
-        if (ctrl)
-            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
-    } else if (h->disturb_on) {   // a handle with a disturbance: k_step_ds for every batch size; the control() form is k_control (undisturbed) behind it
-        if (int rc = rmav_launch_disturb_step(h, a, bs, FinalArgs{})) return rc;
-        if (ctrl)
-            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
-    } else if (h->reward_on) {   // a handle with a tracking reward: k_step_rw for every batch size; the control() form is k_control behind it
-        if (int rc = rmav_launch_reward_step(h, a, bs, FinalArgs{})) return rc;
-        if (ctrl)
-            if (int rc = launch_control(h, a.ctrl_out, (a.flags & F_AOS) ? RMAV_AOS : RMAV_SOA)) return rc;
-    } else if (h->frame_skip > 1) {   // a handle with a frame skip: k_step_fs for every batch size (rollout_impl has refused the control() form)
-        if (int rc = rmav_launch_skip_step(h, a, bs, FinalArgs{})) return rc;
-    } else if (h->range_mask) {   // a handle with a parameter range: k_step_dr for every batch size (eager record load, default store policy)
-        if (int rc = rmav_launch_ranged_step(h, a, ctrl, bs, FinalArgs{})) return rc;
     } else if (h->time_limit > 0) {   // every batch size: the eager record load, k_step's preloaded arguments (k_step_tl)
         const TimeLimitArgs tl = tl_args(h);
         if (ctrl) launch_step_hot(h, a, kp, bs, k_step_tl<K, true>, tl);
@@ -501,22 +431,8 @@ template <int K> int launch_step_final_k(rmav_handle h, const RolloutArgs &a, co
     const KindParams<K> kp = kind_params<K>(h);
     const int bs = step_block(h);
     const TimeLimitArgs tl = tl_args(h);
-    if (h->term_on) {
-        if (int rc = rmav_launch_term_step(h, a, bs, fa)) return rc;
-    } else if (h->start_on) {
-        if (int rc = rmav_launch_start_step(h, a, bs, fa)) return rc;
-    } else if (h->actuator_on) {
-        if (int rc = rmav_launch_actuator_step(h, a, bs, fa)) return rc;
-    } else if (h->sensor_on) {
-        if (int rc = rmav_launch_sensor_step(h, a, bs, fa)) return rc;
-    } else if (h->disturb_on) {
-        if (int rc = rmav_launch_disturb_step(h, a, bs, fa)) return rc;
-    } else if (h->reward_on) {
-        if (int rc = rmav_launch_reward_step(h, a, bs, fa)) return rc;
-    } else if (h->frame_skip > 1) {
-        if (int rc = rmav_launch_skip_step(h, a, bs, fa)) return rc;
-    } else if (h->range_mask) {
-        if (int rc = rmav_launch_ranged_step(h, a, false, bs, fa)) return rc;
+    if (const Rung r = rung_of(h)) {
+        if (int rc = kLadder[r].step(h, a, false, bs, fa)) return rc;
     } else dispatch_store<ST_DEFAULT, ST_WRITE_THROUGH, ST_STREAM>(step_store(h), [&](auto s) {
         constexpr int ST = decltype(s)::value;
         if (h->time_limit > 0) launch_step_hot(h, a, kp, bs, k_step_final<K, true, ST>, tl, fa);
@@ -1186,8 +1102,8 @@ static int rollout_impl(rmav_handle h, int32_t n_steps, int action_mode, const f
     // One wavefront, one k_step launch, outputs in the pinned block: the kernel publishes its completion in a pinned word and
     // the host spins on that (bounded) instead of hipStreamSynchronize.  What the gym-shaped single env runs.
     bool flag_wait = false;
-    // (not rmav_step_control of a handle with a tracking reward, a disturbance, sensor noise or actuator lag: k_control runs behind k_step_rw / k_step_ds / k_step_sn / k_step_al, which would publish too early)
-    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && (h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on || h->term_on))) {
+    // (not rmav_step_control of a handle from the tracking-reward rung up: k_control runs behind its k_step_*, which would publish too early)
+    if (pinned && n_steps == 1 && h->n <= 64 && action_mode == RMAV_ACT_BUFFER && h->kind != RMAV_REINMAV && !(d_ctrl && kLadder[rung_of(h)].control_behind)) {
         if (!h->done_flag && hipHostMalloc((void **)&h->done_flag, 64, hipHostMallocMapped) == hipSuccess) {
             *h->done_flag = 0;
             if (hipHostGetDevicePointer((void **)&h->done_flag_dev, h->done_flag, 0) != hipSuccess) {

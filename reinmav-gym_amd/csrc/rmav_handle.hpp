@@ -383,8 +383,9 @@ inline void take_armed_exchange(rmav_handle h, rmav::RolloutArgs &a, int envs_pe
 }
 
 // Right after the hipLaunchKernelGGL of a rollout that may have taken the armed exchange: a launch that failed will never publish
-// its arrival words, so the exchange goes back to "armed, not fired" and rmav_allgather_stats_post packs as usual.
-inline int check_rollout_launch(rmav_handle h, const rmav::RolloutArgs &a) {
+// its arrival words, so the exchange goes back to "armed, not fired" and rmav_allgather_stats_post packs as usual.  (One copy, out of
+// line: every instantiation of the rollout launchers ends with it.)
+__attribute__((noinline)) inline int check_rollout_launch(rmav_handle h, const rmav::RolloutArgs &a) {
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess) return RMAV_OK;
     if (a.xsend) h->xchg.fired = false;
@@ -463,82 +464,57 @@ constexpr bool policy_has_variants(int kmode) {
 RMAV_INTERNAL int rmav_launch_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt = nullptr,
                                              const rmav::NormArgs *nm = nullptr);
 
-// rmav_range_abi.hip: the launches of a handle with a parameter range (rmav_set_env_param_range).  _rollout: ONE launch of
-// k_rollout_dr<K, mode, st, time limit?> over the envs a names (mode = ACT_BUFFER | ACT_RANDOM | ACT_CONTROLLER, st = a store policy;
-// ST_AOS_LDS runs the write-through kernel); _step: k_step_dr at bs threads per workgroup, ctrl = the launch ends with control(),
-// fa = what rmav_step_final wants (NULL pointers otherwise).  The caller checks hipGetLastError.
+// The rung units (the feature ladder: rmav_ladder.hpp has the order, the table of these launchers and what routes through it).  Every rung
+// has a unit rmav_<x>_abi.hip with two launchers of one shape, and the kernels of a rung take the arguments of every rung below as well
+// (rmav_rung_launch.hpp: rung_tail; a feature the handle lacks is passed switched off - mask = 0, k = 1, the all-zero disturbance, ...):
+//   _rollout  ONE launch of k_rollout_<x> over the envs a names: mode = ACT_BUFFER | ACT_RANDOM | ACT_CONTROLLER; st = a store policy for
+//             the rungs up to the tracking reward (ST_AOS_LDS runs the write-through kernel), ignored above (one store policy).  a.t0 is the
+//             step counter of the launch's first step.
+//   _step     k_step_<x> at bs threads per workgroup; fa = what rmav_step_final wants (NULL pointers otherwise); ctrl = the launch ends with
+//             control(): the ranged kernel alone has that form, the others ignore it.
+// The rungs from the sensor noise up also have a policy unit rmav_<x>_policy_abi.hip whose _policy_rollout launches k_rollout_nrm_<x>,
+// k_rollout_pair_<x> or k_rollout_pair_shared_<x> with rmav_launch_policy_rollout's arguments (kmode = ACT_POLICY_F32M | ACT_POLICY_F16 |
+// ACT_POLICY_F16_SHARED, any other is RMAV_ERR_INVALID; nm is required, bt on a time-limited handle); the rungs below are variants of
+// rmav_policy_abi.hip's kernels.  The _sync functions rewrite the handle's device copy of a spec (what the policy kernels read by pointer)
+// with one small launch on the handle's stream: no allocation, no synchronisation.  The caller checks hipGetLastError.
+// a parameter range (rmav_set_env_param_range): k_rollout_dr<K, mode, st, time limit?>, k_step_dr<K, ctrl, time limit?>
 RMAV_INTERNAL int rmav_launch_ranged_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
 RMAV_INTERNAL int rmav_launch_ranged_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
-
-// rmav_skip_abi.hip: the launches of a handle with a frame skip (rmav_set_frame_skip), shaped as the ranged ones.  _rollout: ONE launch of
-// k_rollout_fs<K, mode, st, time limit?> over the envs a names; _step: k_step_fs at bs threads per workgroup (there is no form that
-// ends with control()).  Both take the handle's range (mask = 0 without one).  The caller checks hipGetLastError.
+// a frame skip (rmav_set_frame_skip): k_rollout_fs, k_step_fs<K, time limit?> (rollout_impl refuses the control() form)
 RMAV_INTERNAL int rmav_launch_skip_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_skip_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
-
-// rmav_reward_abi.hip: the launches of a handle with a tracking reward (rmav_set_reward), shaped as the frame-skip ones, whose arguments
-// they take as well (k = 1 without a skip, mask = 0 without a range).  _rollout: ONE launch of k_rollout_rw<K, mode, st, time limit?>;
-// _step: k_step_rw at bs threads per workgroup; _sync: the handle's device copy of the spec, rewritten on the handle's stream (one small launch: no
-// allocation, no synchronisation).  The caller checks hipGetLastError.
+RMAV_INTERNAL int rmav_launch_skip_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
+// a tracking reward (rmav_set_reward): k_rollout_rw, k_step_rw; _sync: k_set_reward (reward_dev)
 RMAV_INTERNAL int rmav_launch_reward_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_reward_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_reward_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
 RMAV_INTERNAL int rmav_sync_reward_dev(rmav_handle h);
-
-// rmav_disturb_abi.hip: the launches of a handle with a disturbance (rmav_set_disturbance), shaped as the tracking-reward ones, whose
-// arguments they take as well (the reward as a template parameter of the kernels: on or off).  _rollout: ONE launch of
-// k_rollout_ds<K, mode, time limit?, reward?> (one store policy); _step: k_step_ds at bs threads per workgroup; _now: k_disturbance_now
-// into out [3][N] (device memory).  a.t0 is the step counter of the launch's first step.  The caller checks hipGetLastError.
-RMAV_INTERNAL int rmav_launch_disturb_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_disturb_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+// a disturbance (rmav_set_disturbance): k_rollout_ds<K, mode, time limit?, reward?>, k_step_ds<K, time limit?, reward?> - the shape of every rung
+// from here up; _now: k_disturbance_now into out [3][N] (device memory); _sync: k_set_disturbance (disturb_dev)
+RMAV_INTERNAL int rmav_launch_disturb_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_disturb_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
 RMAV_INTERNAL int rmav_launch_disturbance_now(rmav_handle h, float *out_dev);
-// ... and k_set_disturbance: the handle's device copy of the spec (disturb_dev), rewritten in stream order; no allocation, no synchronisation
 RMAV_INTERNAL int rmav_sync_disturb_dev(rmav_handle h);
-
-// rmav_sensor_abi.hip: the launches of a handle with sensor noise (rmav_set_sensor_noise), shaped as the disturbed ones, whose arguments
-// they take as well (a handle without a disturbance: the all-zero spec).  _rollout: ONE launch of k_rollout_sn<K, mode, time limit?, reward?>
-// (one store policy); _step: k_step_sn at bs threads per workgroup; _observe: k_observe of the current state at the handle's step counter
-// into out (device memory, nS * N floats in `layout`).  The caller checks hipGetLastError.
-RMAV_INTERNAL int rmav_launch_sensor_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_sensor_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
-RMAV_INTERNAL int rmav_launch_observe(rmav_handle h, float *out_dev, int layout);
-// rmav_sensor_policy_abi.hip: the policy-in-kernel rollout of a handle with sensor noise - k_rollout_nrm_sn, the fp32 matrix-core actor (kmode
-// ACT_POLICY_F32M; any other is RMAV_ERR_INVALID) - with rmav_launch_policy_rollout's arguments; nm is required, bt on a time-limited handle.
+// sensor noise (rmav_set_sensor_noise): k_rollout_sn, k_step_sn; _observe: k_observe of the current state at the handle's step counter into
+// out (device memory, nS * N floats in `layout`); _sync: k_set_sensor_noise (sensor_dev)
+RMAV_INTERNAL int rmav_launch_sensor_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_sensor_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
 RMAV_INTERNAL int rmav_launch_sensor_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
-// ... and k_set_sensor_noise: the handle's device copy of the spec (sensor_dev), rewritten in stream order; no allocation, no synchronisation
+RMAV_INTERNAL int rmav_launch_observe(rmav_handle h, float *out_dev, int layout);
 RMAV_INTERNAL int rmav_sync_sensor_dev(rmav_handle h);
-
-// rmav_actuator_abi.hip: the launches of a handle with actuator lag (rmav_set_actuator), shaped as the noisy ones, whose arguments they take
-// as well (a handle without sensor noise: sn_on = 0; without a disturbance: the all-zero spec).  _rollout: ONE launch of
-// k_rollout_al<K, mode, time limit?, reward?> (one store policy); _step: k_step_al at bs threads per workgroup; _fill: k_actuator_fill, which
-// sets every env's m to the spec's init, in stream order; _sync: k_set_actuator, the handle's device copy of the coefficients (actuator_dev)
-// rewritten in stream order - no allocation, no synchronisation.  The caller checks hipGetLastError.
-RMAV_INTERNAL int rmav_launch_actuator_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_actuator_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+// actuator lag (rmav_set_actuator): k_rollout_al, k_step_al; _fill: k_actuator_fill, which sets every env's m to the spec's init, in stream
+// order; _sync: k_set_actuator (actuator_dev)
+RMAV_INTERNAL int rmav_launch_actuator_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_actuator_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_actuator_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
 RMAV_INTERNAL int rmav_launch_actuator_fill(rmav_handle h);
 RMAV_INTERNAL int rmav_sync_actuator_dev(rmav_handle h);
-// rmav_actuator_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_al, k_rollout_pair_al, k_rollout_pair_shared_al -
-// with rmav_launch_sensor_policy_rollout's arguments.
-RMAV_INTERNAL int rmav_launch_actuator_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
-
-// rmav_start_abi.hip: the launches of a handle with a start-state spec (rmav_set_start_state), shaped as the lagged ones, whose arguments they
-// take as well (a handle without actuator lag: al_on = 0).  _rollout: ONE launch of k_rollout_ss<K, mode, time limit?, reward?> (one store
-// policy); _step: k_step_ss at bs threads per workgroup; _reset: k_reset_ss, launch_reset's arguments; _sync: k_set_start_state, the handle's
-// device copy of the coefficients (start_dev) rewritten in stream order - no allocation, no synchronisation.  The caller checks hipGetLastError.
-RMAV_INTERNAL int rmav_launch_start_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_start_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
+// a start-state spec (rmav_set_start_state): k_rollout_ss, k_step_ss; _reset: k_reset_ss, launch_reset's arguments; _sync: k_set_start_state (start_dev)
+RMAV_INTERNAL int rmav_launch_start_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_start_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
+RMAV_INTERNAL int rmav_launch_start_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
 RMAV_INTERNAL int rmav_launch_start_reset(rmav_handle h, float *obs_dev, int layout);
 RMAV_INTERNAL int rmav_sync_start_dev(rmav_handle h);
-// rmav_start_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_ss, k_rollout_pair_ss, k_rollout_pair_shared_ss -
-// with rmav_launch_sensor_policy_rollout's arguments.
-RMAV_INTERNAL int rmav_launch_start_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
-
-// rmav_term_abi.hip: the launches of a handle with a termination spec (rmav_set_termination), shaped as those of a start-state spec, whose
-// arguments they take as well (a handle without one: the identity coefficients).  _rollout: ONE launch of k_rollout_tc<K, mode, time limit?,
-// reward?> (one store policy); _step: k_step_tc at bs threads per workgroup; _sync: k_set_termination, the handle's device copy (term_dev)
-// rewritten in stream order - no allocation, no synchronisation.  The caller checks hipGetLastError.
-RMAV_INTERNAL int rmav_launch_term_rollout(rmav_handle h, int mode, const rmav::RolloutArgs &a);
-RMAV_INTERNAL int rmav_launch_term_step(rmav_handle h, const rmav::RolloutArgs &a, int bs, const rmav::FinalArgs &fa);
-RMAV_INTERNAL int rmav_sync_term_dev(rmav_handle h);
-// rmav_term_policy_abi.hip: the policy-in-kernel rollouts of such a handle - k_rollout_nrm_tc, k_rollout_pair_tc, k_rollout_pair_shared_tc -
-// with rmav_launch_sensor_policy_rollout's arguments.
+// a termination spec (rmav_set_termination): k_rollout_tc, k_step_tc; _sync: k_set_termination (term_dev)
+RMAV_INTERNAL int rmav_launch_term_rollout(rmav_handle h, int mode, int st, const rmav::RolloutArgs &a);
+RMAV_INTERNAL int rmav_launch_term_step(rmav_handle h, const rmav::RolloutArgs &a, bool ctrl, int bs, const rmav::FinalArgs &fa);
 RMAV_INTERNAL int rmav_launch_term_policy_rollout(rmav_handle h, int kmode, const rmav::RolloutArgs &a, const rmav::BootArgs *bt, const rmav::NormArgs *nm);
+RMAV_INTERNAL int rmav_sync_term_dev(rmav_handle h);

@@ -855,11 +855,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_sn
     [[maybe_unused]] const BootArgs bt{};
     [[maybe_unused]] const NormArgs nm{};
     static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "noisy launches run the one-wavefront kernels");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 5
+#include "rmav_rollout_rung.inc"
 }
 
 // ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_ds whose nets - the actor and the value net of every step, of the
@@ -879,11 +876,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
     constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 5
+#include "rmav_rollout_rung.inc"
 }
 
 // The one-wavefront kernels of a handle with actuator lag (rmav_set_actuator; ActuatorArgs in rmav_actuator.hpp): k_rollout_sn's body and
@@ -905,15 +899,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_al
     float *const al_m = al.m;
     const uint32_t al_sn = al.sn_on;
     static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "lagged launches run the one-wavefront kernels");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 0
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 6
+#include "rmav_rollout_rung.inc"
 }
 
 // ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_sn whose dynamics read the filtered action.  The filter takes the action
@@ -937,15 +924,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
     constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 0
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 6
+#include "rmav_rollout_rung.inc"
 }
 
 // The one-wavefront kernels of a handle with a start-state spec (rmav_set_start_state; StartArgs in rmav_start.hpp): k_rollout_al's body and
@@ -969,19 +949,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_ss
     const StartCoef &ssc = ss.c;
     const uint32_t ss_al = ss.al_on;
     static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "launches with a start spec run the one-wavefront kernels");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 1
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 0
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 0
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 7
+#include "rmav_rollout_rung.inc"
 }
 
 // ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_al whose fresh states go through the map.  The coefficients are read
@@ -1007,19 +976,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
     constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 1
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 0
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 0
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 7
+#include "rmav_rollout_rung.inc"
 }
 
 // The one-wavefront kernels of a handle with a termination spec (rmav_set_termination; TermArgs in rmav_term.hpp): k_rollout_ss's body and
@@ -1043,23 +1001,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, MODE>())) void k_rollout_tc
     const StartCoef &ssc = ss.c;
     const uint32_t ss_al = ss.al_on;
     static_assert((MODE == ACT_BUFFER || MODE == ACT_RANDOM || MODE == ACT_CONTROLLER) && K != REINMAV, "launches with a termination spec run the one-wavefront kernels");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 1
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 1
-#undef RMAV_ROLLOUT_TC
-#define RMAV_ROLLOUT_TC 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_TC
-#define RMAV_ROLLOUT_TC 0
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 0
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 0
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 8
+#include "rmav_rollout_rung.inc"
 }
 
 // ... and the fp32 matrix-core actor of such a handle: k_rollout_nrm_ss with the rule behind every dynamics sub-step.  The thresholds are read
@@ -1087,23 +1030,8 @@ __global__ __launch_bounds__((rollout_threads_max<K, ACT_POLICY_F32M>())) void k
     constexpr int MODE = ACT_POLICY_F32M, ST = ST_DEFAULT;
     constexpr bool TL = BOOT, FIXED = false, NORM = true, DR = true, FS = true, DS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 1
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 1
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 1
-#undef RMAV_ROLLOUT_TC
-#define RMAV_ROLLOUT_TC 1
-#include "rmav_rollout_body.inc"
-#undef RMAV_ROLLOUT_TC
-#define RMAV_ROLLOUT_TC 0
-#undef RMAV_ROLLOUT_SS
-#define RMAV_ROLLOUT_SS 0
-#undef RMAV_ROLLOUT_AL
-#define RMAV_ROLLOUT_AL 0
-#undef RMAV_ROLLOUT_SN
-#define RMAV_ROLLOUT_SN 0
+#define RMAV_RUNG 8
+#include "rmav_rollout_rung.inc"
 }
 
 // reset_state<K> for the lanes of a wavefront that need it, computed cooperatively (all 64 lanes must be active).

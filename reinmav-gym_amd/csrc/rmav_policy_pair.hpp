@@ -313,11 +313,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_dr(cons
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 1
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a frame skip (rmav_set_frame_skip; FrameSkipArgs in rmav_kernels.hpp): k_rollout_pair_dr - the most general body: a
 // handle without a range passes mask = 0, a call without statistics the identity tables - whose actor wavefront holds each action for
@@ -332,11 +330,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_fs(cons
     constexpr bool TL = BOOT, NORM = true, FS = true, RW = false;
     [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 2
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a tracking reward (rmav_set_reward; RewardArgs in rmav_kernels.hpp): k_rollout_pair_fs (k = 1 without a skip) whose
 // sub-steps are rewarded by reward_rw; the spec is read through the handle's device copy (PolicyRewardArgs).
@@ -350,11 +346,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_rw(cons
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true, FS = true, RW = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 3
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a disturbance (rmav_set_disturbance; rmav_disturb.hpp): k_rollout_pair_rw - whose reward becomes the template
 // parameter RW, as in k_rollout_ds - whose actor wavefront steps under g_vec + d; both specs are read through the handle's device copies.
@@ -369,15 +363,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_ds(cons
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 4
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with sensor noise (rmav_set_sensor_noise; rmav_sensor.hpp): k_rollout_pair_ds - a handle without a disturbance passes
 // the calm spec - whose output rows hold the noisy observation: the actor wavefront computes it once per step, both nets read it.
@@ -393,19 +381,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_sn(cons
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 5
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with actuator lag (rmav_set_actuator; rmav_actuator.hpp): k_rollout_pair_sn whose actor wavefront - the one that
 // integrates - carries the filter state m and feeds the dynamics with it; the action it hands to the critic for storing stays the command.
@@ -427,23 +405,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_al(cons
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 0
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 6
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a start-state spec (rmav_set_start_state; rmav_start.hpp): k_rollout_pair_al whose actor wavefront maps every fresh
 // state it draws; the coefficients are read through the handle's device copy where a state is drawn.
@@ -468,27 +432,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_ss(cons
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 1
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 0
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 0
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 7
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a termination spec (rmav_set_termination; rmav_term.hpp): k_rollout_pair_ss with the rule behind every dynamics
 // sub-step; the thresholds are read through the handle's device copy.
@@ -515,31 +461,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_tc(cons
     constexpr int FMT = FMT_F16;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 1
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 1
-#undef RMAV_PAIR_TC
-#define RMAV_PAIR_TC 1
-#include "rmav_pair_body.inc"
-#undef RMAV_PAIR_TC
-#define RMAV_PAIR_TC 0
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 0
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 0
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 8
+#define RMAV_PAIR_BODY "rmav_pair_body.inc"
+#include "rmav_pair_rung.inc"
 }
 
 // ---- one shared 2 x 64 trunk with a mean head and a value head (RMAV_POLICY_F16_SHARED) -------------------------------------------
@@ -705,11 +629,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     [[maybe_unused]] const FrameSkipArgs fs{};
     [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 1
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a frame skip: k_rollout_pair_shared_dr with the sub-step loop (see k_rollout_pair_fs).
 template <int K, bool BOOT>
@@ -721,11 +643,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     constexpr bool TL = BOOT, NORM = true, FS = true, RW = false;
     [[maybe_unused]] const RewardArgs rw{};
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 2
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a tracking reward: k_rollout_pair_shared_fs with reward_rw (see k_rollout_pair_rw).
 template <int K, bool BOOT>
@@ -737,11 +657,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     const RewardArgs &rw = *ps.rw;
     constexpr bool TL = BOOT, NORM = true, FS = true, RW = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 3
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a disturbance: k_rollout_pair_shared_rw with the reward as a template parameter and wavefront A stepping under
 // g_vec + d (see k_rollout_pair_ds).
@@ -755,15 +673,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     const DisturbRef ds{ps.ds, ps.b0, ps.phase0};
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 4
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with sensor noise: k_rollout_pair_shared_ds whose output rows hold the noisy observation (see k_rollout_pair_sn).
 template <int K, bool BOOT, bool RW>
@@ -777,19 +689,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     const SensorArgs &sn = *ps.sn;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 5
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 
 // ... and of a handle with actuator lag: k_rollout_pair_shared_sn whose wavefront A carries the filter state (see k_rollout_pair_al).
@@ -810,23 +712,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     const uint32_t al_sn = ps.sn_on;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 0
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 6
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 
 // ... and of a handle with a start-state spec: k_rollout_pair_shared_al whose wavefront A maps every fresh state it draws (see k_rollout_pair_ss).
@@ -850,27 +738,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     const uint32_t ss_al = pss.al_on;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 1
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 0
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 0
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 7
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 // ... and of a handle with a termination spec (rmav_set_termination; rmav_term.hpp): k_rollout_pair_shared_ss with the rule behind every dynamics
 // sub-step; the thresholds are read through the handle's device copy.
@@ -896,31 +766,9 @@ __global__ __launch_bounds__(128 * kPairGroupMax, 2) void k_rollout_pair_shared_
     const uint32_t ss_al = pss.al_on;
     constexpr bool TL = BOOT, NORM = true, FS = true;
     static_assert(K != REINMAV, "the four quadrotor kinds");
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 1
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 1
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 1
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 1
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 1
-#undef RMAV_PAIR_TC
-#define RMAV_PAIR_TC 1
-#include "rmav_pair_shared_body.inc"
-#undef RMAV_PAIR_TC
-#define RMAV_PAIR_TC 0
-#undef RMAV_PAIR_SS
-#define RMAV_PAIR_SS 0
-#undef RMAV_PAIR_AL
-#define RMAV_PAIR_AL 0
-#undef RMAV_PAIR_SN
-#define RMAV_PAIR_SN 0
-#undef RMAV_PAIR_DS
-#define RMAV_PAIR_DS 0
-#undef RMAV_PAIR_DR
-#define RMAV_PAIR_DR 0
+#define RMAV_RUNG 8
+#define RMAV_PAIR_BODY "rmav_pair_shared_body.inc"
+#include "rmav_pair_rung.inc"
 }
 
 }  // namespace rmav

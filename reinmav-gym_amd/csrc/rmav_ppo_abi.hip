@@ -3,7 +3,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "rmav_handle.hpp"
+#include "rmav_ladder.hpp"
 #include "rmav_pack_policy.hpp"
 #include "rmav_obs_norm.hpp"
 #include "rmav_ret_norm.hpp"   // (brings rmav_gae.hpp)
@@ -106,32 +106,17 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
                                                "not RMAV_REINMAV: there is no action-rule kernel for it");
         if (int rc = need_variants(precision, "a handle with a policy action rule (rmav_set_policy_action_rule)", "action-rule")) return rc;
     }
-    // ... and so does a handle with a frame skip or a tracking reward: its kernels are the ranged normalised ones with the sub-step loop
-    // ... and one with a disturbance: the *_ds kernels are those with g_vec + d
-    // ... and one with sensor noise: k_rollout_nrm_sn is the disturbed kernel whose nets read the noisy observation
-    // ... and one with actuator lag: the *_al kernels are the noisy ones with the filter between the clipped action and the dynamics
-    // ... and one with a start-state spec: the *_ss kernels are the lagged ones whose fresh states go through the map
-    // ... and one with a termination spec: the *_tc kernels are those of a start-state spec with the rule behind every dynamics sub-step
-    const bool skipped = h->frame_skip > 1 || h->reward_on || h->disturb_on || h->sensor_on || h->actuator_on || h->start_on || h->term_on;
+    // ... and so does a handle on a rung above the range (rmav_ladder.hpp): the policy kernels of every rung from the frame skip up are cut
+    // from the ranged normalised ones, and those of the rung below them
+    const Rung r = rung_of(h);
+    const bool skipped = r >= RUNG_SKIP;
     if (skipped) {
-        if (h->term_on) {
-            if (int rc = need_variants(precision, "a handle with a termination spec (rmav_set_termination)", "termination")) return rc;
-        } else if (h->start_on) {
-            if (int rc = need_variants(precision, "a handle with a start-state spec (rmav_set_start_state)", "start-state")) return rc;
-        } else if (h->actuator_on) {
-            if (int rc = need_variants(precision, "a handle with actuator lag (rmav_set_actuator)", "actuator-lag")) return rc;
-        } else if (h->sensor_on) {
-            if (int rc = need_variants(precision, "a handle with sensor noise (rmav_set_sensor_noise)", "sensor-noise")) return rc;
-        } else if (h->disturb_on) {
-            if (int rc = need_variants(precision, "a handle with a disturbance (rmav_set_disturbance)", "disturbed")) return rc;
-        } else if (h->reward_on) {
-            if (int rc = need_variants(precision, "a handle with a tracking reward (rmav_set_reward)", "tracking-reward")) return rc;
-        } else if (int rc = need_variants(precision, "a handle with a frame skip (rmav_set_frame_skip)", "frame-skip")) return rc;
+        if (int rc = need_variants(precision, kLadder[r].who, kLadder[r].noun)) return rc;
         if (int rc = ensure_range_dev(h)) return rc;
     }
     if (h->range_mask || ruled || skipped) {
         if (h->range_mask)
-            if (int rc = need_variants(precision, "a handle with a parameter range", "ranged")) return rc;
+            if (int rc = need_variants(precision, kLadder[RUNG_RANGE].who, kLadder[RUNG_RANGE].noun)) return rc;
         if (!nm) {
             if (int rc = ensure_ident_norm(h)) return rc;
             nm_r.tab = h->ident_norm;
@@ -143,15 +128,7 @@ static int launch_policy_call(rmav_handle h, int32_t n_steps, const float *weigh
             bt = &bt_r;
         }
     }
-    if (h->term_on) {
-        if (int rc = rmav_launch_term_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
-    } else if (h->start_on) {
-        if (int rc = rmav_launch_start_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
-    } else if (h->actuator_on) {
-        if (int rc = rmav_launch_actuator_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
-    } else if (h->sensor_on) {
-        if (int rc = rmav_launch_sensor_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
-    } else if (int rc = rmav_launch_policy_rollout(h, policy_kmode(precision), a, bt, nm)) return rc;
+    if (int rc = kLadder[r].policy(h, policy_kmode(precision), a, bt, nm)) return rc;   // (the rungs below the sensor noise: rmav_policy_abi.hip's kernels)
     h->t += (uint64_t)n_steps;
     return RMAV_OK;
 }

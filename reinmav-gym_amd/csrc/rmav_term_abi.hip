@@ -2,7 +2,7 @@
 // k_step_tc, the one-wavefront fused rollouts k_rollout_tc, and the small kernel that keeps the handle's device copy of the thresholds,
 // k_set_termination.  A translation unit of its own, as rmav_start_abi.hip and for its reason; rmav_abi.hip decides what a call launches
 // and comes here only for the launch itself.
-#include "rmav_handle.hpp"
+#include "rmav_rung_launch.hpp"
 
 using namespace rmav;
 
@@ -25,75 +25,16 @@ __global__ __launch_bounds__(64) void k_set_termination(uint32_t *dst, const Ter
 
 namespace {
 
-// the handle's reward choice as std::integral_constant<bool, RW>: the kernels take it as a template parameter
-template <typename F> int dispatch_reward(rmav_handle h, F &&f) {
-    if (h->reward_on) return f(std::true_type{});
-    return f(std::false_type{});
-}
-
-template <int K, int MODE> int launch_km(rmav_handle h, const RolloutArgs &a) {
-    const KindParams<K> kp = kind_params<K>(h);
-    const int64_t count = a.slice_count ? (int64_t)a.slice_count : h->n;
-    const dim3 grid((unsigned)((count + block_size(h) - 1) / block_size(h))), block(block_size(h));
-    const TimeLimitArgs tl = tl_args(h);
-    const RangeArgs dr = range_args(h);
-    const FrameSkipArgs fs = skip_args(h);
-    const RewardArgs rw = reward_args(h);
-    const DisturbArgs ds = disturb_or_calm(h, a.t0);
-    const SensorArgs sn = sensor_args(h);
-    const ActuatorArgs al = start_actuator_args(h);
-    const StartArgs ss = term_start_args(h);
-    const TermArgs tc = term_args(h);
-    return dispatch_reward(h, [&](auto r) {
-        constexpr bool RW = decltype(r)::value;
-        if (h->time_limit > 0) hipLaunchKernelGGL((k_rollout_tc<K, MODE, true, RW>), grid, block, 0, h->stream, a, kp.p, kp.pc, tl, dr, fs, rw, ds, sn, al, ss, tc);
-        else hipLaunchKernelGGL((k_rollout_tc<K, MODE, false, RW>), grid, block, 0, h->stream, a, kp.p, kp.pc, tl, dr, fs, rw, ds, sn, al, ss, tc);
-        return (int)RMAV_OK;
-    });
-}
-
-template <int K> int launch_step(rmav_handle h, const RolloutArgs &a, int bs, const FinalArgs &fa) {
-    const KindParams<K> kp = kind_params<K>(h);
-    const dim3 grid((unsigned)((h->n + bs - 1) / bs));
-    const TimeLimitArgs tl = tl_args(h);
-    const RangeArgs dr = range_args(h);
-    const FrameSkipArgs fs = skip_args(h);
-    const RewardArgs rw = reward_args(h);
-    const DisturbArgs ds = disturb_or_calm(h, a.t0);
-    const SensorArgs sn = sensor_args(h);
-    const ActuatorArgs al = start_actuator_args(h);
-    const StartArgs ss = term_start_args(h);
-    const TermArgs tc = term_args(h);
-    // k_step's preloaded leading arguments (StepHot in rmav_kernels.hpp), then the argument block
-    return dispatch_reward(h, [&](auto r) {
-        constexpr bool RW = decltype(r)::value;
-        if (h->time_limit > 0)
-            hipLaunchKernelGGL((k_step_tc<K, true, RW>), grid, dim3(bs), 0, h->stream, a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a,
-                               kp.p, kp.pc, tl, fa, dr, fs, rw, ds, sn, al, ss, tc);
-        else
-            hipLaunchKernelGGL((k_step_tc<K, false, RW>), grid, dim3(bs), 0, h->stream, a.state, a.n, a.act_in, a.pitch, (uint32_t)bs, a.flags, a.ep_ret, a.rec, a,
-                               kp.p, kp.pc, tl, fa, dr, fs, rw, ds, sn, al, ss, tc);
-        return (int)RMAV_OK;
-    });
-}
+struct Kernels {
+    template <int K, int MODE, int ST, bool TL, bool RW> static auto rollout() { return k_rollout_tc<K, MODE, TL, RW>; }
+    template <int K, bool CTRL, bool TL, bool RW> static auto step() { return k_step_tc<K, TL, RW>; }
+};
 
 }  // namespace
 
-int rmav_launch_term_rollout(rmav_handle h, int mode, const RolloutArgs &a) {
-    return dispatch_kind<QUAD_KINDS>(h->kind, [&](auto k) {
-        constexpr int K = decltype(k)::value;
-        switch (mode) {
-        case ACT_BUFFER: return launch_km<K, ACT_BUFFER>(h, a);
-        case ACT_RANDOM: return launch_km<K, ACT_RANDOM>(h, a);
-        case ACT_CONTROLLER: return launch_km<K, ACT_CONTROLLER>(h, a);
-        }
-        return rmav_fail(RMAV_ERR_INVALID, "no termination kernel for action mode %d", mode);
-    });
-}
+int rmav_launch_term_rollout(rmav_handle h, int mode, int st, const RolloutArgs &a) { return launch_rung_rollout<RUNG_TERM, Kernels>(h, mode, st, a); }
 
-int rmav_launch_term_step(rmav_handle h, const RolloutArgs &a, int bs, const FinalArgs &fa) {
-    return dispatch_kind<QUAD_KINDS>(h->kind, [&](auto k) { return launch_step<decltype(k)::value>(h, a, bs, fa); });
-}
+int rmav_launch_term_step(rmav_handle h, const RolloutArgs &a, bool ctrl, int bs, const FinalArgs &fa) { return launch_rung_step<RUNG_TERM, Kernels>(h, a, ctrl, bs, fa); }
 
 int rmav_sync_term_dev(rmav_handle h) {
     hipLaunchKernelGGL(k_set_termination, dim3(1), dim3(64), 0, h->stream, reinterpret_cast<uint32_t *>(h->term_dev), term_args(h), (uint32_t)kCalmHold);
