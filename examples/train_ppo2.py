@@ -78,6 +78,9 @@ def main():
     ap.add_argument("--fused-learner", dest="fused_learner", action="store_true",
                     help="every minibatch's loss and gradients from the fused learner (rmav_ppo_grad, or rmav_ppo_grad_shared with "
                          "--value-network shared) instead of torch autograd; the all-reduce, the norm clip and Adam stay in torch")
+    ap.add_argument("--fused-optimizer", dest="fused_optimizer", action="store_true",
+                    help="with --fused-learner: the advantage moments, the norm clip and Adam in HIP too (rmav_adv_moments, rmav_ppo_adam: "
+                         "one launch instead of clip_grad_norm_ + Adam.step()); the optimiser's state stays torch.optim.Adam's")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -89,6 +92,8 @@ def main():
     kind = g.ENV_IDS[args.env]
     if args.bootstrap_truncated and not args.max_episode_steps:
         ap.error("--bootstrap_truncated needs --max_episode_steps")
+    if args.fused_optimizer and not args.fused_learner:
+        ap.error("--fused-optimizer needs --fused-learner")
     if args.value_network == "shared" and args.actor == "bf16":
         ap.error("--value-network shared runs on the f16 shared-trunk actor, not with --actor bf16")
     randomize = {}
@@ -147,7 +152,8 @@ def main():
                                       max_episode_steps=args.max_episode_steps or None, randomize=randomize or None,
                                       frame_skip=args.frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise,
                                       actuator=actuator, start_state=start_state, termination=termination)
-    learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm, fused_learner=args.fused_learner)
+    learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm, fused_learner=args.fused_learner,
+                  fused_optimizer=args.fused_optimizer)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()
     for it in range(iters):

@@ -315,6 +315,61 @@ int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const
                          const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
                          void *workspace, float *grad_out, float *stats_out);
 
+/* ---- around the fused learner: the advantage moments it takes, and the optimiser step on its gradient --------------------------------
+ * rmav_adv_moments writes the two floats rmav_ppo_grad / rmav_ppo_grad_shared take as adv_norm:
+ *     adv_norm_out[0] = mean_j x_j,   adv_norm_out[1] = 1 / (std + 1e-8),   x_j = adv[idx[j]] (idx NULL: adv[j]),  j < batch
+ * std is torch's default unbiased estimator (divisor batch - 1); batch = 1 gives (x_0, NaN) as torch.std_mean does - no special case.
+ * Two launches on the handle's stream (k_adv_moments, k_adv_moments_fold); nothing allocates, nothing synchronises, the handle's scratch
+ * buffer is not used.  Per lane sum (x - K) and sum (x - K)^2 in fp64 with K = x_0 (x - K is exact in fp64), Chan's pairwise combination
+ * above that in a fixed order, one moment per workgroup in `workspace`, folded in workgroup order.  The last step is fp32, as the torch
+ * expression on fp32 tensors is:
+ *     mean = (float)mean64;   std = (float)sqrt(M2 / (batch - 1));   adv_norm_out[1] = 1.0f / (std + 1e-8f)
+ * DETERMINISM: no atomics; min(ceil(batch / 256), 128) workgroups of 256 lanes, sample j in lane j mod 256 of workgroup (j / 256) mod
+ * workgroups with or without idx, a lane adding its samples in order: the same inputs give the same bits, and the idx route gives the
+ * bits of the gathered route.
+ *   workspace   rmav_adv_moments_workspace_bytes(batch) = 24 * min(ceil(batch / 256), 128) bytes on the DEVICE, 8-byte aligned; its
+ *               contents need no initialisation and mean nothing between calls (-1 for batch < 1)
+ *   idx         int64 [batch] on the DEVICE or NULL; THE CALLER'S CONTRACT on its contents is rmav_ppo_grad's: 0 <= idx[j] < the length
+ *               of adv
+ * RMAV_ERR_INVALID (the message names the argument): batch < 1, adv / workspace / adv_norm_out NULL, a misaligned workspace. */
+int64_t rmav_adv_moments_workspace_bytes(int64_t batch);
+int rmav_adv_moments(rmav_handle h, int64_t batch, const int64_t *idx, const float *adv, void *workspace, float *adv_norm_out);
+
+/* rmav_ppo_adam: what torch.nn.utils.clip_grad_norm_ + torch.optim.Adam.step() (no amsgrad, no weight decay) do to the parameters, from
+ * the flat gradient rmav_ppo_grad / rmav_ppo_grad_shared leave, in ONE launch of one workgroup (k_ppo_adam) on the handle's stream.
+ *   shared      0: the 13 tensors and flat order of rmav_ppo_grad;  1: the 9 of rmav_ppo_grad_shared
+ *   grad        the flat gradient (rmav_ppo_grad_param_count / rmav_ppo_grad_shared_param_count floats), READ ONLY: it keeps the
+ *               unscaled, unclipped gradient (clip_grad_norm_ overwrites p.grad; this call does not)
+ *   params      HOST array of the 13 / 9 DEVICE pointers, updated in place
+ *   exp_avg, exp_avg_sq   Adam's first and second moments, flat, in the order of grad, updated in place (zeros before step 1)
+ *   step        the number of this update, >= 1
+ *   stats_out   2 floats on the DEVICE <- norm, coef; or NULL
+ * THE arithmetic, in fp32, uncontracted, one line per operation, per element i (sqrt and divide correctly rounded):
+ *     g    = grad[i] * grad_scale
+ *     norm = (float)sqrt(sum_i (double)g * (double)g)      strided per-thread partials and a fixed-order reduction in fp64, rounded once
+ *     ratio = max_grad_norm / (norm + 1e-6f)
+ *     coef = ratio >= 1 ? 1 : ratio                          min(1, ratio) that keeps a NaN, as torch.clamp(max = 1) does
+ *     gh   = g * coef
+ *     d = gh - m;   td = omb1 * d;   m = m + td              omb1 = 1.0f - beta1 (fp32, on the host)        [exp_avg.lerp_(gh, 1 - beta1)]
+ *     a = beta2 * v;   b = gh * gh;   c = omb2 * b;   v = a + c      omb2 = 1.0f - beta2                    [exp_avg_sq]
+ *     s = sqrtf(v);   q = s / bc2_sqrt;   den = q + eps      bc2_sqrt = (float)sqrt(1 - (double)beta2^step)
+ *     r = m / den;   u = step_size * r;   p = p - u          step_size = (float)((double)lr / (1 - (double)beta1^step))
+ * The two bias corrections are computed on the host in fp64 from the fp32 fields of the spec and rounded to fp32 once.  Non-finite
+ * gradients get no special case: they propagate as in torch's sequence (a NaN anywhere in grad makes norm, coef and with them every
+ * parameter NaN; a g^2 beyond fp32 makes v infinite and the element's step 0).
+ * DETERMINISM: no atomics, one workgroup, every sum in a fixed order: the same inputs give the same bits.
+ * RMAV_ERR_INVALID (the message names the argument): shared not 0 / 1; grad, params, params[k], exp_avg, exp_avg_sq or spec NULL;
+ * step < 1; lr or eps not finite or < 0; beta1 or beta2 outside [0, 1); max_grad_norm NaN or <= 0; grad_scale not finite or <= 0;
+ * _reserved non-zero. */
+typedef struct rmav_ppo_adam_spec {
+    float lr, beta1, beta2, eps;      /* torch.optim.Adam's; PPO uses 3e-4, 0.9, 0.999, 1e-5 */
+    float max_grad_norm;              /* > 0, or +inf for no clip */
+    float grad_scale;                 /* finite, > 0: 1 / world size after a SUM all-reduce; 1 otherwise */
+    int32_t _reserved[2];             /* 0 */
+} rmav_ppo_adam_spec;
+int rmav_ppo_adam(rmav_handle h, int shared, const float *grad, float *const *params, float *exp_avg, float *exp_avg_sq, int64_t step,
+                  const rmav_ppo_adam_spec *spec, float *stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,7 @@
 // rmav_ppo_abi.hip - the C ABI of include/rmav_ppo.h: policy weights, the policy-in-kernel rollouts (their kernels are launched from
-// rmav_policy_abi.hip), GAE, the observation / return normalisers and the fused learners (rmav_ppo_grad, rmav_ppo_grad_shared).
+// rmav_policy_abi.hip), GAE, the observation / return normalisers, the fused learners (rmav_ppo_grad, rmav_ppo_grad_shared) and what
+// runs around them in a minibatch (rmav_adv_moments, rmav_ppo_adam).
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 
@@ -9,6 +11,7 @@
 #include "rmav_ret_norm.hpp"   // (brings rmav_gae.hpp)
 #include "rmav_learner.hpp"
 #include "rmav_learner_shared.hpp"
+#include "rmav_optim.hpp"
 
 using namespace rmav;
 
@@ -559,6 +562,81 @@ int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_learner_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, h->stream, (const float *)workspace, (int32_t)groups,
                        n_params + kLrnStats, n_params, lay.off[8], a.na, a.batch, a.vf_coef, spec->ent_coef, params[8], grad_out, stats_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+// ---- around the fused learner: the advantage moments it takes and the optimiser step on its gradient, csrc/rmav_optim.hpp ----------------
+int64_t rmav_adv_moments_workspace_bytes(int64_t batch) {
+    if (batch < 1) return -1;
+    return (int64_t)adv_groups(batch) * (int64_t)sizeof(Moment);
+}
+
+int rmav_adv_moments(rmav_handle h, int64_t batch, const int64_t *idx, const float *adv, void *workspace, float *adv_norm_out) {
+    CHECK_HANDLE(h);
+    if (batch < 1) return rmav_fail(RMAV_ERR_INVALID, "batch must be >= 1, got %lld", (long long)batch);
+    if (!adv) return rmav_fail(RMAV_ERR_INVALID, "adv is NULL (required)");
+    if (!workspace) return rmav_fail(RMAV_ERR_INVALID, "workspace is NULL (required)");
+    if (!adv_norm_out) return rmav_fail(RMAV_ERR_INVALID, "adv_norm_out is NULL (required)");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0) return rmav_fail(RMAV_ERR_INVALID, "workspace must be 8-byte aligned");
+    const int groups = adv_groups(batch);   // batch alone decides the geometry
+    hipLaunchKernelGGL(k_adv_moments, dim3((unsigned)groups), dim3(256), 0, h->stream, idx, adv, batch, (Moment *)workspace);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_adv_moments_fold, dim3(1), dim3(256), 0, h->stream, (const Moment *)workspace, (int32_t)groups, batch, adv_norm_out);
+    HIP_TRY(hipGetLastError());
+    return RMAV_OK;
+}
+
+int rmav_ppo_adam(rmav_handle h, int shared, const float *grad, float *const *params, float *exp_avg, float *exp_avg_sq, int64_t step,
+                  const rmav_ppo_adam_spec *spec, float *stats_out) {
+    CHECK_HANDLE(h);
+    if (shared != 0 && shared != 1) return rmav_fail(RMAV_ERR_INVALID, "shared must be 0 or 1, got %d", shared);
+    const struct {
+        const void *p;
+        const char *name;
+    } need[] = {{grad, "grad"}, {params, "params"}, {exp_avg, "exp_avg"}, {exp_avg_sq, "exp_avg_sq"}, {spec, "spec"}};
+    for (const auto &n : need)
+        if (!n.p) return rmav_fail(RMAV_ERR_INVALID, "%s is NULL (required)", n.name);
+    const int n_tensors = shared ? kTrkParams : kLrnParams;
+    for (int k = 0; k < n_tensors; ++k)
+        if (!params[k]) return rmav_fail(RMAV_ERR_INVALID, "params[%d] is NULL (%d device pointers, in the order of %s)", k, n_tensors,
+                                         shared ? "rmav_ppo_grad_shared" : "rmav_ppo_grad");
+    if (step < 1) return rmav_fail(RMAV_ERR_INVALID, "step must be >= 1 (the number of this update), got %lld", (long long)step);
+    const auto finite = [](float x) { return x - x == 0.0f; };
+    if (!finite(spec->lr) || spec->lr < 0.0f) return rmav_fail(RMAV_ERR_INVALID, "lr must be finite and >= 0, got %g", (double)spec->lr);
+    if (!(spec->beta1 >= 0.0f && spec->beta1 < 1.0f)) return rmav_fail(RMAV_ERR_INVALID, "beta1 must be in [0, 1), got %g", (double)spec->beta1);
+    if (!(spec->beta2 >= 0.0f && spec->beta2 < 1.0f)) return rmav_fail(RMAV_ERR_INVALID, "beta2 must be in [0, 1), got %g", (double)spec->beta2);
+    if (!finite(spec->eps) || spec->eps < 0.0f) return rmav_fail(RMAV_ERR_INVALID, "eps must be finite and >= 0, got %g", (double)spec->eps);
+    if (!(spec->max_grad_norm > 0.0f))   // (false for a NaN)
+        return rmav_fail(RMAV_ERR_INVALID, "max_grad_norm must be > 0 (+inf = no clip), got %g", (double)spec->max_grad_norm);
+    if (!finite(spec->grad_scale) || !(spec->grad_scale > 0.0f))
+        return rmav_fail(RMAV_ERR_INVALID, "grad_scale must be finite and > 0, got %g", (double)spec->grad_scale);
+    if (spec->_reserved[0] != 0 || spec->_reserved[1] != 0) return rmav_fail(RMAV_ERR_INVALID, "_reserved must be 0");
+    AdamArgs a;
+    memset(&a, 0, sizeof(a));
+    const int ns = kStateDim[h->kind], na = kActionDim[h->kind];
+    const LearnerLayout lay = learner_layout(ns, na);
+    const TrunkLayout trk = trunk_layout(ns, na);
+    for (int k = 0; k < kAdamMaxTensors; ++k) {
+        a.p[k] = k < n_tensors ? params[k] : nullptr;
+        a.off[k] = k < n_tensors ? (shared ? trk.off[k] : lay.off[k]) : 0x7fffffff;
+    }
+    a.n = shared ? trk.off[kTrkParams] : lay.off[kLrnParams];
+    a.grad = grad;
+    a.m = exp_avg;
+    a.v = exp_avg_sq;
+    a.stats = stats_out;
+    a.grad_scale = spec->grad_scale;
+    a.max_norm = spec->max_grad_norm;
+    a.omb1 = 1.0f - spec->beta1;
+    a.beta2 = spec->beta2;
+    a.omb2 = 1.0f - spec->beta2;
+    // the two bias corrections: fp64 from the fp32 hyperparameters, each scalar rounded to fp32 once
+    const double bc1 = 1.0 - pow((double)spec->beta1, (double)step), bc2 = 1.0 - pow((double)spec->beta2, (double)step);
+    a.step_size = (float)((double)spec->lr / bc1);
+    a.bc2_sqrt = (float)sqrt(bc2);
+    a.eps = spec->eps;
+    hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(kAdamThreads), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
 }

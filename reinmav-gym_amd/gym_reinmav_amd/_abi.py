@@ -103,6 +103,13 @@ class PpoGradSpec(C.Structure):
     _fields_ = [("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("_reserved", C.c_int32)]
 
 
+class PpoAdamSpec(C.Structure):
+    """``rmav_ppo_adam_spec``."""
+
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("max_grad_norm", C.c_float),
+                ("grad_scale", C.c_float), ("_reserved", C.c_int32 * 2)]
+
+
 class EpTotals(C.Structure):
     _fields_ = [("episodes", C.c_uint64), ("return_sum", C.c_double), ("length_sum", C.c_uint64)]
 
@@ -222,6 +229,9 @@ PROTOTYPES = {
     "rmav_ppo_grad_shared_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
     "rmav_ppo_grad_shared": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_void_p),
                                        _vp, C.POINTER(PpoGradSpec), _vp, _fp, _fp]),
+    "rmav_adv_moments_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "rmav_adv_moments": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, _vp, _fp]),
+    "rmav_ppo_adam": (C.c_int, [C.c_void_p, C.c_int, _fp, C.POINTER(C.c_void_p), _fp, _fp, C.c_int64, C.POINTER(PpoAdamSpec), _fp]),
 }
 
 _lib = None

@@ -1227,6 +1227,66 @@ class BatchedQuadrotor:
                                                vp(adv), vp(ret), vp(adv_norm), ptrs, vp(obs_norm), C.byref(spec), vp(ws), vp(grad), vp(stats)))
         return grad, stats
 
+    def adv_moments(self, adv, idx=None, out=None):
+        """The two floats :meth:`ppo_grad` / :meth:`ppo_grad_shared` take as ``adv_norm`` (``rmav_adv_moments``, include/rmav_ppo.h): the
+        mean of ``adv[idx]`` (``idx=None``: of ``adv``) and ``1 / (std + 1e-8)`` with torch's unbiased ``std``, in two launches on the
+        env's stream - per-lane fp64 sums combined in a fixed order, so the same inputs give the same bits and nothing is gathered.  No
+        allocation after the first call of a batch size, no synchronisation.
+
+        ``adv``: contiguous fp32 ``[M]`` on the device; ``idx``: int64 ``[B]`` on the device - THE CALLER guarantees ``0 <= idx < M``.
+        Returns the device tensor of 2 floats, owned by the env and overwritten by the next call (``out=`` to supply it)."""
+        f32 = torch.float32
+        assert adv.dtype == f32 and adv.dim() == 1 and adv.is_contiguous() and adv.is_cuda
+        if idx is not None:
+            assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and idx.is_cuda
+        B = int(adv.numel()) if idx is None else int(idx.numel())
+        cache = self.__dict__.setdefault("_adv_moments_cache", {})
+        if out is None:
+            if "out" not in cache:
+                cache["out"] = torch.empty(2, dtype=f32, device=adv.device)
+            out = cache["out"]
+        assert out.dtype == f32 and out.numel() == 2 and out.is_contiguous() and out.is_cuda
+        need = int(self._lib.rmav_adv_moments_workspace_bytes(max(B, 1)))
+        ws = cache.get("ws")
+        if ws is None or ws.numel() < need:
+            ws = cache["ws"] = torch.empty(need, dtype=torch.uint8, device=adv.device)
+        vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
+        A.check(self._lib.rmav_adv_moments(self._h, B, vp(idx), vp(adv), vp(ws), vp(out)))
+        return out
+
+    def ppo_adam(self, params, grad, exp_avg, exp_avg_sq, step: int, lr: float = 3e-4, beta1: float = 0.9, beta2: float = 0.999,
+                 eps: float = 1e-5, max_grad_norm: float = 0.5, grad_scale: float = 1.0, shared: bool = False, stats=None):
+        """Gradient-norm clip and Adam step in ONE launch (``rmav_ppo_adam``, include/rmav_ppo.h): what ``clip_grad_norm_`` +
+        ``torch.optim.Adam.step()`` (no amsgrad, no weight decay) do, from the flat gradient :meth:`ppo_grad` /
+        :meth:`ppo_grad_shared` leave.  No allocation after the first call, no synchronisation.
+
+        ``params``: the 13 (``shared=True``: 9) contiguous fp32 CUDA tensors in the order of those methods, updated in place;
+        ``grad``, ``exp_avg``, ``exp_avg_sq``: flat fp32 device tensors in that order - ``grad`` is only read (it keeps the unclipped
+        gradient), the two moments are updated in place; ``step >= 1``: the number of this update; ``grad_scale``: ``1 / world`` after a
+        SUM all-reduce of ``grad``; ``max_grad_norm``: ``inf`` = no clip.  Returns ``stats = [norm, coef]``, a device tensor owned
+        by the env and overwritten by the next call (``stats=`` to supply it)."""
+        f32 = torch.float32
+        ps = [p.detach() for p in params]
+        n_t = 9 if shared else 13
+        assert len(ps) == n_t and all(p.is_cuda and p.dtype == f32 and p.is_contiguous() for p in ps), f"{n_t} contiguous fp32 CUDA tensors"
+        count = self._lib.rmav_ppo_grad_shared_param_count if shared else self._lib.rmav_ppo_grad_param_count
+        n_par = int(count(self.kind))
+        assert sum(p.numel() for p in ps) == n_par, "the parameters are not those of an MlpPolicy(hidden=64) of this env and architecture"
+        for x in (grad, exp_avg, exp_avg_sq):
+            assert x.dtype == f32 and x.numel() == n_par and x.is_contiguous() and x.is_cuda
+        if stats is None:
+            cache = self.__dict__.setdefault("_ppo_adam_cache", {})
+            if "stats" not in cache:
+                cache["stats"] = torch.empty(2, dtype=f32, device=grad.device)
+            stats = cache["stats"]
+        assert stats.dtype == f32 and stats.numel() == 2 and stats.is_contiguous() and stats.is_cuda
+        ptrs = (C.c_void_p * n_t)(*[p.data_ptr() for p in ps])
+        spec = A.PpoAdamSpec(float(lr), float(beta1), float(beta2), float(eps), float(max_grad_norm), float(grad_scale), (0, 0))
+        vp = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
+        A.check(self._lib.rmav_ppo_adam(self._h, int(bool(shared)), vp(grad), ptrs, vp(exp_avg), vp(exp_avg_sq), int(step), C.byref(spec),
+                                        vp(stats)))
+        return stats
+
     def normalize_(self, x, mean: float, rstd: float):
         """In place ``x <- (x - mean) * rstd`` on the env's stream (advantage normalisation)."""
         A.check(self._lib.rmav_normalize(self._h, self._ptr(x), x.numel(), float(mean), float(rstd)))

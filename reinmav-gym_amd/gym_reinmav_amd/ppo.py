@@ -22,7 +22,7 @@ MI355X-first choices:
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -655,19 +655,40 @@ def gae(rew, val, done, gamma: float = 0.99, lam: float = 0.95, boot=None):
     return adv, adv + val[:T]
 
 
+class _FusedOptState(NamedTuple):
+    """What PPO(fused_optimizer=True) keeps on the device: Adam's two moments as flat buffers in the fused learner's order, their
+    per-parameter views (installed as the torch optimiser's ``exp_avg`` / ``exp_avg_sq``), and the outputs of the two launches."""
+    exp_avg: torch.Tensor
+    exp_avg_sq: torch.Tensor
+    exp_avg_views: list
+    exp_avg_sq_views: list
+    adv_norm: torch.Tensor   # rmav_adv_moments -> (mean, 1 / (std + 1e-8))
+    stats: torch.Tensor      # rmav_ppo_adam -> (norm, coef)
+
+
 class PPO:
     """Clipped-surrogate PPO (baselines ppo2 defaults: lr 3e-4, clip 0.2, 4 epochs x 4 minibatches,
     vf_coef 0.5, ent_coef 0, max_grad_norm 0.5, gamma 0.99, lambda 0.95)."""
 
     def __init__(self, policy: MlpPolicy, lr: float = 3e-4, clip: float = 0.2, epochs: int = 4, minibatches: int = 4,
                  vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5, gamma: float = 0.99,
-                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None, fused_learner: bool = False):
+                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None, fused_learner: bool = False, fused_optimizer: bool = False):
         """``fused_learner=True``: every minibatch's loss and gradients come from the fused learner instead of torch autograd
         (``value_network="copy"``: ``rmav_ppo_grad``, one launch per net plus a fold, csrc/rmav_learner.hpp; ``"shared"``:
         ``rmav_ppo_grad_shared``, one launch for the trunk and both heads plus the fold, csrc/rmav_learner_shared.hpp); the
         all-reduce, the norm clip and Adam run unchanged on the ``p.grad`` it leaves.  An ``MlpPolicy(hidden=64)`` of either
         architecture with CUDA parameters and a collector that has an env handle; anything else is a ``ValueError``.  The default keeps
         the torch path, bit for bit.
+
+        ``fused_optimizer=True`` (needs ``fused_learner=True``; anything else is a ``ValueError``): the rest of a minibatch runs in HIP
+        too (csrc/rmav_optim.hpp).  The advantage moments come from ``rmav_adv_moments`` instead of a gather and two torch reductions;
+        a data-parallel run all-reduces the flat gradient buffer itself (one ``dist.all_reduce``); and ``clip_grad_norm_`` +
+        ``opt.step()`` become ONE launch, ``rmav_ppo_adam``.  The kernel's state IS ``self.opt``'s: ``exp_avg`` / ``exp_avg_sq`` of
+        every parameter are views of two flat buffers (existing state is copied in first), ``step`` advances on the host, and
+        ``lr`` / ``betas`` / ``eps`` are read from ``self.opt.param_groups[0]`` at every step - ``state_dict()`` /
+        ``load_state_dict()``, learning-rate schedules and switching paths between updates keep working.  ``p.grad`` (views of the
+        flat buffer) holds the UNCLIPPED gradient on this path - on a data-parallel run the ranks' sum - and ``update`` also returns
+        ``grad_norm``, the pre-clip norm of the last minibatch.  The default keeps today's path, bit for bit.
 
         ``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`): baselines' ``VecNormalize(ret=True)`` in front of
         GAE - ``update`` first merges the rollout's discounted returns into it, then computes the advantages from rewards scaled by
@@ -681,6 +702,10 @@ class PPO:
         self.clip, self.epochs, self.minibatches = clip, epochs, minibatches
         self.vf_coef, self.ent_coef, self.max_grad_norm, self.gamma, self.lam = vf_coef, ent_coef, max_grad_norm, gamma, lam
         self.fused_learner = bool(fused_learner)
+        self.fused_optimizer = bool(fused_optimizer)
+        if self.fused_optimizer and not self.fused_learner:
+            raise ValueError("fused_optimizer=True needs fused_learner=True: rmav_ppo_adam steps on the flat gradient the fused learner leaves")
+        self._fused_opt = None   # a _FusedOptState: built by the first fused step
         self._fused = None   # (the 13 or 9 parameters in the ABI order, the flat gradient, its views): built by the first fused update
         if self.fused_learner:
             self._fused_params()
@@ -720,15 +745,79 @@ class PPO:
                 views.append(flat[o:o + p.numel()].view_as(p))
                 o += p.numel()
             self._fused = (ps, flat, views, torch.empty(4, dtype=torch.float32, device=flat.device))
+            if self.fused_optimizer:   # once: this path never rewrites p.grad
+                for p, g in zip(ps, views):
+                    p.grad = g
         ps, flat, views, stats = self._fused
-        std, mean = torch.std_mean(adv[idx])   # the two reductions the launch does not do (a data-parallel run keeps its per-rank moments)
-        adv_norm = torch.stack((mean, 1.0 / (std + 1e-8)))
+        if self.fused_optimizer:   # (a data-parallel run keeps its per-rank moments on either path)
+            adv_norm = env.adv_moments(adv, idx, out=self._fused_buffers().adv_norm)
+        else:
+            std, mean = torch.std_mean(adv[idx])   # the two reductions the launch does not do
+            adv_norm = torch.stack((mean, 1.0 / (std + 1e-8)))
         grad_fn = env.ppo_grad_shared if getattr(self.policy, "shared", False) else env.ppo_grad
         grad_fn(ps, obs, act, logp_old, val_old, adv, ret, adv_norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
                 idx=idx, obs_norm=getattr(self.policy, "obs_norm", None), out=(flat, stats))
-        for p, g in zip(ps, views):
-            p.grad = g
+        if not self.fused_optimizer:
+            for p, g in zip(ps, views):
+                p.grad = g
         return stats
+
+    def _fused_buffers(self):
+        """The fused optimiser's device buffers (a ``_FusedOptState``), allocated once; touches no optimiser state."""
+        if self._fused_opt is None:
+            ps = self._fused[0]
+            dev = ps[0].device
+            m, v = (torch.zeros(self._fused[1].numel(), dtype=torch.float32, device=dev) for _ in range(2))
+            mv, vv, o = [], [], 0
+            for p in ps:
+                mv.append(m[o:o + p.numel()].view_as(p))
+                vv.append(v[o:o + p.numel()].view_as(p))
+                o += p.numel()
+            self._fused_opt = _FusedOptState(m, v, mv, vv, torch.empty(2, dtype=torch.float32, device=dev),
+                                             torch.empty(2, dtype=torch.float32, device=dev))
+        return self._fused_opt
+
+    def _fused_state(self):
+        """Adam's moments as two flat buffers in the fused learner's order, their per-parameter views installed as ``self.opt``'s
+        ``exp_avg`` / ``exp_avg_sq`` (whatever state the optimiser holds - its own steps', a loaded ``state_dict``'s - is copied in
+        first).  Checked once per step by identity, so a ``load_state_dict`` between updates is picked up."""
+        ps, buf = self._fused[0], self._fused_buffers()
+        for p, pm, pv in zip(ps, buf.exp_avg_views, buf.exp_avg_sq_views):
+            st = self.opt.state[p]
+            if st.get("exp_avg") is pm and st.get("exp_avg_sq") is pv:
+                continue
+            with torch.no_grad():
+                if "exp_avg" in st:
+                    pm.copy_(st["exp_avg"])
+                    pv.copy_(st["exp_avg_sq"])
+                else:
+                    pm.zero_()
+                    pv.zero_()
+            if "step" not in st:
+                st["step"] = torch.tensor(0.0)   # as torch.optim.Adam initialises it: a host scalar
+            st["exp_avg"], st["exp_avg_sq"] = pm, pv
+        return buf
+
+    def _fused_opt_step(self, env):
+        """all-reduce (data-parallel), norm clip and Adam of one minibatch: one ``rmav_ppo_adam`` on the flat gradient -> its device
+        ``(norm, coef)``."""
+        ps, flat = self._fused[0], self._fused[1]
+        buf = self._fused_state()
+        group = self.opt.param_groups[0]
+        if len(self.opt.param_groups) != 1 or group.get("amsgrad") or group.get("weight_decay") or group.get("maximize"):
+            raise ValueError("fused_optimizer=True computes torch.optim.Adam with one parameter group and without amsgrad, weight decay or maximize")
+        scale = 1.0
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM)   # the flat buffer itself: no cat, no copy back
+            scale = 1.0 / dist.get_world_size()
+        state = self.opt.state
+        step = int(state[ps[0]]["step"]) + 1
+        for p in ps:
+            state[p]["step"] += 1
+        env.ppo_adam(ps, flat, buf.exp_avg, buf.exp_avg_sq, step, lr=group["lr"], beta1=group["betas"][0], beta2=group["betas"][1], eps=group["eps"],
+                     max_grad_norm=self.max_grad_norm if self.max_grad_norm is not None else math.inf, grad_scale=scale,
+                     shared=bool(getattr(self.policy, "shared", False)), stats=buf.stats)
+        return buf.stats
 
     def _allreduce_grads(self):
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
@@ -790,6 +879,10 @@ class PPO:
                 idx = perm[i * mb:(i + 1) * mb]
                 if fused_env is not None:   # loss, gradients and statistics of the minibatch from rmav_ppo_grad; nothing is gathered but adv
                     st = self._fused_step(fused_env, obs, act, logp_old, val_old, adv, ret, idx)
+                    if self.fused_optimizer:
+                        ost = self._fused_opt_step(fused_env)
+                        stats = {"pg_loss": st[1], "vf_loss": st[2], "ratio_max": st[3], "grad_norm": ost[0]}
+                        continue
                     self._allreduce_grads()
                     torch.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
                     self.opt.step()

@@ -18,7 +18,14 @@ Timings of one process on one GPU; the two paths see the same rollout data in ev
 --value-network shared: the same for an MlpPolicy(value_network="shared") and rmav_ppo_grad_shared (one net launch + the fold).  flop
 is then 6 (nS 64 + 64 64 + 64 (nA + 1)) per sample, grad_us also holds one rmav_ppo_grad call on a copy policy of the same shapes taken
 in the same session (rmav_ppo_grad_copy_same_session), and end_to_end has the one actor of that architecture, f16_shared.  The default,
-copy, prints what it always printed."""
+copy, prints what it always printed.
+
+--fused-optimizer: the A/B is PPO(fused_learner=True) against PPO(fused_learner=True, fused_optimizer=True) instead (both take their
+gradients from the fused learner; "off" is the path without the flag), same alternation, same rollouts:
+  update_ms        as above, per path ("off", "on")
+  call_us          us per rmav_adv_moments call next to torch.std_mean(adv[idx]) + the stack it replaces, and per rmav_ppo_adam call next
+                   to clip_grad_norm_ + Adam.step() on the same gradient (HIP events, median of 20)
+  end_to_end       env-steps/s of collect + update on each path (fp32 matrix-core actor, or f16_shared)"""
 import argparse
 import copy
 import json
@@ -42,14 +49,107 @@ def timed(fn, torch):
     return a.elapsed_time(b), out
 
 
+def finish(res, out):
+    print(json.dumps(res))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def main_optimizer(args):
+    import torch
+
+    import gym_reinmav_amd as g
+    from gym_reinmav_amd.ppo import PPO, FusedPolicyCollector, MlpPolicy
+
+    torch.manual_seed(0)
+    N, T = args.envs, args.steps
+    res = {"shape": {"kind": "quad3d", "envs": N, "steps": T, "epochs": 4, "minibatches": 4, "minibatch": N * T // 4,
+                     "value_network": args.value_network}, "device": torch.cuda.get_device_name(0)}
+    env = g.BatchedQuadrotor("quad3d", N, seed=0)
+    pols = {"off": MlpPolicy(env.nS, env.nA, value_network=args.value_network).cuda()}
+    pols["on"] = copy.deepcopy(pols["off"])
+    ppos = {k: PPO(p, fused_learner=True, fused_optimizer=(k == "on")) for k, p in pols.items()}
+    ro = FusedPolicyCollector(env, pols["off"], T)
+    ms = {"off": [], "on": []}
+    for r in range(args.rounds + 1):   # round 0 warms both paths up
+        ro.collect()
+        for k in ("off", "on") if r % 2 == 0 else ("on", "off"):
+            t, st = timed(lambda: ppos[k].update(ro), torch)
+            if r:
+                ms[k].append(t)
+        ro.roll_over()
+    res["update_ms"] = {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "all": v} for k, v in ms.items()}
+    res["update_gain_ms_median"] = res["update_ms"]["off"]["median"] - res["update_ms"]["on"]["median"]
+
+    def med_us(fn):
+        ts = []
+        for _ in range(23):
+            t, _ = timed(fn, torch)
+            ts.append(t * 1e3)
+        return statistics.median(ts[3:])
+
+    B = N * T
+    adv = ppos["on"].adv.reshape(-1)
+    idx = torch.randperm(B, device="cuda")[:B // 4]
+
+    def torch_moments():
+        std, mean = torch.std_mean(adv[idx])
+        return torch.stack((mean, 1.0 / (std + 1e-8)))
+
+    ppo = ppos["off"]   # its p.grad views hold the last minibatch's gradient; both calls below step on that gradient again and again
+    ps, flat = ppo._fused[0], ppo._fused[1]
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+    shared = args.value_network == "shared"
+
+    def torch_step():
+        torch.nn.utils.clip_grad_norm_(ppo.policy.parameters(), ppo.max_grad_norm)
+        ppo.opt.step()
+
+    keep = flat.clone()
+
+    def torch_step_fresh():   # clip_grad_norm_ rewrites p.grad: restore it (one 40 KB copy, inside the timed span of both arms)
+        flat.copy_(keep)
+        torch_step()
+
+    def fused_step_fresh():
+        flat.copy_(keep)
+        env.ppo_adam(ps, flat, m, v, 7, max_grad_norm=ppo.max_grad_norm, shared=shared)
+
+    res["call_us"] = {"rmav_adv_moments": med_us(lambda: env.adv_moments(adv, idx)), "torch_std_mean_gather_stack": med_us(torch_moments),
+                      "rmav_ppo_adam_with_grad_copy": med_us(fused_step_fresh), "torch_clip_and_adam_with_grad_copy": med_us(torch_step_fresh),
+                      "grad_copy_alone": med_us(lambda: flat.copy_(keep)), "samples": B // 4, "params": flat.numel()}
+    res["end_to_end"] = {}
+    actor = "f16_shared" if shared else "fp32_mfma"
+    for k in ("off", "on"):
+        col = FusedPolicyCollector(env, pols[k], T)
+        rates = []
+        for r in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            col.collect()
+            ppos[k].update(col)
+            col.roll_over()
+            torch.cuda.synchronize()
+            if r:
+                rates.append(N * T / (time.perf_counter() - t0))
+        res["end_to_end"][f"{actor}/{k}"] = {"env_steps_per_s_median": statistics.median(rates), "all": rates}
+    env.close()
+    finish(res, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--value-network", dest="value_network", default="copy", choices=["copy", "shared"])
+    ap.add_argument("--fused-optimizer", dest="fused_optimizer", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.fused_optimizer:
+        return main_optimizer(args)
     import torch
 
     import gym_reinmav_amd as g
@@ -131,12 +231,7 @@ def main():
                     rates.append(N * T / (time.perf_counter() - t0))
             res["end_to_end"][f"{actor}/{k}"] = {"env_steps_per_s_median": statistics.median(rates), "all": rates}
     env.close()
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(json.dumps(res, indent=1) + "\n")
+    finish(res, args.out)
 
 
 if __name__ == "__main__":
