@@ -22,6 +22,9 @@
 // workgroup t mod groups with groups = min(tiles, kLrnMaxGroups); a thread adds its tiles in order; per-workgroup partials go to the
 // caller's workspace and k_learner_fold adds them in workgroup order.  Geometry and order depend on (kind, batch) alone.
 // Tail lanes of the last tile read a valid column (the last sample's) and get delta = 0, so they add exact zeros.
+//
+// The statements learner_net shares with k_trunk_grad (rmav_learner_shared.hpp) are text fragments both include, rmav_learner_stage.inc,
+// _fwd.inc, _pg.inc, _vf.inc and _bwd.inc: as inline functions they changed the ISA of both.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -36,17 +39,7 @@ constexpr int kLrnMaxGroups = 512;   // two workgroups per CU
 constexpr int kLrnParams = 13;       // pi: W1 b1 W2 b2 W3 b3 | vf: the same six | logstd
 constexpr int kLrnStats = 4;         // a workgroup's partial record behind its gradient: sum pg, sum vf, max ratio, pad
 
-// The flat gradient (the ABI order of include/rmav_ppo.h): offsets of the 13 tensors, and the total
-struct LearnerLayout {
-    int32_t off[kLrnParams + 1];
-};
-inline LearnerLayout learner_layout(int ns, int na) {
-    LearnerLayout L;
-    const int sz[kLrnParams] = {64 * ns, 64, 64 * 64, 64, na * 64, na, 64 * ns, 64, 64 * 64, 64, 64, 1, na};
-    L.off[0] = 0;
-    for (int k = 0; k < kLrnParams; ++k) L.off[k + 1] = L.off[k] + sz[k];
-    return L;
-}
+// (the flat gradient's layout, the ABI order of include/rmav_ppo.h, is host code: flat_layout in rmav_ppo_abi.hip)
 inline int learner_groups(int64_t batch) {
     const int64_t tiles = (batch + kLrnTile - 1) / kLrnTile;
     return (int)(tiles < kLrnMaxGroups ? tiles : kLrnMaxGroups);
@@ -109,16 +102,7 @@ __device__ __forceinline__ void learner_net(const LearnerArgs &A, LearnerLds &S,
     const int t = threadIdx.x, rb = t >> 4, cb = t & 15;
     const int ns = A.ns, n_out = VALUE ? 1 : A.na;
     // ---- stage the net's weights ------------------------------------------------------------------------------------------------------
-    for (int e = t; e < 64 * 64; e += kLrnThreads) {
-        const int j = e >> 6, i = e & 63;   // W2[j][i]
-        const float w = p[2][e];
-        S.w2t[i * 64 + lrn_pos(j)] = w;
-        S.w2n[j * 64 + lrn_pos(i)] = w;
-    }
-    for (int e = t; e < 16 * 64; e += kLrnThreads) {
-        const int i = e >> 6, j = e & 63;   // W1[j][i]
-        S.w1t[i * 64 + lrn_pos(j)] = i < ns ? p[0][j * ns + i] : 0.0f;
-    }
+#include "rmav_learner_stage.inc"
     {
         const int o = t >> 6, k = t & 63;
         S.w3[t] = o < n_out ? p[4][o * 64 + k] : 0.0f;
@@ -135,59 +119,14 @@ __device__ __forceinline__ void learner_net(const LearnerArgs &A, LearnerLds &S,
     __syncthreads();
 
     float g2[4][4] = {}, g1[4] = {}, g3 = 0.0f, gb2[4] = {}, gb1[4] = {};   // this thread's share of dW2, dW1, dW3, db2, db1
-    float gb3[4] = {}, gls[4] = {}, sum_loss = 0.0f, max_ratio = 0.0f;       // per-sample lane (wave 0): db3, dlogstd, loss sum
+    // per-sample lane (wave 0): db3, dlogstd, the loss sums (one of the two per net: two names, since the policy and the value term
+    // are shared text, rmav_learner_pg.inc and rmav_learner_vf.inc)
+    float gb3[4] = {}, gls[4] = {}, sum_pg = 0.0f, sum_vf = 0.0f, max_ratio = 0.0f;
     const float inv_b = 1.0f / (float)A.batch;
     const int64_t tiles = ((int64_t)A.batch + kLrnTile - 1) / kLrnTile;
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        // ---- the observation tile: x[c][s], rows >= ns zero; a tail lane reads the last sample's column ------------------------------
-        const int s = t & 63;
-        const int64_t j = tile * kLrnTile + s;
-        const bool live = j < A.batch;
-        const int64_t jc = live ? j : (int64_t)A.batch - 1;
-        const int64_t col = A.idx ? A.idx[jc] : jc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = (t >> 6) + 4 * q;
-            float x = 0.0f;
-            if (c < ns) {
-                x = A.obs[(int64_t)c * A.obs_pitch + col];
-                if (A.norm_tab) {   // THE arithmetic of include/rmav_ppo.h, uncontracted
-                    const float lim = A.norm_tab[32];
-                    x = (x - A.norm_tab[c]) * A.norm_tab[16 + c];
-                    x = fminf(fmaxf(x, -lim), lim);
-                }
-            }
-            S.x[c * kLrnPitch + s] = x;
-        }
-        __syncthreads();
-        // ---- forward ------------------------------------------------------------------------------------------------------------------
-        {
-            float acc[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[r][q] = S.b1[rb + 16 * r];
-            lrn_gemm(S.w1t, S.x, ns, rb, cb, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<float4 *>(&S.h1[(rb + 16 * r) * kLrnPitch + 4 * cb]) =
-                    make_float4(tanhf(acc[r][0]), tanhf(acc[r][1]), tanhf(acc[r][2]), tanhf(acc[r][3]));
-        }
-        __syncthreads();
-        {
-            float acc[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[r][q] = S.b2[rb + 16 * r];
-            lrn_gemm(S.w2t, S.h1, 64, rb, cb, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<float4 *>(&S.h2[(rb + 16 * r) * kLrnPitch + 4 * cb]) =
-                    make_float4(tanhf(acc[r][0]), tanhf(acc[r][1]), tanhf(acc[r][2]), tanhf(acc[r][3]));
-        }
-        __syncthreads();
+#include "rmav_learner_fwd.inc"
         {   // output layer: thread (o, s), wavefront-uniform o
             const int o = t >> 6;
             if (o < n_out) {
@@ -201,55 +140,12 @@ __device__ __forceinline__ void learner_net(const LearnerArgs &A, LearnerLds &S,
         // ---- the loss of sample s and the delta of the output layer (wave 0) ----------------------------------------------------------
         if (t < 64) {
             if constexpr (!VALUE) {
-                float ss = 0.0f, sum_ls = 0.0f, z[4], inv_std[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    z[c] = inv_std[c] = 0.0f;
-                    if (c < A.na) {
-                        inv_std[c] = expf(-S.logstd[c]);
-                        z[c] = (A.act[(int64_t)c * A.act_pitch + col] - S.out[c * kLrnTile + s]) * inv_std[c];
-                        ss = fmaf(z[c], z[c], ss);
-                        sum_ls += S.logstd[c];
-                    }
-                }
-                const float logp = -0.5f * ss - sum_ls - 0.5f * (float)A.na * 1.8378770664093453f;   // log(2 pi)
-                const float ratio = expf(logp - A.logp_old[col]);
-                const float a = (A.adv[col] - A.adv_norm[0]) * A.adv_norm[1];
-                const float lo = 1.0f - A.clip, hi = 1.0f + A.clip;
-                const float t1 = -a * ratio, t2 = -a * fminf(fmaxf(ratio, lo), hi);
-                const bool inside = ratio >= lo && ratio <= hi;
-                // autograd: max() hands the gradient to the larger argument and halves it on a tie; clamp's is 1 on the closed interval
-                float g_ratio = 0.0f;
-                if (t1 > t2 || (t1 == t2 && inside)) g_ratio = -a;
-                else if (t1 == t2) g_ratio = -0.5f * a;
-                const float gl = live ? g_ratio * ratio * inv_b : 0.0f;   // d loss / d logp of this sample
-                if (live) {
-                    sum_loss += fmaxf(t1, t2);
-                    max_ratio = fmaxf(max_ratio, ratio);
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (c < A.na) {
-                        const float d = gl * z[c] * inv_std[c];   // d logp / d mean_c = z_c / std_c
-                        S.d3[c * kLrnTile + s] = d;
-                        gb3[c] += d;
-                        gls[c] = fmaf(gl, fmaf(z[c], z[c], -1.0f), gls[c]);   // d logp / d logstd_c = z_c^2 - 1
-                    }
+                const int na = A.na;
+#include "rmav_learner_pg.inc"
             } else {
-                const float v = S.out[s], vo = A.val_old[col], rt = A.ret[col];
-                const float dv = v - vo;
-                const float vc = vo + fminf(fmaxf(dv, -A.clip), A.clip);
-                const float u1 = v - rt, u2 = vc - rt;
-                const float e1 = u1 * u1, e2 = u2 * u2;
-                const bool inside = dv >= -A.clip && dv <= A.clip;
-                float gv;   // d max(e1, e2) / d v
-                if (e1 > e2) gv = 2.0f * u1;
-                else if (e1 < e2) gv = inside ? 2.0f * u2 : 0.0f;
-                else gv = u1 + (inside ? u2 : 0.0f);
-                const float d = live ? A.vf_coef * 0.5f * gv * inv_b : 0.0f;
-                if (live) sum_loss += fmaxf(e1, e2);
-                S.d3[s] = d;
-                gb3[0] += d;
+                constexpr int vrow = 0;   // the value net's one output row, and its bias gradient
+                float &gbv = gb3[0];
+#include "rmav_learner_vf.inc"
             }
         }
         __syncthreads();
@@ -289,52 +185,7 @@ __device__ __forceinline__ void learner_net(const LearnerArgs &A, LearnerLds &S,
             gb2[r] += (dl.x + dl.y) + (dl.z + dl.w);
         }
         __syncthreads();
-        // ---- dW2 += d2 . h1^T: thread (rows rb + 16 r of d2) x (rows cb + 16 c of h1), K = the tile's samples -------------------------
-        for (int s4 = 0; s4 < kLrnTile; s4 += 4) {
-            float4 d[4], h[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) d[r] = lds4(&S.h2[(rb + 16 * r) * kLrnPitch + s4]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) h[c] = lds4(&S.h1[(cb + 16 * c) * kLrnPitch + s4]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    g2[r][c] = fmaf(d[r].x, h[c].x, g2[r][c]);
-                    g2[r][c] = fmaf(d[r].y, h[c].y, g2[r][c]);
-                    g2[r][c] = fmaf(d[r].z, h[c].z, g2[r][c]);
-                    g2[r][c] = fmaf(d[r].w, h[c].w, g2[r][c]);
-                }
-        }
-        __syncthreads();
-        // ---- delta 1 = (W2^T d2) * (1 - h1^2), in place -------------------------------------------------------------------------------
-        {
-            float acc[4][4] = {};
-            lrn_gemm(S.w2n, S.h2, 64, rb, cb, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float4 *hp = reinterpret_cast<float4 *>(&S.h1[(rb + 16 * r) * kLrnPitch + 4 * cb]);
-                const float4 h = *hp;
-                const float4 dl = make_float4(acc[r][0] * fmaf(-h.x, h.x, 1.0f), acc[r][1] * fmaf(-h.y, h.y, 1.0f),
-                                              acc[r][2] * fmaf(-h.z, h.z, 1.0f), acc[r][3] * fmaf(-h.w, h.w, 1.0f));
-                *hp = dl;
-                gb1[r] += (dl.x + dl.y) + (dl.z + dl.w);
-            }
-        }
-        __syncthreads();
-        // ---- dW1 += d1 . x^T: thread (rows rb + 16 r of d1) x (row cb of x; rows >= ns are zero) --------------------------------------
-        for (int s4 = 0; s4 < kLrnTile; s4 += 4) {
-            const float4 x = lds4(&S.x[cb * kLrnPitch + s4]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float4 d = lds4(&S.h1[(rb + 16 * r) * kLrnPitch + s4]);
-                g1[r] = fmaf(d.x, x.x, g1[r]);
-                g1[r] = fmaf(d.y, x.y, g1[r]);
-                g1[r] = fmaf(d.z, x.z, g1[r]);
-                g1[r] = fmaf(d.w, x.w, g1[r]);
-            }
-        }
-        __syncthreads();   // (the next tile overwrites x and h1)
+#include "rmav_learner_bwd.inc"
     }
 
     // ---- this workgroup's partial gradient of the net ---------------------------------------------------------------------------------
@@ -358,7 +209,7 @@ __device__ __forceinline__ void learner_net(const LearnerArgs &A, LearnerLds &S,
             red[2048 + c * 64 + t] = gb3[c];
             red[2048 + (4 + c) * 64 + t] = gls[c];
         }
-        red[2048 + 8 * 64 + t] = sum_loss;
+        red[2048 + 8 * 64 + t] = VALUE ? sum_vf : sum_pg;
         red[2048 + 9 * 64 + t] = max_ratio;
     }
     __syncthreads();

@@ -16,10 +16,7 @@
 // sum pg, sum vf, max ratio, pad) and k_learner_fold, unchanged, adds the records: it is generic in n_params / off_logstd, and logstd
 // stays last.  Every product runs on the vector ALU from LDS; no matrix instruction, no atomics.
 //
-// DETERMINISM: no atomics.  Sample j sits in lane j mod 64 of tile j / 64 whether it came through idx or not; tile t belongs to
-// workgroup t mod groups with groups = min(tiles, kLrnMaxGroups); a thread adds its tiles in order; per-workgroup partials go to the
-// caller's workspace and k_learner_fold adds them in workgroup order.  Geometry and order depend on (kind, batch) alone.
-// Tail lanes of the last tile read a valid column (the last sample's) and get delta = 0, so they add exact zeros.
+// DETERMINISM: the paragraph of rmav_learner.hpp holds word for word (same tile walk, same partial records, same fold).
 //
 // Included by rmav_ppo_abi.hip alone, BEHIND rmav_learner.hpp: lrn_gemm, lrn_pos, lds4, learner_groups, k_learner_fold and the
 // constants are that header's (it has one includer, which tests/test_learner_build.py counts, so this file does not include it).
@@ -33,19 +30,8 @@ namespace rmav {
 constexpr int kTrkParams = 9;   // pi.W1 pi.b1 pi.W2 pi.b2 pi.W3 pi.b3 | vf.W vf.b | logstd
 constexpr int kTrkRows = 5;     // output rows held in LDS: at most 4 means + the value
 
-// The flat gradient (the ABI order of include/rmav_ppo.h): offsets of the 9 tensors, and the total.  The kernel derives its own copy
-// from (ns, na) when it writes its record: nine offsets as kernel arguments would sit in scalar registers across the tile loop.
-struct TrunkLayout {
-    int32_t off[kTrkParams + 1];
-};
-inline TrunkLayout trunk_layout(int ns, int na) {
-    TrunkLayout L;
-    const int sz[kTrkParams] = {64 * ns, 64, 64 * 64, 64, na * 64, na, 64, 1, na};
-    L.off[0] = 0;
-    for (int k = 0; k < kTrkParams; ++k) L.off[k + 1] = L.off[k] + sz[k];
-    return L;
-}
-
+// The kernel derives the offsets of the flat gradient (flat_layout in rmav_ppo_abi.hip) from (ns, na) when it writes its record: nine
+// offsets as kernel arguments would sit in scalar registers across the tile loop.
 struct TrunkArgs {
     const int64_t *idx;       // [batch] or null
     const float *obs, *act;   // [ns][obs_pitch], [na][act_pitch]
@@ -79,17 +65,9 @@ __global__ __launch_bounds__(kLrnThreads) void k_trunk_grad(const TrunkArgs A) {
     __shared__ TrunkLds S;
     const int t = threadIdx.x, rb = t >> 4, cb = t & 15;
     const int ns = A.ns, na = A.na, n_out = na + 1;
+    const float *const *p = A.p;
     // ---- stage the trunk and both heads -------------------------------------------------------------------------------------------------
-    for (int e = t; e < 64 * 64; e += kLrnThreads) {
-        const int j = e >> 6, i = e & 63;   // W2[j][i]
-        const float w = A.p[2][e];
-        S.w2t[i * 64 + lrn_pos(j)] = w;
-        S.w2n[j * 64 + lrn_pos(i)] = w;
-    }
-    for (int e = t; e < 16 * 64; e += kLrnThreads) {
-        const int i = e >> 6, j = e & 63;   // W1[j][i]
-        S.w1t[i * 64 + lrn_pos(j)] = i < ns ? A.p[0][j * ns + i] : 0.0f;
-    }
+#include "rmav_learner_stage.inc"
     for (int e = t; e < kTrkRows * 64; e += kLrnThreads) {
         const int o = e >> 6, k = e & 63;
         S.w3[e] = o < na ? A.p[4][o * 64 + k] : (o == na ? A.p[6][k] : 0.0f);
@@ -112,54 +90,7 @@ __global__ __launch_bounds__(kLrnThreads) void k_trunk_grad(const TrunkArgs A) {
     const int64_t tiles = ((int64_t)A.batch + kLrnTile - 1) / kLrnTile;
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        // ---- the observation tile: x[c][s], rows >= ns zero; a tail lane reads the last sample's column ------------------------------
-        const int s = t & 63;
-        const int64_t j = tile * kLrnTile + s;
-        const bool live = j < A.batch;
-        const int64_t jc = live ? j : (int64_t)A.batch - 1;
-        const int64_t col = A.idx ? A.idx[jc] : jc;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = (t >> 6) + 4 * q;
-            float x = 0.0f;
-            if (c < ns) {
-                x = A.obs[(int64_t)c * A.obs_pitch + col];
-                if (A.norm_tab) {   // THE arithmetic of include/rmav_ppo.h, uncontracted
-                    const float lim = A.norm_tab[32];
-                    x = (x - A.norm_tab[c]) * A.norm_tab[16 + c];
-                    x = fminf(fmaxf(x, -lim), lim);
-                }
-            }
-            S.x[c * kLrnPitch + s] = x;
-        }
-        __syncthreads();
-        // ---- forward, once ------------------------------------------------------------------------------------------------------------
-        {
-            float acc[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[r][q] = S.b1[rb + 16 * r];
-            lrn_gemm(S.w1t, S.x, ns, rb, cb, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<float4 *>(&S.h1[(rb + 16 * r) * kLrnPitch + 4 * cb]) =
-                    make_float4(tanhf(acc[r][0]), tanhf(acc[r][1]), tanhf(acc[r][2]), tanhf(acc[r][3]));
-        }
-        __syncthreads();
-        {
-            float acc[4][4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[r][q] = S.b2[rb + 16 * r];
-            lrn_gemm(S.w2t, S.h1, 64, rb, cb, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<float4 *>(&S.h2[(rb + 16 * r) * kLrnPitch + 4 * cb]) =
-                    make_float4(tanhf(acc[r][0]), tanhf(acc[r][1]), tanhf(acc[r][2]), tanhf(acc[r][3]));
-        }
-        __syncthreads();
+#include "rmav_learner_fwd.inc"
         // ---- the output layer: thread (o, s), wavefront-uniform o; the fifth row is wave 0's second pass -----------------------------
         for (int o = t >> 6; o < n_out; o += 4) {
             float acc = S.b3[o];
@@ -171,56 +102,11 @@ __global__ __launch_bounds__(kLrnThreads) void k_trunk_grad(const TrunkArgs A) {
         // ---- both loss terms of sample s and the deltas of both heads (wave 0) -------------------------------------------------------
         if (t < 64) {
             {   // the policy term: learner_net<false>
-                float ss = 0.0f, sum_ls = 0.0f, z[4], inv_std[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    z[c] = inv_std[c] = 0.0f;
-                    if (c < na) {
-                        inv_std[c] = expf(-S.logstd[c]);
-                        z[c] = (A.act[(int64_t)c * A.act_pitch + col] - S.out[c * kLrnTile + s]) * inv_std[c];
-                        ss = fmaf(z[c], z[c], ss);
-                        sum_ls += S.logstd[c];
-                    }
-                }
-                const float logp = -0.5f * ss - sum_ls - 0.5f * (float)na * 1.8378770664093453f;   // log(2 pi)
-                const float ratio = expf(logp - A.logp_old[col]);
-                const float a = (A.adv[col] - A.adv_norm[0]) * A.adv_norm[1];
-                const float lo = 1.0f - A.clip, hi = 1.0f + A.clip;
-                const float t1 = -a * ratio, t2 = -a * fminf(fmaxf(ratio, lo), hi);
-                const bool inside = ratio >= lo && ratio <= hi;
-                // autograd: max() hands the gradient to the larger argument and halves it on a tie; clamp's is 1 on the closed interval
-                float g_ratio = 0.0f;
-                if (t1 > t2 || (t1 == t2 && inside)) g_ratio = -a;
-                else if (t1 == t2) g_ratio = -0.5f * a;
-                const float gl = live ? g_ratio * ratio * inv_b : 0.0f;   // d loss / d logp of this sample
-                if (live) {
-                    sum_pg += fmaxf(t1, t2);
-                    max_ratio = fmaxf(max_ratio, ratio);
-                }
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (c < na) {
-                        const float d = gl * z[c] * inv_std[c];   // d logp / d mean_c = z_c / std_c
-                        S.d3[c * kLrnTile + s] = d;
-                        gb3[c] += d;
-                        gls[c] = fmaf(gl, fmaf(z[c], z[c], -1.0f), gls[c]);   // d logp / d logstd_c = z_c^2 - 1
-                    }
+#include "rmav_learner_pg.inc"
             }
             {   // the value term: learner_net<true>, on row na
-                const float v = S.out[na * kLrnTile + s], vo = A.val_old[col], rt = A.ret[col];
-                const float dv = v - vo;
-                const float vc = vo + fminf(fmaxf(dv, -A.clip), A.clip);
-                const float u1 = v - rt, u2 = vc - rt;
-                const float e1 = u1 * u1, e2 = u2 * u2;
-                const bool inside = dv >= -A.clip && dv <= A.clip;
-                float gv;   // d max(e1, e2) / d v
-                if (e1 > e2) gv = 2.0f * u1;
-                else if (e1 < e2) gv = inside ? 2.0f * u2 : 0.0f;
-                else gv = u1 + (inside ? u2 : 0.0f);
-                const float d = live ? A.vf_coef * 0.5f * gv * inv_b : 0.0f;
-                if (live) sum_vf += fmaxf(e1, e2);
-                S.d3[na * kLrnTile + s] = d;
-                gbv += d;
+                const int vrow = na;
+#include "rmav_learner_vf.inc"
             }
         }
         __syncthreads();
@@ -269,52 +155,7 @@ __global__ __launch_bounds__(kLrnThreads) void k_trunk_grad(const TrunkArgs A) {
             gb2[r] += (dl.x + dl.y) + (dl.z + dl.w);
         }
         __syncthreads();
-        // ---- dW2 += d2 . h1^T: thread (rows rb + 16 r of d2) x (rows cb + 16 c of h1), K = the tile's samples -------------------------
-        for (int s4 = 0; s4 < kLrnTile; s4 += 4) {
-            float4 d[4], h[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) d[r] = lds4(&S.h2[(rb + 16 * r) * kLrnPitch + s4]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) h[c] = lds4(&S.h1[(cb + 16 * c) * kLrnPitch + s4]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    g2[r][c] = fmaf(d[r].x, h[c].x, g2[r][c]);
-                    g2[r][c] = fmaf(d[r].y, h[c].y, g2[r][c]);
-                    g2[r][c] = fmaf(d[r].z, h[c].z, g2[r][c]);
-                    g2[r][c] = fmaf(d[r].w, h[c].w, g2[r][c]);
-                }
-        }
-        __syncthreads();
-        // ---- delta 1 = (W2^T d2) * (1 - h1^2), in place -------------------------------------------------------------------------------
-        {
-            float acc[4][4] = {};
-            lrn_gemm(S.w2n, S.h2, 64, rb, cb, acc);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float4 *hp = reinterpret_cast<float4 *>(&S.h1[(rb + 16 * r) * kLrnPitch + 4 * cb]);
-                const float4 h = *hp;
-                const float4 dl = make_float4(acc[r][0] * fmaf(-h.x, h.x, 1.0f), acc[r][1] * fmaf(-h.y, h.y, 1.0f),
-                                              acc[r][2] * fmaf(-h.z, h.z, 1.0f), acc[r][3] * fmaf(-h.w, h.w, 1.0f));
-                *hp = dl;
-                gb1[r] += (dl.x + dl.y) + (dl.z + dl.w);
-            }
-        }
-        __syncthreads();
-        // ---- dW1 += d1 . x^T: thread (rows rb + 16 r of d1) x (row cb of x; rows >= ns are zero) --------------------------------------
-        for (int s4 = 0; s4 < kLrnTile; s4 += 4) {
-            const float4 x = lds4(&S.x[cb * kLrnPitch + s4]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float4 d = lds4(&S.h1[(rb + 16 * r) * kLrnPitch + s4]);
-                g1[r] = fmaf(d.x, x.x, g1[r]);
-                g1[r] = fmaf(d.y, x.y, g1[r]);
-                g1[r] = fmaf(d.z, x.z, g1[r]);
-                g1[r] = fmaf(d.w, x.w, g1[r]);
-            }
-        }
-        __syncthreads();   // (the next tile overwrites x and h1)
+#include "rmav_learner_bwd.inc"
     }
 
     // ---- this workgroup's partial record: offsets of the flat layout from (ns, na) ------------------------------------------------------

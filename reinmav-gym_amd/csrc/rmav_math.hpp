@@ -38,6 +38,8 @@ template <> struct Dims<QUAD3D>    { static constexpr int NS = 10, NA = 4; using
 template <> struct Dims<QUAD3D_SL> { static constexpr int NS = 16, NA = 4; using real = double; };
 template <> struct Dims<REINMAV>   { static constexpr int NS = 13, NA = 4; using real = double; };
 
+constexpr float kLog2Pi = 1.8378770664093453f;   // log(2 pi): the Gaussian log-density of the rollouts' actors and of the learners
+
 // ---- scalar helpers -----------------------------------------------------------------------------
 RMAV_HD float  rfma(float a, float b, float c)    { return __builtin_fmaf(a, b, c); }
 RMAV_HD double rfma(double a, double b, double c) { return __builtin_fma(a, b, c); }

@@ -11,7 +11,7 @@
         float sl = 0.0f;
 #pragma unroll
         for (int c = 0; c < NA; ++c) sl += logstd[c];
-        const float logp0 = -sl - 0.5f * (float)NA * 1.8378770664093453f;   // - sum(logstd) - NA/2 ln(2 pi)
+        const float logp0 = -sl - 0.5f * (float)NA * kLog2Pi;   // - sum(logstd) - NA/2 ln(2 pi)
         float *logp_out = a.logp_out, *val_out = a.val_out;
         auto draw = [&](int32_t k) {   // z of step k -> its tile half; log-probability of the action it will make
             float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};

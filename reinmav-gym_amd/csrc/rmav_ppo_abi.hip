@@ -426,93 +426,33 @@ int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_
                     sums_out);
 }
 
-// ---- the fused learner: loss and gradient of one PPO minibatch, csrc/rmav_learner.hpp ----------------------------------------------------
-int64_t rmav_ppo_grad_param_count(int kind) {
+// ---- the fused learners: loss and gradient of one PPO minibatch, csrc/rmav_learner.hpp (value_network="copy": one launch per net) and
+// csrc/rmav_learner_shared.hpp ("shared": one launch), then the one fold ----------------------------------------------------------------
+// The flat gradient of either learner (the ABI order of include/rmav_ppo.h): n tensors, their offsets, the total in off[n]; logstd is last
+struct FlatLayout {
+    int32_t n;
+    int32_t off[kLrnParams + 1];
+};
+static FlatLayout flat_layout(bool shared, int ns, int na) {
+    const int copy[kLrnParams] = {64 * ns, 64, 64 * 64, 64, na * 64, na, 64 * ns, 64, 64 * 64, 64, 64, 1, na};
+    const int trunk[kTrkParams] = {64 * ns, 64, 64 * 64, 64, na * 64, na, 64, 1, na};
+    FlatLayout L;
+    L.n = shared ? kTrkParams : kLrnParams;
+    L.off[0] = 0;
+    for (int k = 0; k < L.n; ++k) L.off[k + 1] = L.off[k] + (shared ? trunk : copy)[k];
+    return L;
+}
+static int64_t grad_param_count(bool shared, int kind) {
     if (kind < 0 || kind >= kNumKinds) return -1;
-    return learner_layout(kStateDim[kind], kActionDim[kind]).off[kLrnParams];
+    const FlatLayout lay = flat_layout(shared, kStateDim[kind], kActionDim[kind]);
+    return lay.off[lay.n];
 }
-
-int64_t rmav_ppo_grad_workspace_bytes(int kind, int64_t batch) {
+static int64_t grad_workspace_bytes(bool shared, int kind, int64_t batch) {
     if (kind < 0 || kind >= kNumKinds || batch < 1) return -1;
-    return (int64_t)learner_groups(batch) * (rmav_ppo_grad_param_count(kind) + kLrnStats) * (int64_t)sizeof(float);
+    return (int64_t)learner_groups(batch) * (grad_param_count(shared, kind) + kLrnStats) * (int64_t)sizeof(float);
 }
 
-int rmav_ppo_grad(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act, int64_t act_pitch,
-                  const float *logp_old, const float *val_old, const float *adv, const float *ret, const float *adv_norm,
-                  const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec, void *workspace, float *grad_out,
-                  float *stats_out) {
-    CHECK_HANDLE(h);
-    if (batch < 1 || batch > (int64_t)0x7fffffff) return rmav_fail(RMAV_ERR_INVALID, "batch must be in [1, 2^31), got %lld", (long long)batch);
-    const struct {
-        const void *p;
-        const char *name;
-    } need[] = {{obs, "obs"}, {act, "act"}, {logp_old, "logp_old"}, {val_old, "val_old"}, {adv, "adv"}, {ret, "ret"}, {adv_norm, "adv_norm"},
-                {params, "params"}, {spec, "spec"}, {workspace, "workspace"}, {grad_out, "grad_out"}, {stats_out, "stats_out"}};
-    for (const auto &n : need)
-        if (!n.p) return rmav_fail(RMAV_ERR_INVALID, "%s is NULL (required)", n.name);
-    for (int k = 0; k < kLrnParams; ++k)
-        if (!params[k]) return rmav_fail(RMAV_ERR_INVALID, "params[%d] is NULL (13 device pointers: pi W1 b1 W2 b2 W3 b3, vf the same, logstd)", k);
-    const int64_t min_pitch = idx ? 1 : batch;
-    if (obs_pitch < min_pitch) return rmav_fail(RMAV_ERR_INVALID, "obs_pitch must be >= %lld, got %lld", (long long)min_pitch, (long long)obs_pitch);
-    if (act_pitch < min_pitch) return rmav_fail(RMAV_ERR_INVALID, "act_pitch must be >= %lld, got %lld", (long long)min_pitch, (long long)act_pitch);
-    if (spec->clip - spec->clip != 0.0f || spec->clip < 0.0f) return rmav_fail(RMAV_ERR_INVALID, "clip must be finite and >= 0, got %g", (double)spec->clip);
-    if (spec->vf_coef - spec->vf_coef != 0.0f) return rmav_fail(RMAV_ERR_INVALID, "vf_coef must be finite, got %g", (double)spec->vf_coef);
-    if (spec->ent_coef - spec->ent_coef != 0.0f) return rmav_fail(RMAV_ERR_INVALID, "ent_coef must be finite, got %g", (double)spec->ent_coef);
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "workspace must be 16-byte aligned");
-    if (obs_stats && (reinterpret_cast<uintptr_t>(obs_stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "obs_stats must be 16-byte aligned");
-    LearnerArgs a;
-    memset(&a, 0, sizeof(a));
-    a.idx = idx;
-    a.obs = obs;
-    a.act = act;
-    a.obs_pitch = obs_pitch;
-    a.act_pitch = act_pitch;
-    a.logp_old = logp_old;
-    a.val_old = val_old;
-    a.adv = adv;
-    a.ret = ret;
-    a.adv_norm = adv_norm;
-    a.norm_tab = obs_stats ? ((const ObsNormStats *)obs_stats)->mean_f : nullptr;
-    a.partial = (float *)workspace;
-    a.clip = spec->clip;
-    a.vf_coef = spec->vf_coef;
-    a.batch = (int32_t)batch;
-    a.ns = kStateDim[h->kind];
-    a.na = kActionDim[h->kind];
-    const LearnerLayout lay = learner_layout(a.ns, a.na);
-    const int32_t n_params = lay.off[kLrnParams];
-    a.pstride = n_params + kLrnStats;
-    a.logstd = params[12];
-    a.off_logstd = lay.off[12];
-    a.off_stats = n_params;
-    const int groups = learner_groups(batch);   // (kind, batch) alone decide the geometry
-    for (int net = 0; net < 2; ++net) {
-        for (int k = 0; k < 6; ++k) {
-            a.p[k] = params[6 * net + k];
-            a.goff[k] = lay.off[6 * net + k];
-        }
-        if (net == 0) hipLaunchKernelGGL(k_learner_grad<false>, dim3((unsigned)groups), dim3(kLrnThreads), 0, h->stream, a);
-        else hipLaunchKernelGGL(k_learner_grad<true>, dim3((unsigned)groups), dim3(kLrnThreads), 0, h->stream, a);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_learner_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, h->stream, (const float *)workspace, (int32_t)groups,
-                       a.pstride, n_params, lay.off[12], a.na, a.batch, a.vf_coef, spec->ent_coef, params[12], grad_out, stats_out);
-    HIP_TRY(hipGetLastError());
-    return RMAV_OK;
-}
-
-// ---- the fused learner of the shared-trunk policy: one net launch and the same fold, csrc/rmav_learner_shared.hpp ----------------------
-int64_t rmav_ppo_grad_shared_param_count(int kind) {
-    if (kind < 0 || kind >= kNumKinds) return -1;
-    return trunk_layout(kStateDim[kind], kActionDim[kind]).off[kTrkParams];
-}
-
-int64_t rmav_ppo_grad_shared_workspace_bytes(int kind, int64_t batch) {
-    if (kind < 0 || kind >= kNumKinds || batch < 1) return -1;
-    return (int64_t)learner_groups(batch) * (rmav_ppo_grad_shared_param_count(kind) + kLrnStats) * (int64_t)sizeof(float);
-}
-
-int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+static int ppo_grad_impl(rmav_handle h, bool shared, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
                          int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
                          const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
                          void *workspace, float *grad_out, float *stats_out) {
@@ -525,8 +465,12 @@ int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const
                 {params, "params"}, {spec, "spec"}, {workspace, "workspace"}, {grad_out, "grad_out"}, {stats_out, "stats_out"}};
     for (const auto &n : need)
         if (!n.p) return rmav_fail(RMAV_ERR_INVALID, "%s is NULL (required)", n.name);
-    for (int k = 0; k < kTrkParams; ++k)
-        if (!params[k]) return rmav_fail(RMAV_ERR_INVALID, "params[%d] is NULL (9 device pointers: pi W1 b1 W2 b2 W3 b3, vf W b, logstd)", k);
+    const int32_t ns = kStateDim[h->kind], na = kActionDim[h->kind];
+    const FlatLayout lay = flat_layout(shared, ns, na);
+    for (int k = 0; k < lay.n; ++k)
+        if (!params[k])
+            return rmav_fail(RMAV_ERR_INVALID, shared ? "params[%d] is NULL (9 device pointers: pi W1 b1 W2 b2 W3 b3, vf W b, logstd)"
+                                                      : "params[%d] is NULL (13 device pointers: pi W1 b1 W2 b2 W3 b3, vf the same, logstd)", k);
     const int64_t min_pitch = idx ? 1 : batch;
     if (obs_pitch < min_pitch) return rmav_fail(RMAV_ERR_INVALID, "obs_pitch must be >= %lld, got %lld", (long long)min_pitch, (long long)obs_pitch);
     if (act_pitch < min_pitch) return rmav_fail(RMAV_ERR_INVALID, "act_pitch must be >= %lld, got %lld", (long long)min_pitch, (long long)act_pitch);
@@ -535,35 +479,76 @@ int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const
     if (spec->ent_coef - spec->ent_coef != 0.0f) return rmav_fail(RMAV_ERR_INVALID, "ent_coef must be finite, got %g", (double)spec->ent_coef);
     if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "workspace must be 16-byte aligned");
     if (obs_stats && (reinterpret_cast<uintptr_t>(obs_stats) & 15u) != 0) return rmav_fail(RMAV_ERR_INVALID, "obs_stats must be 16-byte aligned");
-    TrunkArgs a;
-    memset(&a, 0, sizeof(a));
-    a.idx = idx;
-    a.obs = obs;
-    a.act = act;
-    a.obs_pitch = obs_pitch;
-    a.act_pitch = act_pitch;
-    a.logp_old = logp_old;
-    a.val_old = val_old;
-    a.adv = adv;
-    a.ret = ret;
-    a.adv_norm = adv_norm;
-    a.norm_tab = obs_stats ? ((const ObsNormStats *)obs_stats)->mean_f : nullptr;
-    a.partial = (float *)workspace;
-    a.clip = spec->clip;
-    a.vf_coef = spec->vf_coef;
-    a.batch = (int32_t)batch;
-    a.ns = kStateDim[h->kind];
-    a.na = kActionDim[h->kind];
-    for (int k = 0; k < kTrkParams; ++k) a.p[k] = params[k];
-    const TrunkLayout lay = trunk_layout(a.ns, a.na);
-    const int32_t n_params = lay.off[kTrkParams];
-    const int groups = learner_groups(batch);   // (kind, batch) alone decide the geometry
-    hipLaunchKernelGGL(k_trunk_grad, dim3((unsigned)groups), dim3(kLrnThreads), 0, h->stream, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_learner_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, h->stream, (const float *)workspace, (int32_t)groups,
-                       n_params + kLrnStats, n_params, lay.off[8], a.na, a.batch, a.vf_coef, spec->ent_coef, params[8], grad_out, stats_out);
+    const auto fill = [&](auto &a) {   // the fields LearnerArgs and TrunkArgs have in common
+        memset(&a, 0, sizeof(a));
+        a.idx = idx;
+        a.obs = obs;
+        a.act = act;
+        a.obs_pitch = obs_pitch;
+        a.act_pitch = act_pitch;
+        a.logp_old = logp_old;
+        a.val_old = val_old;
+        a.adv = adv;
+        a.ret = ret;
+        a.adv_norm = adv_norm;
+        a.norm_tab = obs_stats ? ((const ObsNormStats *)obs_stats)->mean_f : nullptr;
+        a.partial = (float *)workspace;
+        a.clip = spec->clip;
+        a.vf_coef = spec->vf_coef;
+        a.batch = (int32_t)batch;
+        a.ns = ns;
+        a.na = na;
+    };
+    const int32_t n_params = lay.off[lay.n], off_logstd = lay.off[lay.n - 1], pstride = n_params + kLrnStats;
+    const float *logstd = params[lay.n - 1];
+    const dim3 grid((unsigned)learner_groups(batch));   // (kind, batch) alone decide the geometry
+    if (shared) {
+        TrunkArgs a;
+        fill(a);
+        for (int k = 0; k < kTrkParams; ++k) a.p[k] = params[k];
+        hipLaunchKernelGGL(k_trunk_grad, grid, dim3(kLrnThreads), 0, h->stream, a);
+        HIP_TRY(hipGetLastError());
+    } else {
+        LearnerArgs a;
+        fill(a);
+        a.pstride = pstride;
+        a.logstd = logstd;
+        a.off_logstd = off_logstd;
+        a.off_stats = n_params;
+        for (int net = 0; net < 2; ++net) {
+            for (int k = 0; k < 6; ++k) {
+                a.p[k] = params[6 * net + k];
+                a.goff[k] = lay.off[6 * net + k];
+            }
+            if (net == 0) hipLaunchKernelGGL(k_learner_grad<false>, grid, dim3(kLrnThreads), 0, h->stream, a);
+            else hipLaunchKernelGGL(k_learner_grad<true>, grid, dim3(kLrnThreads), 0, h->stream, a);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_learner_fold, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, h->stream, (const float *)workspace, (int32_t)grid.x,
+                       pstride, n_params, off_logstd, na, (int32_t)batch, spec->vf_coef, spec->ent_coef, logstd, grad_out, stats_out);
     HIP_TRY(hipGetLastError());
     return RMAV_OK;
+}
+
+int64_t rmav_ppo_grad_param_count(int kind) { return grad_param_count(false, kind); }
+int64_t rmav_ppo_grad_workspace_bytes(int kind, int64_t batch) { return grad_workspace_bytes(false, kind, batch); }
+int64_t rmav_ppo_grad_shared_param_count(int kind) { return grad_param_count(true, kind); }
+int64_t rmav_ppo_grad_shared_workspace_bytes(int kind, int64_t batch) { return grad_workspace_bytes(true, kind, batch); }
+
+int rmav_ppo_grad(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act, int64_t act_pitch,
+                  const float *logp_old, const float *val_old, const float *adv, const float *ret, const float *adv_norm,
+                  const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec, void *workspace, float *grad_out,
+                  float *stats_out) {
+    return ppo_grad_impl(h, false, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
+                         workspace, grad_out, stats_out);
+}
+int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+                         int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
+                         const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
+                         void *workspace, float *grad_out, float *stats_out) {
+    return ppo_grad_impl(h, true, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
+                         workspace, grad_out, stats_out);
 }
 
 // ---- around the fused learner: the advantage moments it takes and the optimiser step on its gradient, csrc/rmav_optim.hpp ----------------
@@ -597,7 +582,8 @@ int rmav_ppo_adam(rmav_handle h, int shared, const float *grad, float *const *pa
     } need[] = {{grad, "grad"}, {params, "params"}, {exp_avg, "exp_avg"}, {exp_avg_sq, "exp_avg_sq"}, {spec, "spec"}};
     for (const auto &n : need)
         if (!n.p) return rmav_fail(RMAV_ERR_INVALID, "%s is NULL (required)", n.name);
-    const int n_tensors = shared ? kTrkParams : kLrnParams;
+    const FlatLayout lay = flat_layout(shared != 0, kStateDim[h->kind], kActionDim[h->kind]);
+    const int n_tensors = lay.n;
     for (int k = 0; k < n_tensors; ++k)
         if (!params[k]) return rmav_fail(RMAV_ERR_INVALID, "params[%d] is NULL (%d device pointers, in the order of %s)", k, n_tensors,
                                          shared ? "rmav_ppo_grad_shared" : "rmav_ppo_grad");
@@ -614,14 +600,11 @@ int rmav_ppo_adam(rmav_handle h, int shared, const float *grad, float *const *pa
     if (spec->_reserved[0] != 0 || spec->_reserved[1] != 0) return rmav_fail(RMAV_ERR_INVALID, "_reserved must be 0");
     AdamArgs a;
     memset(&a, 0, sizeof(a));
-    const int ns = kStateDim[h->kind], na = kActionDim[h->kind];
-    const LearnerLayout lay = learner_layout(ns, na);
-    const TrunkLayout trk = trunk_layout(ns, na);
     for (int k = 0; k < kAdamMaxTensors; ++k) {
         a.p[k] = k < n_tensors ? params[k] : nullptr;
-        a.off[k] = k < n_tensors ? (shared ? trk.off[k] : lay.off[k]) : 0x7fffffff;
+        a.off[k] = k < n_tensors ? lay.off[k] : 0x7fffffff;
     }
-    a.n = shared ? trk.off[kTrkParams] : lay.off[kLrnParams];
+    a.n = lay.off[n_tensors];
     a.grad = grad;
     a.m = exp_avg;
     a.v = exp_avg_sq;

@@ -583,7 +583,7 @@
                 if constexpr (NORM) pol_std[c] *= ar.noise;   // the action rule: std_eff (noise = 1: the same bits)
                 sl += ls;
             }
-            pol_logp0 = -sl - 0.5f * (float)NA * 1.8378770664093453f;
+            pol_logp0 = -sl - 0.5f * (float)NA * kLog2Pi;
         }
 
         // ACT_BUFFER: actions are prefetched one step ahead

@@ -1151,39 +1151,7 @@ class BatchedQuadrotor:
         ``None``: columns ``0 .. M - 1``.  ``obs_norm``: a ``RunningObsNorm`` (or any 16-byte aligned device buffer of its layout)
         whose tables normalise ``obs``.  Returns ``(grad, stats)``: the flat gradient in the ABI order and ``stats = [loss, pg, vf,
         max ratio]``, both device tensors owned by the env and overwritten by the next call (``out=(grad, stats)`` to supply them)."""
-        f32 = torch.float32
-        M = int(obs.shape[1])
-        assert tuple(obs.shape) == (self.nS, M) and tuple(act.shape) == (self.nA, M) and obs.dtype == f32 and act.dtype == f32
-        assert obs.stride(1) == 1 and act.stride(1) == 1, "obs / act are feature-major with unit stride along the samples"
-        for x in (logp_old, val_old, adv, ret):
-            assert x.dtype == f32 and tuple(x.shape) == (M,) and x.is_contiguous()
-        assert adv_norm.dtype == f32 and adv_norm.numel() == 2 and adv_norm.is_contiguous()
-        ps = [p.detach() for p in policy_params]
-        assert len(ps) == 13 and all(p.is_cuda and p.dtype == f32 and p.is_contiguous() for p in ps), "13 contiguous fp32 CUDA tensors"
-        if idx is not None:
-            assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and idx.is_cuda
-        B = M if idx is None else int(idx.numel())
-        n_par = int(self._lib.rmav_ppo_grad_param_count(self.kind))
-        assert sum(p.numel() for p in ps) == n_par, "the parameters are not those of an MlpPolicy(value_network='copy', hidden=64) of this env"
-        cache = self.__dict__.setdefault("_ppo_grad_cache", {})
-        dev = obs.device
-        if out is None:
-            if "out" not in cache:
-                cache["out"] = (torch.empty(n_par, dtype=f32, device=dev), torch.empty(4, dtype=f32, device=dev))
-            out = cache["out"]
-        grad, stats = out
-        assert grad.dtype == f32 and grad.numel() == n_par and grad.is_contiguous() and stats.dtype == f32 and stats.numel() == 4
-        need = int(self._lib.rmav_ppo_grad_workspace_bytes(self.kind, max(B, 1)))
-        ws = cache.get("ws")
-        if ws is None or ws.numel() < need:
-            ws = cache["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * 13)(*[p.data_ptr() for p in ps])
-        spec = A.PpoGradSpec(float(clip), float(vf_coef), float(ent_coef), 0)
-        pitch = lambda x: int(x.stride(0)) if x.shape[0] > 1 else M  # noqa: E731
-        vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-        A.check(self._lib.rmav_ppo_grad(self._h, B, vp(idx), vp(obs), pitch(obs), vp(act), pitch(act), vp(logp_old), vp(val_old), vp(adv),
-                                        vp(ret), vp(adv_norm), ptrs, vp(obs_norm), C.byref(spec), vp(ws), vp(grad), vp(stats)))
-        return grad, stats
+        return self._ppo_grad(False, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out)
 
     def ppo_grad_shared(self, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip: float = 0.2, vf_coef: float = 0.5,
                         ent_coef: float = 0.0, idx=None, obs_norm=None, out=None):
@@ -1193,6 +1161,13 @@ class BatchedQuadrotor:
         ``MlpPolicy(value_network="shared", hidden=64)``; every other argument, the returned ``(grad, stats)`` (the flat gradient in
         that order) and the caller's contract on ``idx`` are :meth:`ppo_grad`'s.  The cached outputs and the workspace are this
         method's own."""
+        return self._ppo_grad(True, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out)
+
+    def _ppo_grad(self, shared, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out):
+        """The body of :meth:`ppo_grad` (``shared=False``) and :meth:`ppo_grad_shared`: they differ in the tensor count, the three
+        library functions and the cache (outputs and workspace) they own."""
+        n, arch, sfx = (9, "shared", "_shared") if shared else (13, "copy", "")
+        count, ws_bytes, call = (getattr(self._lib, f"rmav_ppo_grad{sfx}{f}") for f in ("_param_count", "_workspace_bytes", ""))
         f32 = torch.float32
         M = int(obs.shape[1])
         assert tuple(obs.shape) == (self.nS, M) and tuple(act.shape) == (self.nA, M) and obs.dtype == f32 and act.dtype == f32
@@ -1201,13 +1176,13 @@ class BatchedQuadrotor:
             assert x.dtype == f32 and tuple(x.shape) == (M,) and x.is_contiguous()
         assert adv_norm.dtype == f32 and adv_norm.numel() == 2 and adv_norm.is_contiguous()
         ps = [p.detach() for p in policy_params]
-        assert len(ps) == 9 and all(p.is_cuda and p.dtype == f32 and p.is_contiguous() for p in ps), "9 contiguous fp32 CUDA tensors"
+        assert len(ps) == n and all(p.is_cuda and p.dtype == f32 and p.is_contiguous() for p in ps), f"{n} contiguous fp32 CUDA tensors"
         if idx is not None:
             assert idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous() and idx.is_cuda
         B = M if idx is None else int(idx.numel())
-        n_par = int(self._lib.rmav_ppo_grad_shared_param_count(self.kind))
-        assert sum(p.numel() for p in ps) == n_par, "the parameters are not those of an MlpPolicy(value_network='shared', hidden=64) of this env"
-        cache = self.__dict__.setdefault("_ppo_grad_shared_cache", {})
+        n_par = int(count(self.kind))
+        assert sum(p.numel() for p in ps) == n_par, f"the parameters are not those of an MlpPolicy(value_network='{arch}', hidden=64) of this env"
+        cache = self.__dict__.setdefault(f"_ppo_grad{sfx}_cache", {})
         dev = obs.device
         if out is None:
             if "out" not in cache:
@@ -1215,16 +1190,16 @@ class BatchedQuadrotor:
             out = cache["out"]
         grad, stats = out
         assert grad.dtype == f32 and grad.numel() == n_par and grad.is_contiguous() and stats.dtype == f32 and stats.numel() == 4
-        need = int(self._lib.rmav_ppo_grad_shared_workspace_bytes(self.kind, max(B, 1)))
+        need = int(ws_bytes(self.kind, max(B, 1)))
         ws = cache.get("ws")
         if ws is None or ws.numel() < need:
             ws = cache["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        ptrs = (C.c_void_p * 9)(*[p.data_ptr() for p in ps])
+        ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in ps])
         spec = A.PpoGradSpec(float(clip), float(vf_coef), float(ent_coef), 0)
         pitch = lambda x: int(x.stride(0)) if x.shape[0] > 1 else M  # noqa: E731
         vp = lambda x: None if x is None else C.c_void_p(x.data_ptr())  # noqa: E731
-        A.check(self._lib.rmav_ppo_grad_shared(self._h, B, vp(idx), vp(obs), pitch(obs), vp(act), pitch(act), vp(logp_old), vp(val_old),
-                                               vp(adv), vp(ret), vp(adv_norm), ptrs, vp(obs_norm), C.byref(spec), vp(ws), vp(grad), vp(stats)))
+        A.check(call(self._h, B, vp(idx), vp(obs), pitch(obs), vp(act), pitch(act), vp(logp_old), vp(val_old), vp(adv), vp(ret), vp(adv_norm),
+                     ptrs, vp(obs_norm), C.byref(spec), vp(ws), vp(grad), vp(stats)))
         return grad, stats
 
     def adv_moments(self, adv, idx=None, out=None):
