@@ -31,7 +31,32 @@ CLEAR = 1e-3
 MARGIN = 10.0
 FLOOR = 2.0 ** -22
 BATCHES = (1, 31, 32, 33, 64, 65, 130, 2125)
+# Batches at which a workgroup walks several tiles (groups = min(tiles, 512)), as (kind, B, statistics, idx route, ent_coef): 514 tiles
+# (workgroups 0 and 1 walk a second one, workgroup 1's a one-sample tail); 1 026 tiles (workgroups 0 and 1 walk three, the rest two,
+# workgroup 1's third a one-sample tail); 2 048 full tiles, four per workgroup, at the widest state
+WALKS = (("quad3d", 32833, True, True, 0.01), ("quad3d", 65601, True, True, 0.01), ("quad3d_sl", 131072, False, False, 0.0))
+# Hyper-parameters other than (CLIP, VF_COEF): (clip, vf_coef, ent_coef) x kind x B
+HYPERS = ((0.1, 1.0, 0.01), (0.3, 0.25, 0.0))
+HYPER_KINDS = ("quad2d_sl", "quad3d")
+HYPER_BATCHES = (130, 2125)
 MODES = ("mixed", "pg_clipped", "vf_clipped")
+
+
+def chain(B):
+    """the longest run of sequential roundings of a kernel sum: 64 over K, 64 per tile and tile after tile in a thread, then the
+    workgroups' partials one after the other"""
+    tiles = -(-B // 64)
+    return 64 + 64 * -(-tiles // 512) + min(tiles, 512)
+
+
+def margin(B):
+    """The factor of the bound err(kernel) <= margin(B) * max(err(torch fp32), FLOOR).  profiles/r23/learner.md rounds MARGIN = 10 for
+    every chain up to the 162 roundings of its largest shape, B = 2125; that holds unchanged: 10 for every B of BATCHES.  (The
+    quotient itself, evaluated with a full tile for the small batches, would be wider there - 21.5 at B = 1 - and is NOT used.)  A
+    longer chain gets the quotient the rule rounds: the kernel's chain over the shortest a blocked or pairwise sum can have,
+    log2 64 + log2 B: 704 / 21.0 = 33.5 at B = 32 833, 768 / 22.0 = 34.9 at 65 601, 832 / 23.0 = 36.2 at 131 072.  Both learners walk
+    their tiles the same way (tile t on workgroup t mod groups: csrc/rmav_learner.hpp), so one rule serves both."""
+    return MARGIN if chain(B) <= 162 else max(MARGIN, chain(B) / (6.0 + math.log2(B)))
 
 
 class TableNorm:

@@ -8,8 +8,8 @@ value head ``vf.0`` on its latent.
   switches for the arithmetic mutants the host test uses: learner_ref's seven and two that cut one head's delta off the trunk.
 * ``make_case`` / ``trained_policy``: the inputs the GPU test and the host test share; built as learner_ref's, from the fp64 SHARED
   policy's outputs, with one more mode (``both_clipped``).
-Everything but ``trained_policy``, ``restate`` and ``margin`` IS learner_ref's function, called with this module's ``ARCH`` record.
-* ``margin``: MARGIN for the chains profiles/r23/learner.md rounded it for, the chain-length rule evaluated for a longer one.
+Everything but ``trained_policy`` and ``restate`` IS learner_ref's function, called with this module's ``ARCH`` record; ``chain`` and
+``margin`` (one tile walk, one rule for both learners) are re-exported from there.
 
 SEED was chosen before any GPU run, on the CPU (profiles/r24/learner_shared.md): among seeds 0..7 the one whose one-element tensor
 ``vf.0.bias`` - the sum of per-sample terms that may cancel - has the mildest worst cancellation sum|d_j| / |sum d_j| over every
@@ -21,28 +21,13 @@ import numpy as np
 import torch
 
 import learner_ref as R
-from learner_ref import BATCHES, CLEAR, CLIP, FLOOR, KINDS, MARGIN, VF_COEF, TableNorm, adv_moments, make_norm  # noqa: F401
+from learner_ref import (BATCHES, CLEAR, CLIP, FLOOR, HYPER_BATCHES, HYPER_KINDS, HYPERS, KINDS, MARGIN, VF_COEF, WALKS, TableNorm,  # noqa: F401
+                         adv_moments, chain, make_norm, margin)
 
 NAMES = tuple(f"pi.{k}.{w}" for k in range(3) for w in ("weight", "bias")) + ("vf.0.weight", "vf.0.bias", "logstd")
 NET = NAMES[:8]   # the eight tensors of the net (everything but logstd)
 SEED = 3   # (worst cancellation 77; the other seven: 206 .. 2906)
 MODES = ("mixed", "pg_clipped", "vf_clipped", "both_clipped")
-
-
-def chain(B):
-    """the longest run of sequential roundings of a kernel sum: 64 over K, 64 per tile and tile after tile in a thread, then the
-    workgroups' partials one after the other"""
-    tiles = -(-B // 64)
-    return 64 + 64 * -(-tiles // 512) + min(tiles, 512)
-
-
-def margin(B):
-    """The factor of the bound err(kernel) <= margin(B) * max(err(torch fp32), FLOOR).  profiles/r23/learner.md rounds MARGIN = 10 for
-    every chain up to the 162 roundings of its largest shape, B = 2125; that holds here unchanged: 10 for every B of BATCHES.  (The
-    quotient itself, evaluated with a full tile for the small batches, would be wider there - 21.5 at B = 1 - and is NOT used.)  A
-    longer chain gets the quotient the rule rounds: the kernel's chain over the shortest a blocked or pairwise sum can have,
-    log2 64 + log2 B: 704 / 21.0 = 33.5 at B = 32 833."""
-    return MARGIN if chain(B) <= 162 else max(MARGIN, chain(B) / (6.0 + math.log2(B)))
 
 
 def trained_policy(kind, seed, norm=None):

@@ -3,7 +3,12 @@ parameter range, a frame skip, a tracking reward, a disturbance, sensor noise, a
 under an episode time limit.  Such a handle runs the top rung's kernels (k_rollout_tc, k_step_tc) with every slot of their argument lists
 taken from a real spec.  Three twin handles with the same seed are driven with the same action buffer: one fused ACT_BUFFER rollout, 8 single
 steps and 8 rmav_step_final calls.  Observations, rewards, done bytes and the final state are bit-equal across the three (the step and the
-rollout kernels round identically: DESIGN.md); no array is excluded."""
+rollout kernels round identically: DESIGN.md); no array is excluded.
+
+This file drives the handle with buffered actions (mode="buffer" rollouts and single steps).  The policy side - the in-kernel actors of
+FusedPolicyCollector on the same handle, and on every cumulative handle below it - is tests/test_gpu_ladder_policy.py, which takes
+all_eight, N, T, H and the HOVER / START tables from here; the sampled draw on such handles is test_every_route_stores_the_same_bits of
+tests/test_gpu_policy_sample.py (variants ds, sn, al, ss, tc, all8)."""
 import disturbance_ref as D
 import numpy as np
 import pytest
@@ -27,8 +32,8 @@ HOVER = {"quad2d": 0.98, "quad3d_sl": None}     # thrust command of the held env
 START = {"quad2d": 0.25, "quad3d_sl": 0.75}     # half-width of the start-state ranges
 
 
-def all_eight(G, kind):
-    return make(G, kind, N, term="spec", max_episode_steps=H, randomize={"mass": (0.8, 1.2)}, frame_skip=2, reward=True,
+def all_eight(G, kind, n=N):
+    return make(G, kind, n, term="spec", max_episode_steps=H, randomize={"mass": (0.8, 1.2)}, frame_skip=2, reward=True,
                 disturbance=TD.dist(G, D.SPEC), sensor_noise=G.SensorNoise(0.25), actuator=G.Actuator(TAUS[NA[kind]], init=INIT[NA[kind]]),
                 start_state=G.StartState(-START[kind], START[kind]))
 

@@ -5,10 +5,10 @@ determinism, the PPO integration and the refusals.
 Tolerance (learner_shared_ref.margin, learner_ref.FLOOR; derived in profiles/r23/learner.md, restated in profiles/r24/learner_shared.md):
 per parameter tensor, err = max|g - g64| / max|g64|,
     err(kernel) <= margin(B) * max(err(torch fp32 learner on the same GPU, same inputs), FLOOR),
-margin(B) = 10 for every B of BATCHES and 33.5 at B = 32 833.
+margin(B) = 10 for every B of BATCHES, 33.5 at B = 32 833, 34.9 at 65 601 and 36.2 at 131 072 (learner_ref.WALKS).
 Measured (MI355X, all 321 cases): kernel errors 2.4e-7 .. 2.3e-6, the quotient err(kernel) / max(err(torch), FLOOR) typically 1.0 .. 3 and
 9.0 at the worst (quad2d_sl, B = 31: the one-element vf.0.bias, whose 31 per-sample terms cancel 42-fold); 1.8 at B = 32 833.  The table
-is in profiles/r24/learner_shared.md."""
+is in profiles/r24/learner_shared.md; the longer walks (2.4 and 4.2) and the other hyper-parameters are in profiles/r28/ladder_policy.md."""
 import copy
 import ctypes as C
 
@@ -66,7 +66,7 @@ def _spread(case, pitch, seed):
     return out, idx
 
 
-def _run(env, pol, case, idx=None, norm_buf=None, ent_coef=0.0):
+def _run(env, pol, case, idx=None, norm_buf=None, ent_coef=0.0, clip=R.CLIP, vf_coef=R.VF_COEF):
     """rmav_ppo_grad_shared on CUDA copies of the case -> (grad, stats) CUDA tensors (clones)"""
     import torch
 
@@ -74,7 +74,7 @@ def _run(env, pol, case, idx=None, norm_buf=None, ent_coef=0.0):
     adv_mb = c["adv"] if idx is None else c["adv"][idx]
     adv_norm = torch.stack(R.adv_moments(adv_mb))
     grad, stats = env.ppo_grad_shared(_params(pol), c["obs"], c["act"], c["logp_old"], c["val_old"], c["adv"], c["ret"], adv_norm,
-                                      clip=R.CLIP, vf_coef=R.VF_COEF, ent_coef=ent_coef, idx=idx, obs_norm=norm_buf)
+                                      clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, idx=idx, obs_norm=norm_buf)
     return grad.clone(), stats.clone()
 
 
@@ -138,8 +138,7 @@ def test_two_tiles_per_workgroup_against_the_fp64_oracle(envs):
     _check(kind, B, f"norm=1 ent={ent} idx=1", g, s, g64, s64, gy, sy)
 
 
-@pytest.mark.parametrize("kind", ["quad2d_sl", "quad3d"])
-def test_clipped_branches_give_exact_zeros(envs, kind):
+def _exact_zeros(envs, kind, clip=R.CLIP, vf_coef=R.VF_COEF):
     import torch
 
     env, sl = envs(kind), R.slices(kind)
@@ -152,21 +151,33 @@ def test_clipped_branches_give_exact_zeros(envs, kind):
 
     # every sample's clipped surrogate branch strictly active: nothing reaches the mean head, logstd keeps the entropy term alone; the
     # trunk still learns from the value head
-    g, _ = _run(env, pol, R.make_case(kind, 130, SEED, mode="pg_clipped"), ent_coef=0.01)
+    g, _ = _run(env, pol, R.make_case(kind, 130, SEED, mode="pg_clipped", clip=clip), ent_coef=0.01, clip=clip, vf_coef=vf_coef)
     g = g.cpu()
     assert zero(g, "pi.2.weight") and zero(g, "pi.2.bias"), "the mean head's gradient must be bitwise zero"
     assert torch.equal(g[logstd], torch.full((n_ls,), -0.01)), g[logstd]   # 0 - ent_coef: one exact rounding
     assert g[trunk].abs().max() > 0 and g[sl["vf.0.weight"]].abs().max() > 0
     # v_clip's branch active everywhere with |v - val_old| > clip: nothing reaches the value head; the trunk learns from the mean head
-    g, _ = _run(env, pol, R.make_case(kind, 130, SEED, mode="vf_clipped"))
+    g, _ = _run(env, pol, R.make_case(kind, 130, SEED, mode="vf_clipped", clip=clip), clip=clip, vf_coef=vf_coef)
     g = g.cpu()
     assert zero(g, "vf.0.weight") and zero(g, "vf.0.bias"), "the value head's gradient must be bitwise zero"
     assert g[trunk].abs().max() > 0 and g[sl["pi.2.weight"]].abs().max() > 0 and g[logstd].abs().max() > 0
     # both: every tensor but logstd
-    g, _ = _run(env, pol, R.make_case(kind, 130, SEED, mode="both_clipped"), ent_coef=0.01)
+    g, _ = _run(env, pol, R.make_case(kind, 130, SEED, mode="both_clipped", clip=clip), ent_coef=0.01, clip=clip, vf_coef=vf_coef)
     g = g.cpu()
     assert torch.equal(g[:logstd.start], torch.zeros(logstd.start)), "the whole net's gradient must be bitwise zero"
     assert torch.equal(g[logstd], torch.full((n_ls,), -0.01)), g[logstd]
+
+
+@pytest.mark.parametrize("kind", ["quad2d_sl", "quad3d"])
+def test_clipped_branches_give_exact_zeros(envs, kind):
+    _exact_zeros(envs, kind)
+
+
+@pytest.mark.parametrize("kind", ["quad2d_sl", "quad3d"])
+def test_clipped_branches_give_exact_zeros_at_clip_0_1(envs, kind):
+    """the batches drawn for clip = 0.1 (ratios from 1.2 and 0.8 on, |v - val_old| from 0.15 on): a kernel that kept 0.2 would let
+    gradient through on the samples between the two clips"""
+    _exact_zeros(envs, kind, *R.HYPERS[0][:2])
 
 
 @pytest.mark.parametrize("B", [2125, 70001])
@@ -186,6 +197,101 @@ def test_same_inputs_same_bits_and_idx_equals_gathered(envs, B):
     g3, s3 = _run(env, pol, spread, idx.cuda(), buf, 0.01)
     assert torch.equal(g1, g3) and torch.equal(s1, s3), "the idx route must give the bits of the gathered-contiguous route"
     assert g1.abs().max() > 0 and torch.isfinite(g1).all()
+
+
+# ---- the tile walk, the hyper-parameters, the pitches and the workspace ---------------------------------------------------------------
+@pytest.mark.parametrize("kind,B,with_norm,use_idx,ent", R.WALKS[1:])
+def test_several_tiles_per_workgroup_against_the_fp64_oracle(envs, kind, B, with_norm, use_idx, ent):
+    """The training loop's regime (groups = min(tiles, 512), a 65 536 x 32 rollout in four minibatches walks 16 tiles per workgroup):
+    accumulators carried in registers from tile to tile, h1 / h2 overwritten in place by the deltas of every tile.  learner_ref.WALKS
+    behind B = 32 833, which test_two_tiles_per_workgroup_against_the_fp64_oracle runs:
+    B = 65 601 = 1 026 tiles - workgroups 0 and 1 walk three, the rest two, workgroup 1's third is a one-sample tail - with
+    statistics, through idx; B = 131 072 = 2 048 full tiles, four per workgroup, at nS = 16, contiguous.  margin(B) is the chain rule
+    of profiles/r23/learner.md evaluated (34.9 and 36.2), not a new number."""
+    env = envs(kind)
+    tiles = -(-B // 64)
+    assert tiles > 512 and (B % 64 in (0, 1)), "more tiles than workgroups; full tiles, or a one-sample tail"
+    norm = R.make_norm(kind, SEED) if with_norm else None
+    case = R.make_case(kind, B, SEED, norm)
+    g64, s64, clear = R.oracle(kind, SEED, case, norm, ent_coef=ent)
+    assert min(clear.values()) >= R.CLEAR, clear
+    gy, sy = R.torch_learner(R.trained_policy(kind, SEED, norm.to(device="cuda") if with_norm else None).cuda(), case, ent_coef=ent)
+    pol, buf = R.trained_policy(kind, SEED).cuda(), (norm.buffer("cuda") if with_norm else None)
+    if use_idx:
+        spread, idx = _spread(case, B + 37, 11 + B)
+        g, s = _run(env, pol, spread, idx.cuda(), buf, ent)
+    else:
+        g, s = _run(env, pol, case, None, buf, ent)
+    _check(kind, B, f"norm={int(with_norm)} ent={ent} idx={int(use_idx)}", g, s, g64, s64, gy, sy)
+
+
+@pytest.mark.parametrize("B", R.HYPER_BATCHES)
+@pytest.mark.parametrize("kind", R.HYPER_KINDS)
+@pytest.mark.parametrize("clip,vf_coef,ent", R.HYPERS)
+def test_other_hyper_parameters_against_the_fp64_oracle(envs, kind, B, clip, vf_coef, ent):
+    """clip, vf_coef and ent_coef away from the (0.2, 0.5) every other case passes: a literal anywhere between the binding and the
+    kernel would land 5.8e4 x outside this bound (the host test's mutants).  The batch is drawn for the case's clip."""
+    env = envs(kind)
+    case = R.make_case(kind, B, SEED, clip=clip)
+    g64, s64, clear = R.oracle(kind, SEED, case, clip=clip, vf_coef=vf_coef, ent_coef=ent)
+    assert min(clear.values()) >= R.CLEAR, clear
+    gy, sy = R.torch_learner(R.trained_policy(kind, SEED).cuda(), case, clip=clip, vf_coef=vf_coef, ent_coef=ent)
+    pol = R.trained_policy(kind, SEED).cuda()
+    spread, idx = _spread(case, B + 37, 11 + B)
+    for use_idx in (False, True):
+        g, s = _run(env, pol, spread if use_idx else case, idx.cuda() if use_idx else None, None, ent, clip, vf_coef)
+        _check(kind, B, f"clip={clip} vf_coef={vf_coef} ent={ent} idx={int(use_idx)}", g, s, g64, s64, gy, sy)
+
+
+@pytest.mark.parametrize("use_idx", (False, True))
+def test_unequal_pitches_give_the_bits_of_the_contiguous_call(envs, use_idx):
+    """obs_pitch and act_pitch are separate arguments of the ABI (the binding takes each from its array's stride(0)): obs rows M + 37
+    apart, act rows M + 101 apart, the 1-D arrays of length M - the gradient and the statistics of the contiguous call, bit for bit."""
+    import torch
+
+    kind, B, ent = "quad3d", 130, 0.01
+    env = envs(kind)
+    pol = R.trained_policy(kind, SEED).cuda()
+    norm = R.make_norm(kind, SEED)
+    buf = norm.buffer("cuda")
+    case, idx = R.make_case(kind, B, SEED, norm), None
+    if use_idx:
+        case, idx = _spread(case, B + 37, 11 + B)
+        idx = idx.cuda()
+    M = case["adv"].numel()
+    g1, s1 = _run(env, pol, case, idx, buf, ent)
+    wide = {k: v.cuda() for k, v in case.items()}
+    gen = torch.Generator().manual_seed(5)
+    for key, extra in (("obs", 37), ("act", 101)):   # finite filler behind every row, which the launch must not read
+        full = (torch.randn(case[key].shape[0], M + extra, generator=gen) * 3.0).cuda()
+        full[:, :M] = wide[key]
+        wide[key] = full[:, :M]
+        assert wide[key].stride() == (M + extra, 1) and not wide[key].is_contiguous()
+    g2, s2 = _run(env, pol, wide, idx, buf, ent)
+    assert torch.equal(g1, g2) and torch.equal(s1, s2)
+    assert g1.abs().max() > 0 and torch.isfinite(g1).all()
+
+
+def test_a_grown_workspace_is_reused_by_smaller_and_larger_batches(G):
+    """The binding keeps one workspace per handle and grows it: B = 2 125, then 65, then 2 125 on ONE handle, each result the bits of
+    the same call on a fresh handle (a smaller batch must not fold partials a larger one left behind)."""
+    import torch
+
+    kind, ent = "quad3d", 0.01
+    pol = R.trained_policy(kind, SEED).cuda()
+    norm = R.make_norm(kind, SEED)
+    buf = norm.buffer("cuda")
+    one = G.BatchedQuadrotor(kind, 64, seed=0)
+    for B in (2125, 65, 2125):
+        case = R.make_case(kind, B, SEED, norm)
+        fresh = G.BatchedQuadrotor(kind, 64, seed=0)
+        g0, s0 = _run(fresh, pol, case, None, buf, ent)
+        g1, s1 = _run(one, pol, case, None, buf, ent)
+        torch.cuda.synchronize()
+        fresh.close()
+        assert torch.equal(g0, g1) and torch.equal(s0, s1), B
+        assert g0.abs().max() > 0 and torch.isfinite(g0).all()
+    one.close()
 
 
 def test_ppo_fused_learner_leaves_the_torch_paths_gradients(G):

@@ -25,6 +25,11 @@ pytestmark = pytest.mark.gpu
 
 H = 2                      # the time limit of the tl / tl_boot variants: every env ends at least two episodes inside T = 5 steps
 CLIP = (-0.05, 0.05)       # binds on most components (|B3| >= 0.09, std >= 0.3)
+# the actuator of the `al` / `all8` variants, per action count: one time constant per component (one of them: no lag)
+UPPER = {"ds": ("disturbance",), "sn": ("sensor_noise",), "al": ("actuator",), "ss": ("start_state",), "tc": ("termination",),
+         "all8": ("disturbance", "sensor_noise", "actuator", "start_state", "termination", "reward")}
+UPPER_TAUS = {2: (0.01, 0.02), 4: (0.01, 0.02, 0.015, 0.0)}
+UPPER_INIT = {2: (1.5, -0.25), 4: (1.5, -0.25, 0.125, 0.0)}
 
 
 @pytest.fixture(scope="module")
@@ -44,14 +49,26 @@ def _launch(G, actor, kind, n, variant="plain", group=None, base=BASE, t0=0, ste
     from gym_reinmav_amd.ppo import FusedPolicyCollector
 
     kw = {}
-    if variant in ("tl", "tl_boot"):
+    if variant in ("tl", "tl_boot", "all8"):
         kw["max_episode_steps"] = H
-    if variant == "ranged":
+    if variant in ("ranged", "all8"):
         kw["randomize"] = {"mass": (0.8, 1.25)}
-    if variant == "skip3":
+    if variant in ("skip3", "all8"):
         kw["frame_skip"] = 3
-    if variant == "reward":
+    if variant in ("reward", "all8"):
         kw["reward"] = G.TrackingReward(alive=1.0, w_pos=1.0, w_vel=0.1, w_act=0.01, terminal=-10.0)
+    # the five upper rungs of the feature ladder, one at a time and (all8) on top of each other and of the four lower features
+    if variant in ("ds", "all8"):
+        kw["disturbance"] = G.Disturbance(wind=((-1.0, 1.0), (-0.5, 0.75), (0.0, 0.5)), gust=(0.5, 0.25, 0.125), hold=3)
+    if variant in ("sn", "all8"):
+        kw["sensor_noise"] = G.SensorNoise(0.25)
+    if variant in ("al", "all8"):
+        kw["actuator"] = G.Actuator(UPPER_TAUS[dims(kind)[1]], init=UPPER_INIT[dims(kind)[1]])
+    if variant in ("ss", "all8"):
+        kw["start_state"] = G.StartState(-0.75, 0.75)
+    if variant in ("tc", "all8"):
+        d = 2 if kind.startswith("quad2d") else 3
+        kw["termination"] = G.Termination(pos_lo=(-0.97,) * d, pos_hi=(0.97,) * d, max_tilt=0.5 if d == 2 else 1.6)
     env = G.BatchedQuadrotor(kind, n, seed=SEED, env_id_base=base, **kw)
     if t0:
         env.step_count = t0
@@ -65,19 +82,21 @@ def _launch(G, actor, kind, n, variant="plain", group=None, base=BASE, t0=0, ste
         env.set_state(env.get_state() + np.random.RandomState(0).normal(scale=0.1, size=(n, 13)).astype(np.float32))
     else:
         env.set_state(random_cases(kind, n, seed=5)[0])
+    for feature in UPPER.get(variant, ()):
+        assert getattr(env, feature) is not None, (variant, feature)
     if variant == "norm":
         torch.manual_seed(2)
         on = RunningObsNorm(env.nS, f"cuda:{env.device}", clip=2.0)
         on.update(torch.randn(64, env.nS, n, device="cuda") * 1.7 + 0.4, env=env)
         pol.obs_norm = on
     col = FusedPolicyCollector(env, pol, steps, f32_mfma=(False if actor == "fp32" else None), bf16_mfma=actor.startswith("bf16"),
-                               f16_mfma=(actor == "f16"), bootstrap_truncated=(variant == "tl_boot"), clip_actions=(CLIP if variant == "clip" else False))
+                               f16_mfma=(actor == "f16"), bootstrap_truncated=(variant in ("tl_boot", "all8")), clip_actions=(CLIP if variant == "clip" else False))
     assert col.actor == ("bf16" if actor == "bf16_1w" else actor)
     col.collect()
     torch.cuda.synchronize()
     assert env.step_count == t0 + steps     # frame skip: the counter advances per agent step
     act, logp, done = col.act.cpu().numpy().transpose(0, 2, 1), col.logp.cpu().numpy(), col.done.cpu().numpy()
-    if variant in ("tl", "tl_boot"):
+    if variant in ("tl", "tl_boot", "all8"):
         assert (done.sum(0) >= 2).all()   # the comparison runs through two resets of every env (terminated, or truncated after H steps)
     env.close()
     return act, logp
@@ -207,11 +226,16 @@ def test_every_route_stores_the_same_bits(G, kind):
     """Under the zero-head policy the mean is B3 in every actor (a zero weight adds exact zeros) and std = expf(logstd) in every kernel,
     so the stored action and the log-probability are the same statement on the same operands everywhere: the two fp32 actors, the bf16
     pair and one-wavefront routes, the f16 and shared-trunk pairs at 1 and 4 pairs per workgroup, and the time-limited, bootstrap,
-    normalised, ranged, frame-skip, tracking-reward and clipped kernels of the three actors that have them store identical bits."""
+    normalised, ranged, frame-skip, tracking-reward and clipped kernels of the three actors that have them store identical bits.  So do
+    the kernels of the five upper rungs of the feature ladder (ds: disturbance, sn: sensor noise, al: actuator lag, ss: start-state
+    ranges, tc: termination spec - whose noise, lag and resets change every observation but not the zero-head mean) and all8, every
+    feature at once under a time limit with the bootstrap term, at the automatic choice and at 1 and 4 pairs per workgroup."""
     n = 130
     ref = _launch(G, "fp32", kind, n)
     routes = [(a, "plain", None) for a in ACTORS[1:]] + [(a, "plain", g) for a in ("bf16", "f16", "f16_shared") for g in (1, 4)]
     routes += [(a, v, None) for a in ("fp32_mfma", "f16", "f16_shared") for v in ("tl", "tl_boot", "norm", "ranged", "skip3", "reward", "clip")]
+    upper = ("fp32_mfma", "f16", "f16_shared")
+    routes += [(a, v, None) for a in upper for v in ("ds", "sn", "al", "ss", "tc", "all8")] + [(a, "all8", g) for a in upper for g in (1, 4)]
     differ = []
     for actor, variant, group in routes:
         act, logp = _launch(G, actor, kind, n, variant, group)

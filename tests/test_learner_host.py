@@ -66,6 +66,53 @@ def test_mutants_land_a_decade_outside_the_gpu_bound(kind, B, mutant):
     assert worst >= 10.0, (mutant, worst, em)
 
 
+def test_the_margin_of_the_walks_is_the_chain_rule_evaluated():
+    """one rule for both learners (learner_shared_ref re-exports it): MARGIN up to the 162 roundings of B = 2125, the quotient beyond"""
+    import learner_ref
+    import learner_shared_ref
+
+    assert learner_shared_ref.margin is learner_ref.margin and learner_shared_ref.chain is learner_ref.chain
+    assert [R.margin(B) for B in R.BATCHES] == [R.MARGIN] * len(R.BATCHES)
+    assert [R.chain(B) for _, B, *_ in R.WALKS] == [64 + 128 + 512, 64 + 192 + 512, 64 + 256 + 512]
+    assert [round(R.margin(B), 1) for _, B, *_ in R.WALKS] == [33.5, 34.9, 36.2]
+
+
+@pytest.mark.parametrize("kind,B,with_norm,use_idx,ent", R.WALKS)
+def test_the_walks_keep_their_clearances(kind, B, with_norm, use_idx, ent):
+    """the batches at which a workgroup walks several tiles: the same three distances, and the tile counts the GPU test names"""
+    tiles = -(-B // 64)
+    assert (tiles, B % 64) in ((514, 1), (1026, 1), (2048, 0)) and -(-tiles // 512) in (2, 3, 4)
+    norm = R.make_norm(kind, SEED) if with_norm else None
+    case = R.make_case(kind, B, SEED, norm)
+    _, _, clear = R.oracle(kind, SEED, case, norm, ent_coef=ent)
+    assert min(clear.values()) >= R.CLEAR, clear
+    assert case["adv"].min() < 0 < case["adv"].max()
+
+
+@pytest.mark.parametrize("B", R.HYPER_BATCHES)
+@pytest.mark.parametrize("kind", R.HYPER_KINDS)
+@pytest.mark.parametrize("clip,vf_coef,ent", R.HYPERS)
+def test_a_kept_default_lands_outside_the_gpu_bound(kind, B, clip, vf_coef, ent):
+    """The GPU test's other hyper-parameters: the batch drawn for the case's clip keeps its clearances, the clean restatement is
+    inside margin(B) * max(err of the fp32 learner, FLOOR), and a restatement that keeps clip = 0.2 or vf_coef = 0.5 - a literal
+    somewhere between the binding and the kernel - lands more than a decade outside it."""
+    assert clip != R.CLIP and vf_coef != R.VF_COEF
+    case = R.make_case(kind, B, SEED, clip=clip)
+    g64, s64, clear = R.oracle(kind, SEED, case, clip=clip, vf_coef=vf_coef, ent_coef=ent)
+    assert min(clear.values()) >= R.CLEAR, clear
+    g32, _ = R.torch_learner(R.trained_policy(kind, SEED), case, clip=clip, vf_coef=vf_coef, ent_coef=ent)
+    bound = {n: R.margin(B) * max(e, R.FLOOR) for n, e in R.tensor_errors(kind, g32, g64).items()}
+    P = R.params64(R.trained_policy(kind, SEED))
+    g, stats = R.restate(P, case, clip=clip, vf_coef=vf_coef, ent_coef=ent)
+    clean = R.tensor_errors(kind, g, g64)
+    assert all(clean[n] <= bound[n] for n in bound)
+    np.testing.assert_allclose(stats, s64, rtol=1e-12, atol=1e-13)
+    for kept in (dict(clip=R.CLIP, vf_coef=vf_coef), dict(clip=clip, vf_coef=R.VF_COEF)):
+        em = R.tensor_errors(kind, R.restate(P, case, ent_coef=ent, **kept)[0], g64)
+        worst = max(em[n] / bound[n] for n in bound)
+        assert worst >= 10.0, (kept, worst, em)
+
+
 @pytest.mark.parametrize("kind", sorted(R.KINDS))
 def test_the_gpu_inputs_keep_their_clearances(kind):
     """every (B, statistics) case the GPU test runs: ratios away from 1 +- clip, |v - val_old| away from clip, the two vf terms apart"""
