@@ -81,6 +81,9 @@ def main():
     ap.add_argument("--fused-optimizer", dest="fused_optimizer", action="store_true",
                     help="with --fused-learner: the advantage moments, the norm clip and Adam in HIP too (rmav_adv_moments, rmav_ppo_adam: "
                          "one launch instead of clip_grad_norm_ + Adam.step()); the optimiser's state stays torch.optim.Adam's")
+    ap.add_argument("--matrix-learner", dest="matrix_learner", action="store_true",
+                    help="with --fused-learner and --value-network shared: the fused learner's products on the fp32 matrix cores "
+                         "(rmav_ppo_grad_shared_mfma); the same precision class, another order of summation")
     ap.add_argument("--save_path", default=None)
     ap.add_argument("--load_path", default=None)
     ap.add_argument("--play", action="store_true", help="after training: run the policy (mean action) on one env and print its path")
@@ -94,6 +97,8 @@ def main():
         ap.error("--bootstrap_truncated needs --max_episode_steps")
     if args.fused_optimizer and not args.fused_learner:
         ap.error("--fused-optimizer needs --fused-learner")
+    if args.matrix_learner and not (args.fused_learner and args.value_network == "shared"):
+        ap.error("--matrix-learner needs --fused-learner and --value-network shared")
     if args.value_network == "shared" and args.actor == "bf16":
         ap.error("--value-network shared runs on the f16 shared-trunk actor, not with --actor bf16")
     randomize = {}
@@ -153,7 +158,7 @@ def main():
                                       frame_skip=args.frame_skip, reward=reward, disturbance=disturbance, sensor_noise=sensor_noise,
                                       actuator=actuator, start_state=start_state, termination=termination)
     learner = PPO(policy, lr=1e-3, reward_scale=args.reward_scale, ret_norm=ret_norm, fused_learner=args.fused_learner,
-                  fused_optimizer=args.fused_optimizer)
+                  fused_optimizer=args.fused_optimizer, matrix_learner=args.matrix_learner)
     iters = int(args.num_timesteps // (args.num_env * args.nsteps))
     t0 = time.perf_counter()
     for it in range(iters):

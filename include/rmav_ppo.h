@@ -315,6 +315,26 @@ int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const
                          const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
                          void *workspace, float *grad_out, float *stats_out);
 
+/* ---- the shared-trunk learner on the fp32 matrix cores: the same loss and gradient, every product on v_mfma_f32_32x32x2_f32 ------------
+ * rmav_ppo_grad_shared with another net kernel (csrc/rmav_learner_mfma.hpp): the loss, the sub-gradient rules, the arithmetic of x, the
+ * statistics, the 9 parameters, the flat gradient (rmav_ppo_grad_shared_param_count(kind) floats in that order) and the two launches
+ * (the net, then the same fold) are those of the block above.  The fp32-input matrix instruction is a k-ordered fmaf chain: the result
+ * is in the precision class of rmav_ppo_grad_shared and differs from it in the order of summation only.
+ *   geometry      a wavefront owns a tile of 32 samples, a workgroup of 4 wavefronts a step of 128; step s belongs to workgroup
+ *                 s mod workgroups, workgroups = min(ceil(batch / 128), 256): one workgroup per CU (124.5 KB of LDS)
+ *   determinism   no atomics; sample j sits in lane j mod 32 of wavefront (j / 32) mod 4 of step j / 128 with or without idx (the idx
+ *                 route gives the bits of the gathered route); a wavefront adds its tiles in order, a workgroup its wavefronts in
+ *                 order, the fold the workgroups in order; geometry and order depend on (kind, batch) alone, so the same inputs give
+ *                 the same bits.  A lane beyond batch reads the last sample's column and adds exact zeros.
+ * Bytes of the caller-owned DEVICE workspace: workgroups * (rmav_ppo_grad_shared_param_count(kind) + 4) * 4 with the workgroups above;
+ * the rules of rmav_ppo_grad_workspace_bytes.  -1 for a bad kind or batch < 1. */
+int64_t rmav_ppo_grad_shared_mfma_workspace_bytes(int kind, int64_t batch);
+/* The arguments of rmav_ppo_grad_shared with the same meaning, checks and messages; workspace has the size the function above gives. */
+int rmav_ppo_grad_shared_mfma(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+                              int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
+                              const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
+                              void *workspace, float *grad_out, float *stats_out);
+
 /* ---- around the fused learner: the advantage moments it takes, and the optimiser step on its gradient --------------------------------
  * rmav_adv_moments writes the two floats rmav_ppo_grad / rmav_ppo_grad_shared take as adv_norm:
  *     adv_norm_out[0] = mean_j x_j,   adv_norm_out[1] = 1 / (std + 1e-8),   x_j = adv[idx[j]] (idx NULL: adv[j]),  j < batch

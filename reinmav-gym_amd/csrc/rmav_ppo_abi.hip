@@ -1,5 +1,5 @@
 // rmav_ppo_abi.hip - the C ABI of include/rmav_ppo.h: policy weights, the policy-in-kernel rollouts (their kernels are launched from
-// rmav_policy_abi.hip), GAE, the observation / return normalisers, the fused learners (rmav_ppo_grad, rmav_ppo_grad_shared) and what
+// rmav_policy_abi.hip), GAE, the observation / return normalisers, the fused learners (rmav_ppo_grad, rmav_ppo_grad_shared, rmav_ppo_grad_shared_mfma) and what
 // runs around them in a minibatch (rmav_adv_moments, rmav_ppo_adam).
 #include <cmath>
 #include <cstdint>
@@ -11,6 +11,7 @@
 #include "rmav_ret_norm.hpp"   // (brings rmav_gae.hpp)
 #include "rmav_learner.hpp"
 #include "rmav_learner_shared.hpp"
+#include "rmav_learner_mfma.hpp"
 #include "rmav_optim.hpp"
 
 using namespace rmav;
@@ -427,7 +428,7 @@ int rmav_gae_norm(rmav_handle h, int32_t n_steps, const float *rew, const uint8_
 }
 
 // ---- the fused learners: loss and gradient of one PPO minibatch, csrc/rmav_learner.hpp (value_network="copy": one launch per net) and
-// csrc/rmav_learner_shared.hpp ("shared": one launch), then the one fold ----------------------------------------------------------------
+// csrc/rmav_learner_shared.hpp ("shared": one launch; on the matrix cores: csrc/rmav_learner_mfma.hpp), then the one fold ----------------------------------------------------------------
 // The flat gradient of either learner (the ABI order of include/rmav_ppo.h): n tensors, their offsets, the total in off[n]; logstd is last
 struct FlatLayout {
     int32_t n;
@@ -447,12 +448,14 @@ static int64_t grad_param_count(bool shared, int kind) {
     const FlatLayout lay = flat_layout(shared, kStateDim[kind], kActionDim[kind]);
     return lay.off[lay.n];
 }
-static int64_t grad_workspace_bytes(bool shared, int kind, int64_t batch) {
+// (matrix: the shared-trunk learner on the matrix cores, csrc/rmav_learner_mfma.hpp - another net kernel with a geometry of its own)
+static int grad_groups(bool matrix, int64_t batch) { return matrix ? matrix_groups(batch) : learner_groups(batch); }
+static int64_t grad_workspace_bytes(bool shared, int kind, int64_t batch, bool matrix = false) {
     if (kind < 0 || kind >= kNumKinds || batch < 1) return -1;
-    return (int64_t)learner_groups(batch) * (grad_param_count(shared, kind) + kLrnStats) * (int64_t)sizeof(float);
+    return (int64_t)grad_groups(matrix, batch) * (grad_param_count(shared, kind) + kLrnStats) * (int64_t)sizeof(float);
 }
 
-static int ppo_grad_impl(rmav_handle h, bool shared, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+static int ppo_grad_impl(rmav_handle h, bool shared, bool matrix, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
                          int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
                          const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
                          void *workspace, float *grad_out, float *stats_out) {
@@ -501,12 +504,13 @@ static int ppo_grad_impl(rmav_handle h, bool shared, int64_t batch, const int64_
     };
     const int32_t n_params = lay.off[lay.n], off_logstd = lay.off[lay.n - 1], pstride = n_params + kLrnStats;
     const float *logstd = params[lay.n - 1];
-    const dim3 grid((unsigned)learner_groups(batch));   // (kind, batch) alone decide the geometry
+    const dim3 grid((unsigned)grad_groups(matrix, batch));   // (kind, batch) alone decide the geometry
     if (shared) {
         TrunkArgs a;
         fill(a);
         for (int k = 0; k < kTrkParams; ++k) a.p[k] = params[k];
-        hipLaunchKernelGGL(k_trunk_grad, grid, dim3(kLrnThreads), 0, h->stream, a);
+        if (matrix) hipLaunchKernelGGL(k_matrix_grad, grid, dim3(kMatThreads), 0, h->stream, a);
+        else hipLaunchKernelGGL(k_trunk_grad, grid, dim3(kLrnThreads), 0, h->stream, a);
         HIP_TRY(hipGetLastError());
     } else {
         LearnerArgs a;
@@ -535,19 +539,27 @@ int64_t rmav_ppo_grad_param_count(int kind) { return grad_param_count(false, kin
 int64_t rmav_ppo_grad_workspace_bytes(int kind, int64_t batch) { return grad_workspace_bytes(false, kind, batch); }
 int64_t rmav_ppo_grad_shared_param_count(int kind) { return grad_param_count(true, kind); }
 int64_t rmav_ppo_grad_shared_workspace_bytes(int kind, int64_t batch) { return grad_workspace_bytes(true, kind, batch); }
+int64_t rmav_ppo_grad_shared_mfma_workspace_bytes(int kind, int64_t batch) { return grad_workspace_bytes(true, kind, batch, true); }
 
 int rmav_ppo_grad(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act, int64_t act_pitch,
                   const float *logp_old, const float *val_old, const float *adv, const float *ret, const float *adv_norm,
                   const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec, void *workspace, float *grad_out,
                   float *stats_out) {
-    return ppo_grad_impl(h, false, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
+    return ppo_grad_impl(h, false, false, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
                          workspace, grad_out, stats_out);
 }
 int rmav_ppo_grad_shared(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
                          int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
                          const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
                          void *workspace, float *grad_out, float *stats_out) {
-    return ppo_grad_impl(h, true, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
+    return ppo_grad_impl(h, true, false, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
+                         workspace, grad_out, stats_out);
+}
+int rmav_ppo_grad_shared_mfma(rmav_handle h, int64_t batch, const int64_t *idx, const float *obs, int64_t obs_pitch, const float *act,
+                              int64_t act_pitch, const float *logp_old, const float *val_old, const float *adv, const float *ret,
+                              const float *adv_norm, const float *const *params, const void *obs_stats, const rmav_ppo_grad_spec *spec,
+                              void *workspace, float *grad_out, float *stats_out) {
+    return ppo_grad_impl(h, true, true, batch, idx, obs, obs_pitch, act, act_pitch, logp_old, val_old, adv, ret, adv_norm, params, obs_stats, spec,
                          workspace, grad_out, stats_out);
 }
 

@@ -229,6 +229,9 @@ PROTOTYPES = {
     "rmav_ppo_grad_shared_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
     "rmav_ppo_grad_shared": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.POINTER(C.c_void_p),
                                        _vp, C.POINTER(PpoGradSpec), _vp, _fp, _fp]),
+    "rmav_ppo_grad_shared_mfma_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "rmav_ppo_grad_shared_mfma": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, C.c_int64, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp,
+                                            C.POINTER(C.c_void_p), _vp, C.POINTER(PpoGradSpec), _vp, _fp, _fp]),
     "rmav_adv_moments_workspace_bytes": (C.c_int64, [C.c_int64]),
     "rmav_adv_moments": (C.c_int, [C.c_void_p, C.c_int64, _vp, _fp, _vp, _fp]),
     "rmav_ppo_adam": (C.c_int, [C.c_void_p, C.c_int, _fp, C.POINTER(C.c_void_p), _fp, _fp, C.c_int64, C.POINTER(PpoAdamSpec), _fp]),

@@ -1151,7 +1151,7 @@ class BatchedQuadrotor:
         ``None``: columns ``0 .. M - 1``.  ``obs_norm``: a ``RunningObsNorm`` (or any 16-byte aligned device buffer of its layout)
         whose tables normalise ``obs``.  Returns ``(grad, stats)``: the flat gradient in the ABI order and ``stats = [loss, pg, vf,
         max ratio]``, both device tensors owned by the env and overwritten by the next call (``out=(grad, stats)`` to supply them)."""
-        return self._ppo_grad(False, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out)
+        return self._ppo_grad("", policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out)
 
     def ppo_grad_shared(self, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip: float = 0.2, vf_coef: float = 0.5,
                         ent_coef: float = 0.0, idx=None, obs_norm=None, out=None):
@@ -1161,13 +1161,23 @@ class BatchedQuadrotor:
         ``MlpPolicy(value_network="shared", hidden=64)``; every other argument, the returned ``(grad, stats)`` (the flat gradient in
         that order) and the caller's contract on ``idx`` are :meth:`ppo_grad`'s.  The cached outputs and the workspace are this
         method's own."""
-        return self._ppo_grad(True, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out)
+        return self._ppo_grad("_shared", policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out)
 
-    def _ppo_grad(self, shared, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out):
-        """The body of :meth:`ppo_grad` (``shared=False``) and :meth:`ppo_grad_shared`: they differ in the tensor count, the three
-        library functions and the cache (outputs and workspace) they own."""
-        n, arch, sfx = (9, "shared", "_shared") if shared else (13, "copy", "")
-        count, ws_bytes, call = (getattr(self._lib, f"rmav_ppo_grad{sfx}{f}") for f in ("_param_count", "_workspace_bytes", ""))
+    def ppo_grad_shared_mfma(self, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip: float = 0.2, vf_coef: float = 0.5,
+                             ent_coef: float = 0.0, idx=None, obs_norm=None, out=None):
+        """:meth:`ppo_grad_shared` on the fp32 matrix cores (``rmav_ppo_grad_shared_mfma``, include/rmav_ppo.h): the same loss, the same
+        9 tensors and flat gradient, every product on ``v_mfma_f32_32x32x2_f32`` - the precision class of :meth:`ppo_grad_shared`,
+        another order of summation.  Every argument and the returned ``(grad, stats)`` are that method's; the cached outputs and the
+        workspace are this method's own."""
+        return self._ppo_grad("_shared_mfma", policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm,
+                              out)
+
+    def _ppo_grad(self, sfx, policy_params, obs, act, logp_old, val_old, adv, ret, adv_norm, clip, vf_coef, ent_coef, idx, obs_norm, out):
+        """The body of :meth:`ppo_grad` (``sfx=""``), :meth:`ppo_grad_shared` (``"_shared"``) and :meth:`ppo_grad_shared_mfma`
+        (``"_shared_mfma"``): they differ in the tensor count, the library functions and the cache (outputs and workspace) they own."""
+        n, arch = (9, "shared") if sfx.startswith("_shared") else (13, "copy")
+        count = getattr(self._lib, f"rmav_ppo_grad{'_shared' if n == 9 else ''}_param_count")   # (the matrix kernel's is the shared one's)
+        ws_bytes, call = (getattr(self._lib, f"rmav_ppo_grad{sfx}{f}") for f in ("_workspace_bytes", ""))
         f32 = torch.float32
         M = int(obs.shape[1])
         assert tuple(obs.shape) == (self.nS, M) and tuple(act.shape) == (self.nA, M) and obs.dtype == f32 and act.dtype == f32

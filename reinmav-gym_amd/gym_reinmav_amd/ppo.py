@@ -672,7 +672,8 @@ class PPO:
 
     def __init__(self, policy: MlpPolicy, lr: float = 3e-4, clip: float = 0.2, epochs: int = 4, minibatches: int = 4,
                  vf_coef: float = 0.5, ent_coef: float = 0.0, max_grad_norm: float = 0.5, gamma: float = 0.99,
-                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None, fused_learner: bool = False, fused_optimizer: bool = False):
+                 lam: float = 0.95, reward_scale: float = 1.0, ret_norm=None, fused_learner: bool = False, fused_optimizer: bool = False,
+                 matrix_learner: bool = False):
         """``fused_learner=True``: every minibatch's loss and gradients come from the fused learner instead of torch autograd
         (``value_network="copy"``: ``rmav_ppo_grad``, one launch per net plus a fold, csrc/rmav_learner.hpp; ``"shared"``:
         ``rmav_ppo_grad_shared``, one launch for the trunk and both heads plus the fold, csrc/rmav_learner_shared.hpp); the
@@ -690,6 +691,11 @@ class PPO:
         flat buffer) holds the UNCLIPPED gradient on this path - on a data-parallel run the ranks' sum - and ``update`` also returns
         ``grad_norm``, the pre-clip norm of the last minibatch.  The default keeps today's path, bit for bit.
 
+        ``matrix_learner=True`` (needs ``fused_learner=True`` and an ``MlpPolicy(value_network="shared", hidden=64)``; anything else is
+        a ``ValueError``): the minibatch's loss and gradients come from ``rmav_ppo_grad_shared_mfma`` (csrc/rmav_learner_mfma.hpp), the
+        shared-trunk learner with every product on the fp32 matrix cores - the same precision class, another order of summation.  It
+        works with ``fused_optimizer`` on or off.  The default keeps today's path, bit for bit.
+
         ``ret_norm`` (a :class:`~gym_reinmav_amd.ret_norm.RunningReturnNorm`): baselines' ``VecNormalize(ret=True)`` in front of
         GAE - ``update`` first merges the rollout's discounted returns into it, then computes the advantages from rewards scaled by
         the statistics that already include them (``ret_norm.py``); ``ro.rew`` stays raw.  ``self.adv`` / ``self.ret`` keep the
@@ -705,6 +711,11 @@ class PPO:
         self.fused_optimizer = bool(fused_optimizer)
         if self.fused_optimizer and not self.fused_learner:
             raise ValueError("fused_optimizer=True needs fused_learner=True: rmav_ppo_adam steps on the flat gradient the fused learner leaves")
+        self.matrix_learner = bool(matrix_learner)
+        if self.matrix_learner and not self.fused_learner:
+            raise ValueError("matrix_learner=True needs fused_learner=True: it selects the fused learner's kernel (rmav_ppo_grad_shared_mfma)")
+        if self.matrix_learner and not getattr(policy, "shared", False):
+            raise ValueError('matrix_learner=True computes an MlpPolicy(value_network="shared", hidden=64): this policy is not a shared-trunk one')
         self._fused_opt = None   # a _FusedOptState: built by the first fused step
         self._fused = None   # (the 13 or 9 parameters in the ABI order, the flat gradient, its views): built by the first fused update
         if self.fused_learner:
@@ -755,6 +766,8 @@ class PPO:
             std, mean = torch.std_mean(adv[idx])   # the two reductions the launch does not do
             adv_norm = torch.stack((mean, 1.0 / (std + 1e-8)))
         grad_fn = env.ppo_grad_shared if getattr(self.policy, "shared", False) else env.ppo_grad
+        if self.matrix_learner:
+            grad_fn = env.ppo_grad_shared_mfma
         grad_fn(ps, obs, act, logp_old, val_old, adv, ret, adv_norm, clip=self.clip, vf_coef=self.vf_coef, ent_coef=self.ent_coef,
                 idx=idx, obs_norm=getattr(self.policy, "obs_norm", None), out=(flat, stats))
         if not self.fused_optimizer:

@@ -2,7 +2,8 @@
 """A/B of the PPO learner: torch autograd (PPO.update as it always was) against the fused learner (PPO(fused_learner=True) ->
 rmav_ppo_grad), in ONE process, alternating, on the same rollouts.
 
-    python tools/learner_ab.py [--envs 65536] [--steps 32] [--rounds 6] [--value-network copy|shared] [--out profiles/r23/learner_ab.json]
+    python tools/learner_ab.py [--envs 65536] [--steps 32] [--rounds 6] [--value-network copy|shared] [--fused-optimizer | --matrix-learner]
+                                  [--out profiles/r23/learner_ab.json]
 
 Shape: quadrotor3d, the per-GPU shape of the PPO benchmark (65 536 envs x 32 steps, 4 epochs x 4 minibatches of 524 288 samples).
 Reports, as one JSON object (also written to --out):
@@ -25,7 +26,14 @@ gradients from the fused learner; "off" is the path without the flag), same alte
   update_ms        as above, per path ("off", "on")
   call_us          us per rmav_adv_moments call next to torch.std_mean(adv[idx]) + the stack it replaces, and per rmav_ppo_adam call next
                    to clip_grad_norm_ + Adam.step() on the same gradient (HIP events, median of 20)
-  end_to_end       env-steps/s of collect + update on each path (fp32 matrix-core actor, or f16_shared)"""
+  end_to_end       env-steps/s of collect + update on each path (fp32 matrix-core actor, or f16_shared)
+
+--matrix-learner (with --value-network shared): the A/B is the vector-ALU shared-trunk kernel (rmav_ppo_grad_shared) against the
+matrix-core one (rmav_ppo_grad_shared_mfma, PPO(matrix_learner=True)), both with the fused optimiser on, same alternation, same rollouts:
+  update_ms        as above, per path ("vector", "matrix"), with the spread max - min of each
+  grad_us          us per call of each kernel (net + fold) on one minibatch: in every round 20 calls of each, the order alternating;
+                   median and min over the rounds' medians, and the round-to-round spread (max - min of the rounds' medians)
+  end_to_end       env-steps/s of collect + update on each path (f16_shared actor)"""
 import argparse
 import copy
 import json
@@ -139,6 +147,79 @@ def main_optimizer(args):
     finish(res, args.out)
 
 
+def main_matrix(args):
+    import torch
+
+    import gym_reinmav_amd as g
+    from gym_reinmav_amd.ppo import PPO, FusedPolicyCollector, MlpPolicy
+
+    if args.value_network != "shared":
+        raise SystemExit("--matrix-learner needs --value-network shared (the matrix-core learner computes the shared-trunk policy)")
+    torch.manual_seed(0)
+    N, T = args.envs, args.steps
+    res = {"shape": {"kind": "quad3d", "envs": N, "steps": T, "epochs": 4, "minibatches": 4, "minibatch": N * T // 4,
+                     "value_network": "shared", "fused_optimizer": True}, "device": torch.cuda.get_device_name(0)}
+    env = g.BatchedQuadrotor("quad3d", N, seed=0)
+    pols = {"vector": MlpPolicy(env.nS, env.nA, value_network="shared").cuda()}
+    pols["matrix"] = copy.deepcopy(pols["vector"])
+    ppos = {k: PPO(p, fused_learner=True, fused_optimizer=True, matrix_learner=(k == "matrix")) for k, p in pols.items()}
+    ro = FusedPolicyCollector(env, pols["vector"], T)
+    B = N * T
+    idx = torch.randperm(B, device="cuda")[:B // 4]
+    ms, us = {"vector": [], "matrix": []}, {"vector": [], "matrix": []}
+    fns = {"vector": env.ppo_grad_shared, "matrix": env.ppo_grad_shared_mfma}
+    for r in range(args.rounds + 1):   # round 0 warms both paths up
+        ro.collect()
+        order = ("vector", "matrix") if r % 2 == 0 else ("matrix", "vector")
+        for k in order:
+            t, st = timed(lambda: ppos[k].update(ro), torch)
+            if r:
+                ms[k].append(t)
+        # one call of each kernel on one minibatch of this rollout, in the same order
+        obs = ro.obs[:T].permute(1, 0, 2).reshape(env.nS, B)
+        act = ro.act.permute(1, 0, 2).reshape(env.nA, B)
+        logp, val = ro.logp.reshape(-1), ro.val[:T].reshape(-1).contiguous()
+        adv, ret = ppos["vector"].adv.reshape(-1), ppos["vector"].ret.reshape(-1)
+        an = torch.stack((adv[idx].mean(), 1.0 / (adv[idx].std() + 1e-8)))
+        ps = ppos["vector"]._fused[0]
+        for k in order:
+            ts = []
+            for _ in range(23):
+                t, _ = timed(lambda: fns[k](ps, obs, act, logp, val, adv, ret, an, idx=idx), torch)
+                ts.append(t * 1e3)
+            if r:
+                us[k].append(statistics.median(ts[3:]))
+        ro.roll_over()
+
+    def summary(v):
+        return {"median": statistics.median(v), "min": min(v), "max": max(v), "spread": max(v) - min(v), "all": v}
+
+    res["update_ms"] = {k: summary(v) for k, v in ms.items()}
+    res["grad_us"] = {k: summary(v) for k, v in us.items()}
+    res["grad_us"]["samples"] = B // 4
+    res["grad_speedup_median"] = res["grad_us"]["vector"]["median"] / res["grad_us"]["matrix"]["median"]
+    res["update_speedup_median"] = res["update_ms"]["vector"]["median"] / res["update_ms"]["matrix"]["median"]
+    flop = 6 * (env.nS * 64 + 64 * 64 + 64 * (env.nA + 1)) * (B // 4)
+    res["flop"] = {"per_minibatch": flop, "roofline_tflops": MATRIX_FP32_TFLOPS,
+                   "of_matrix_fp32_roofline": {k: flop / res["grad_us"][k]["median"] / 1e6 / MATRIX_FP32_TFLOPS for k in ("vector", "matrix")}}
+    res["end_to_end"] = {}
+    for k in ("vector", "matrix"):
+        col = FusedPolicyCollector(env, pols[k], T)
+        rates = []
+        for r in range(4):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            col.collect()
+            ppos[k].update(col)
+            col.roll_over()
+            torch.cuda.synchronize()
+            if r:
+                rates.append(N * T / (time.perf_counter() - t0))
+        res["end_to_end"][f"f16_shared/{k}"] = {"env_steps_per_s_median": statistics.median(rates), "all": rates}
+    env.close()
+    finish(res, args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=65536)
@@ -146,8 +227,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--value-network", dest="value_network", default="copy", choices=["copy", "shared"])
     ap.add_argument("--fused-optimizer", dest="fused_optimizer", action="store_true")
+    ap.add_argument("--matrix-learner", dest="matrix_learner", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.matrix_learner:
+        return main_matrix(args)
     if args.fused_optimizer:
         return main_optimizer(args)
     import torch
